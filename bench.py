@@ -17,8 +17,14 @@ run are timed in the same process and reported under `extra`.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks ITSELF (child
 processes, before anything touches the GPU); under `python -m torch.distributed.run ... bench.py --gpus N` it is
-one of the ranks.  Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP events on the launch stream)
-and `cpu_baseline` (the oracle's restatement of the cull on this box's host cores: a reported baseline).
+one of the ranks.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).
+`--full` adds everything else, each leg timed in runs of its own after the headline: `roofline` (dominant kernel, HIP events on
+the launch stream), the oracle's bit-exact check of the list, `cpu_baseline` (the oracle's restatement of the cull on the host's
+cores: a reported baseline), the N = 1 secondary legs under `extra` and, at N > 1, the step breakdown, the other gather
+modes and the weak-scaled run.  `--dump-outputs DIR` writes what the timed call left for its caller after the last timed step
+(`dump_outputs`).
 """
 import argparse
 import concurrent.futures
@@ -55,6 +61,11 @@ def parse_args(argv=None):
     ap.add_argument("--timeout", type=float, default=0.0, help="launcher: kill the ranks and fail after this many seconds (0 = none)")
     ap.add_argument("--dist", choices=["baseline", "small"], default="baseline",
                     help="baseline = BASELINE.md §3 (S in [0.25,4]); small = S in [0.02,0.6] (more culled)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (see the module docstring); the three "
+                         "--no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the draw list and count of the last timed step to DIR/*.npy (float64; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs (emit_draws, BVH build, TLAS, ...)")
@@ -199,6 +210,35 @@ def scaling_ceiling(n_total, world, vis, weak):
             "full_M_inst_per_s": round(n_total / full / 1e3, 1), "shard_M_inst_per_s": round(n_total / own / 1e3, 1),
             "model": "max(8us, shard*145.1B/6.5TB/s) + [25us all-gather, assumed] + 6us + list bytes/5.5TB/s (DESIGN.md 6); "
                      "full = every GPU writes the whole list, shard = its own part only"}
+
+
+DUMP_ROWS = 1 << 20      # draw-list rows --dump-outputs writes at most: 40 MiB of commands + 8 MiB of row numbers
+DUMP_SEED = 20_250_607
+
+
+def dump_outputs(out_dir, d_list, d_count):
+    """`--dump-outputs DIR`: what the caller of the timed call receives - the ordered draw list d_list[0 .. count) and the
+    count - as float64 .npy files (every field of a command is a 32-bit integer, so float64 holds it exactly):
+      draw_count.npy  [1]         the count;
+      draws.npy       [rows, 5]   vertex_count, instance_count, base_index, vertex_offset, base_instance;
+      draw_rows.npy   [rows]      which rows of the list draws.npy holds: all of them up to DUMP_ROWS, beyond that DUMP_ROWS
+                                  rows drawn without replacement by a fixed seed, in list order."""
+    import numpy as np
+    import torch
+    count = int(d_count[0].item())
+    if not 0 <= count <= d_list.numel() // 20:       # a lost count word reads 0xffffffff (= -1 here): never index past the buffer
+        raise RuntimeError(f"bench.py: draw count {count} outside the output buffer ({d_list.numel() // 20} commands)")
+    if count <= DUMP_ROWS:
+        rows = np.arange(count, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(count, size=DUMP_ROWS, replace=False))
+    cmds = d_list[: count * 20].view(torch.int32).view(-1, 5)[torch.from_numpy(rows).to(d_list.device)].cpu().numpy()
+    draws = cmds.view(np.uint32).astype(np.float64)
+    draws[:, 3] = cmds[:, 3]                          # vertex_offset is the one signed field
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "draw_count.npy"), np.array([count], dtype=np.float64))
+    np.save(os.path.join(out_dir, "draws.npy"), draws)
+    np.save(os.path.join(out_dir, "draw_rows.npy"), rows.astype(np.float64))
 
 
 def latest_pmc(kind="cull"):
@@ -414,9 +454,14 @@ def run_rank(args):
     mode = args.gather if distributed else "full"
     step = step_fn(mode)
     ms_per_step = timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:           # before anything below runs the kernels again
+        if distributed and mode != "shard":
+            dump_outputs(args.dump_outputs, d_all, d_cnt_all)
+        else:
+            dump_outputs(args.dump_outputs, d_out, d_cnt)
 
     breakdown, gather_modes, weak_line, bvh_replicas = None, None, None, None
-    if distributed:
+    if distributed and args.full:
         # where a step goes at this N (every rank runs every leg; max over ranks, like the headline): the local cull to a
         # bitmask, the RCCL all-gather of the masks alone, and the expansion of ALL shards to the full draw list
         leg = lambda fn: round(timed(fn, args.steps, 1), 4)
@@ -490,35 +535,36 @@ def run_rank(args):
     ctx.cull_compact_dev(cam, d_m, n_mesh, d_i, n, d_out, d_cnt, False, lo)
     torch.cuda.synchronize()
     count = int(d_cnt[0].item())
-
-    # Kernel-level timing: HIP events recorded by the library on the launch stream around each pass of
-    # vd_cull_compact (large inputs run two passes: cull -> bitmask + mesh id, then expansion).
-    barrier()
-    ctx.set_timing(True)
-    k_all, k_cull, k_expand = [], [], []
-    for _ in range(args.steps):
-        ctx.cull_compact_dev(cam, d_m, n_mesh, d_i, n, d_out, d_cnt, False, lo)
-        k_all.append(ctx.last_gpu_ms())
-        k_cull.append(ctx.last_gpu_ms_stage(0))
-        k_expand.append(ctx.last_gpu_ms_stage(1))
-    ctx.set_timing(False)
-    step_kernel_ms = sum(k_all) / len(k_all)
-    split = min(k_cull) > 0
     vis = count / max(n, 1)
-    step_bytes = n * (144.0 + 20.0 * vis)          # 144 B read + 20 B per survivor
-    if split:
-        id_bytes = vdist.id_width(n_mesh)
-        kernel_name = "cull_mask_tiled_kernel"
-        kernel_ms = sum(k_cull) / len(k_cull)
-        alg_bytes = n * (144.0 + 0.125 + id_bytes)  # 144 B instance read + 1 bit written + the compact mesh id (compared; rewritten when it changed)
-        expand_ms = sum(k_expand) / len(k_expand)
-        expand_bytes = n * (0.125 + id_bytes) + count * 20.0
-    else:
-        kernel_name, kernel_ms, alg_bytes, expand_ms, expand_bytes = "cull_compact_kernel", step_kernel_ms, step_bytes, None, None
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+
+    if args.full:
+        # Kernel-level timing: HIP events recorded by the library on the launch stream around each pass of
+        # vd_cull_compact (large inputs run two passes: cull -> bitmask + mesh id, then expansion).
+        barrier()
+        ctx.set_timing(True)
+        k_all, k_cull, k_expand = [], [], []
+        for _ in range(args.steps):
+            ctx.cull_compact_dev(cam, d_m, n_mesh, d_i, n, d_out, d_cnt, False, lo)
+            k_all.append(ctx.last_gpu_ms())
+            k_cull.append(ctx.last_gpu_ms_stage(0))
+            k_expand.append(ctx.last_gpu_ms_stage(1))
+        ctx.set_timing(False)
+        step_kernel_ms = sum(k_all) / len(k_all)
+        split = min(k_cull) > 0
+        step_bytes = n * (144.0 + 20.0 * vis)          # 144 B read + 20 B per survivor
+        if split:
+            id_bytes = vdist.id_width(n_mesh)
+            kernel_name = "cull_mask_tiled_kernel"
+            kernel_ms = sum(k_cull) / len(k_cull)
+            alg_bytes = n * (144.0 + 0.125 + id_bytes)  # 144 B instance read + 1 bit written + the compact mesh id (compared; rewritten when it changed)
+            expand_ms = sum(k_expand) / len(k_expand)
+            expand_bytes = n * (0.125 + id_bytes) + count * 20.0
+        else:
+            kernel_name, kernel_ms, alg_bytes, expand_ms, expand_bytes = "cull_compact_kernel", step_kernel_ms, step_bytes, None, None
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
 
     verified, cpu, near, list_crc = None, None, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import ref  # checker + cpu_baseline leg only
         threads = os.cpu_count() or 1
         if not args.no_verify:
@@ -579,12 +625,12 @@ def run_rank(args):
         extra["gather_modes"] = gather_modes
     if weak_line:
         extra["weak_scaling"] = weak_line
-    if not args.no_extra and rank == 0 and not distributed:   # single-GPU extras (no collective; N > 1 runs skip them)
+    if args.full and not args.no_extra and rank == 0 and not distributed:   # single-GPU extras (no collective; N > 1 runs skip them)
         extra.update(single_gpu_extras(args, ctx, dev, cam, meshes, d_m, inst, d_i, d_out, d_cnt, n, lo, count))
 
     traffic = None
     pmc_path = latest_pmc()
-    if rank == 0 and pmc_path and n == 10_000_000 and args.dist == "baseline":
+    if args.full and rank == 0 and pmc_path and n == 10_000_000 and args.dist == "baseline":
         # HBM bytes per launch of the dominant kernel from separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`
         # passes of this same command (profiles/README.md); gfx950: FETCH_SIZE counts 64 B per 128-B request
         pmc = json.load(open(pmc_path)).get(kernel_name)
@@ -628,24 +674,25 @@ def run_rank(args):
                        "visible_fraction": round(vis, 4), "distribution": args.dist, "parallelism": par,
                        "verified_bit_exact_vs_oracle": verified, "draw_list_crc32": list_crc, "near_frustum_plane": near,
                        "input_gen_s": round(t_gen, 1)},
-            "roofline": {"bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": (os.path.join("profiles", os.path.basename(pmc_path)) +
-                                                                " (separate rocprofv3 --pmc passes of this command, committed; not re-measured by this run)") if traffic else None,
-                         "kernel_ms": round(kernel_ms, 4),
-                         "algorithmic_bytes_per_launch": int(alg_bytes),
-                         "second_kernel": None if not split else {
-                             "kernel": "mask_scan_kernel + expand_mask_u8_kernel", "kernel_ms": round(expand_ms, 4),
-                             "algorithmic_bytes_per_launch": int(expand_bytes),
-                             "achieved": round(expand_bytes / (expand_ms * 1e-3) / 1e9, 1)},
-                         "step": {"kernels_ms": round(step_kernel_ms, 4), "algorithmic_bytes": int(step_bytes),
-                                  "achieved": round(step_bytes / (step_kernel_ms * 1e-3) / 1e9, 1),
-                                  "frac": round(step_bytes / (step_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}},
-            "cpu_baseline": cpu,
-            "extra": extra,
         }
-        promote_second_metric(line, extra)
-        line["scaling_ceiling"] = scaling_ceiling(n_total, world, vis if not distributed else count / max(n, 1), weak)
+        if args.full:
+            line["roofline"] = {"bound": "hbm", "kernel": kernel_name, "achieved": round(achieved, 1),
+                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                                "traffic": traffic, "traffic_source": (os.path.join("profiles", os.path.basename(pmc_path)) +
+                                                                       " (separate rocprofv3 --pmc passes of this command, committed; not re-measured by this run)") if traffic else None,
+                                "kernel_ms": round(kernel_ms, 4),
+                                "algorithmic_bytes_per_launch": int(alg_bytes),
+                                "second_kernel": None if not split else {
+                                    "kernel": "mask_scan_kernel + expand_mask_u8_kernel", "kernel_ms": round(expand_ms, 4),
+                                    "algorithmic_bytes_per_launch": int(expand_bytes),
+                                    "achieved": round(expand_bytes / (expand_ms * 1e-3) / 1e9, 1)},
+                                "step": {"kernels_ms": round(step_kernel_ms, 4), "algorithmic_bytes": int(step_bytes),
+                                         "achieved": round(step_bytes / (step_kernel_ms * 1e-3) / 1e9, 1),
+                                         "frac": round(step_bytes / (step_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
+            line["cpu_baseline"] = cpu
+            line["extra"] = extra
+            promote_second_metric(line, extra)
+            line["scaling_ceiling"] = scaling_ceiling(n_total, world, vis if not distributed else count / max(n, 1), weak)
         if rccl_info:
             line["config"]["rccl"] = rccl_info
         if breakdown:

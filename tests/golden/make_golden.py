@@ -229,6 +229,7 @@ def helmet_case():
     (prim,) = doc.primitives()
     v, i = prim.arrays()
     assert v.shape == (14556, 3) and i.shape == (46356,)
+    helmet_geometry_glb(src)
     nodes, idx = ref.bvh_build(v, i)
     T = np.eye(4); T[:3, 3] = (0.0, 0.0, 9.0)
     ((M, _, _),) = doc.scene_instances(T @ np.diag([3.0, 3.0, 3.0, 1.0]))
@@ -246,6 +247,37 @@ def helmet_case():
                         instances=inst, meshes=infos, tlas=tl, camera=cam, width=np.uint32(160), height=np.uint32(160),
                         hit=hits["hit"].astype(np.uint8), dist=hits["dist"], triangle=hits["triangle"])
     print("helmet: nodes", len(nodes), "hits", int(hits["hit"].sum()))
+
+
+def helmet_geometry_glb(src):
+    """tests/golden/helmet_geometry.glb: the helmet's glTF-Binary cut to the geometry GltfDocument reads, so that the test of
+    the reader and of helmet.npz needs no file outside the repository.  The asset's first three buffer views - indices,
+    POSITION, NORMAL - are copied byte for byte at their offsets with their accessor, mesh, node and scene entries; the UVs,
+    material, textures and images after them are dropped."""
+    import json
+    import struct
+    raw = open(src, "rb").read()
+    (jlen,) = struct.unpack_from("<I", raw, 12)
+    doc = json.loads(raw[20:20 + jlen])
+    (blen,) = struct.unpack_from("<I", raw, 20 + jlen)
+    binary = raw[28 + jlen:28 + jlen + blen]
+    ((mesh, (prim,)),) = [(m, m["primitives"]) for m in doc["meshes"]]
+    at = prim["attributes"]
+    assert [prim["indices"], at["POSITION"], at["NORMAL"]] == [0, 1, 2]
+    assert [doc["accessors"][k]["bufferView"] for k in range(3)] == [0, 1, 2]
+    views = doc["bufferViews"][:3]
+    end = views[2]["byteOffset"] + views[2]["byteLength"]
+    assert all(w["byteOffset"] >= end for w in doc["bufferViews"][3:])
+    out = {"asset": doc["asset"], "scene": doc["scene"], "scenes": doc["scenes"], "nodes": doc["nodes"],
+           "meshes": [{"name": mesh["name"], "primitives": [{"attributes": {"NORMAL": 2, "POSITION": 1}, "indices": 0}]}],
+           "accessors": doc["accessors"][:3], "bufferViews": views, "buffers": [{"byteLength": end}]}
+    js = json.dumps(out).encode()
+    js += b" " * (-len(js) % 4)
+    body = binary[:end] + b"\0" * (-end % 4)
+    chunks = struct.pack("<II", len(js), 0x4E4F534A) + js + struct.pack("<II", len(body), 0x004E4942) + body
+    with open(os.path.join(OUT, "helmet_geometry.glb"), "wb") as f:
+        f.write(struct.pack("<III", 0x46546C67, 2, 12 + len(chunks)) + chunks)
+    print("helmet_geometry.glb", 12 + len(chunks), "bytes")
 
 
 

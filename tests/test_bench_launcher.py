@@ -136,3 +136,41 @@ def test_second_metric_is_promoted_into_the_keys_a_reader_keeps():
     bare = {"roofline": {}, "cpu_baseline": None}
     bench.promote_second_metric(bare, {})
     assert bare == {"roofline": {}, "cpu_baseline": None}
+
+
+def test_dump_outputs_writes_the_list_exactly_and_samples_a_long_one(tmp_path, monkeypatch):
+    """--dump-outputs: the count and the commands as float64, every 32-bit field exact (vertex_offset signed); a list longer
+    than DUMP_ROWS is a fixed seeded sample in list order; a count the buffer cannot hold is refused before any indexing."""
+    import torch
+    import bench
+    rng = np.random.default_rng(3)
+    cmds = rng.integers(-2**31, 2**31, size=(50, 5)).astype(np.int32)
+    d_list = torch.from_numpy(cmds.view(np.uint8).reshape(-1).copy())
+    load = lambda d, f: np.load(os.path.join(d, f))
+    for count, rows_cap in ((37, 1 << 20), (37, 8), (0, 8)):
+        monkeypatch.setattr(bench, "DUMP_ROWS", rows_cap)
+        d = str(tmp_path / f"{count}_{rows_cap}")
+        bench.dump_outputs(d, d_list, torch.tensor([count, 0, 0, 0], dtype=torch.int32))
+        rows, draws = load(d, "draw_rows.npy"), load(d, "draws.npy")
+        assert load(d, "draw_count.npy").tolist() == [count] and draws.dtype == np.float64 and rows.dtype == np.float64
+        assert len(rows) == min(count, rows_cap) and draws.shape == (len(rows), 5)
+        assert np.all(np.diff(rows) > 0) and (rows.size == 0 or rows[-1] < count)
+        r = rows.astype(np.int64)
+        assert np.array_equal(draws[:, [0, 1, 2, 4]], cmds[r][:, [0, 1, 2, 4]].view(np.uint32).astype(np.float64))
+        assert np.array_equal(draws[:, 3], cmds[r, 3].astype(np.float64))
+        again = str(tmp_path / "again")
+        bench.dump_outputs(again, d_list, torch.tensor([count, 0, 0, 0], dtype=torch.int32))
+        assert all(open(os.path.join(d, f), "rb").read() == open(os.path.join(again, f), "rb").read() for f in os.listdir(d))
+    for bad in (-1, 51):
+        try:
+            bench.dump_outputs(str(tmp_path / "bad"), d_list, torch.tensor([bad, 0, 0, 0], dtype=torch.int32))
+            raise AssertionError(f"count {bad} accepted")
+        except RuntimeError:
+            pass
+
+
+def test_a_plain_run_is_the_headline_only():
+    import bench
+    a = bench.parse_args(["--steps", "7"])
+    assert a.steps == 7 and a.full is False and a.dump_outputs is None
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full is True

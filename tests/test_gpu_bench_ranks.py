@@ -26,7 +26,7 @@ def _bench(*argv, env=None):
 
 @pytest.mark.parametrize("gather", ["full", "indices", "draws", "shard"])
 def test_two_ranks_one_gpu_equal_single_gpu(gather):
-    common = ["--instances", "3000001", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"]
+    common = ["--instances", "3000001", "--steps", "3", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline"]
     one = _bench("--gpus", "1", *common)
     two = _bench("--gpus", "2", "--gather", gather, *common, env={"VOIDIN_DIST_BACKEND": "gloo"})
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
@@ -42,7 +42,7 @@ def test_two_ranks_one_gpu_equal_single_gpu(gather):
 
 
 def test_weak_scaling_mode_two_ranks():
-    two = _bench("--gpus", "2", "--scaling", "weak", "--instances", "1000000", "--steps", "2", "--warmup", "1", "--no-extra",
+    two = _bench("--gpus", "2", "--scaling", "weak", "--instances", "1000000", "--steps", "2", "--warmup", "1", "--full", "--no-extra",
                  "--no-cpu-baseline", env={"VOIDIN_DIST_BACKEND": "gloo"})
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and two["config"]["instances_total"] == 2000000
     assert two["config"]["verified_bit_exact_vs_oracle"] is True
@@ -51,7 +51,7 @@ def test_weak_scaling_mode_two_ranks():
 def test_two_ranks_report_the_second_metric_and_the_weak_run():
     """Without --no-extra an N > 1 line also carries BASELINE's second metric at N GPUs - one BLAS build per rank, replicas
     only, the same nodes on every rank - and the weak-scaled run next to the strong headline."""
-    two = _bench("--gpus", "2", "--instances", "400000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--bvh-u", "128", "--bvh-v", "64",
+    two = _bench("--gpus", "2", "--instances", "400000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--bvh-u", "128", "--bvh-v", "64",
                  env={"VOIDIN_DIST_BACKEND": "gloo"})
     rep = two["extra"]["bvh_build_replicas"]
     assert rep["ranks"] == 2 and rep["tris_per_rank"] == 2 * 128 * 64 and rep["same_nodes_on_every_rank"] is True and rep["value"] > 0
@@ -60,7 +60,7 @@ def test_two_ranks_report_the_second_metric_and_the_weak_run():
 
 
 def test_eight_ranks_default_command_finishes_in_time_and_carries_the_scaling_keys():
-    """The command the driver's 8-GPU tier runs - `bench.py --gpus 8 --steps K --warmup W` (here with --no-extra) at the DEFAULT
+    """The command the driver's 8-GPU tier runs - `bench.py --gpus 8 --steps K --warmup W` (here with --full --no-extra) at the DEFAULT
     10 M instances - end to end on one GPU: the launcher, every rank's input generation, the C-ABI exchange (vd_dist_*, RCCL bound
     through $VD_RCCL_LIB = the tests' double, tests/cpp/fake_rccl.cpp; real RCCL refuses eight ranks on one device), all four
     gather modes, and rank 0's verification of the WHOLE gathered list against the oracle.  Wall clock < 120 s, so that an
@@ -76,7 +76,7 @@ def test_eight_ranks_default_command_finishes_in_time_and_carries_the_scaling_ke
         env = {"VD_RCCL_LIB": build_fake(), "VD_FAKE_RCCL_DIR": d, "VD_FAKE_RCCL_TIMEOUT_S": "120", "VOIDIN_RANKS_SHARE_GPUS": "1",
                "HSA_ENABLE_IPC_MODE_LEGACY": "0", "OMP_NUM_THREADS": "4"}
         t0 = time.time()
-        line = _bench("--gpus", "8", "--steps", "20", "--warmup", "5", "--no-extra", "--timeout", "300", env=env)
+        line = _bench("--gpus", "8", "--steps", "20", "--warmup", "5", "--full", "--no-extra", "--timeout", "300", env=env)
         wall = time.time() - t0
     finally:
         shutil.rmtree(d, ignore_errors=True)
@@ -92,5 +92,5 @@ def test_eight_ranks_default_command_finishes_in_time_and_carries_the_scaling_ke
     assert set(line["extra"]["gather_modes"]) >= {"full", "draws", "indices", "shard"}
     assert line["scaling_ceiling"]["mask_allgather_ms_measured"] == line["step_breakdown"]["mask_allgather_ms"]
     # the ordered list of the whole scene is the one-GPU list (same CRC as the N = 1 line of the same workload)
-    one = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline")
+    one = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline")
     assert one["config"]["draw_list_crc32"] == line["config"]["draw_list_crc32"]

@@ -11,18 +11,18 @@ O=gpurun_out/round
 rm -rf $O; mkdir -p $O
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -q -m gpu --durations=8 2>&1 | tail -14 | tee $O/${R}_pytest_gpu.log
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tee $O/${R}_smoke.log
-echo "== bench"; timeout 900 python bench.py 2>&1 | grep -v amdgpu.ids | grep '^{' | tail -1 > $O/${R}_bench_line.json; cut -c1-400 $O/${R}_bench_line.json
+echo "== bench"; timeout 900 python bench.py --full 2>&1 | grep -v amdgpu.ids | grep '^{' | tail -1 > $O/${R}_bench_line.json; cut -c1-400 $O/${R}_bench_line.json
 echo "== bench --gpus 2 (two ranks on this one GPU, gloo rendezvous: functional, the timing is not a scaling number)"
-VOIDIN_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 10 --warmup 2 --no-extra 2>&1 | grep '^{' | tail -1 > $O/${R}_bench_line_2ranks_1gpu_gloo.json; cut -c1-300 $O/${R}_bench_line_2ranks_1gpu_gloo.json
+VOIDIN_DIST_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 10 --warmup 2 --no-extra 2>&1 | grep '^{' | tail -1 > $O/${R}_bench_line_2ranks_1gpu_gloo.json; cut -c1-300 $O/${R}_bench_line_2ranks_1gpu_gloo.json
 echo "== the driver's multi-GPU form: torch.distributed.run starts the ranks (here 2 on one GPU over gloo)"
-VOIDIN_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --no-extra --gather shard 2>&1 | grep '^{' | tail -1 > $O/${R}_bench_line_torchrun_2ranks_shard.json; cut -c1-300 $O/${R}_bench_line_torchrun_2ranks_shard.json
+VOIDIN_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-extra --gather shard 2>&1 | grep '^{' | tail -1 > $O/${R}_bench_line_torchrun_2ranks_shard.json; cut -c1-300 $O/${R}_bench_line_torchrun_2ranks_shard.json
 echo "== rocprof kernel stats (bench)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-verify > $O/kt_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-verify > $O/kt_stdout.log 2>&1
 find $O/kt -name "*kernel_trace.csv" -delete
 cp $(find $O/kt -name "bench_kernel_stats.csv" | head -1) $O/${R}_bench_kernel_stats.csv
 head -4 $O/${R}_bench_kernel_stats.csv | cut -c1-200
 echo "== rocprof kernel stats (headline legs only: --no-extra)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kh -o head -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-verify --no-extra > $O/kh_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kh -o head -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-verify --no-extra > $O/kh_stdout.log 2>&1
 find $O/kh -name "*kernel_trace.csv" -delete
 cp $(find $O/kh -name "head_kernel_stats.csv" | head -1) $O/${R}_bench_noextra_kernel_stats.csv
 head -3 $O/${R}_bench_noextra_kernel_stats.csv | cut -c1-200
@@ -32,8 +32,8 @@ find $O/kb -name "*kernel_trace.csv" -delete
 cp $(find $O/kb -name "bvh_kernel_stats.csv" | head -1) $O/${R}_bvh_kernel_stats.csv
 grep -v amdgpu.ids $O/kb_stdout.log | tail -22 > $O/${R}_bench_bvh.log
 echo "== rocprof pmc"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o cull -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-verify --no-extra > $O/pmc_fetch_stdout.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o cull -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-verify --no-extra > $O/pmc_write_stdout.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o cull -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-verify --no-extra > $O/pmc_fetch_stdout.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o cull -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-verify --no-extra > $O/pmc_write_stdout.log 2>&1
 R=$R python3 - <<'PY'
 import csv,glob,json,os,shutil
 R=os.environ['R']
