@@ -191,7 +191,9 @@ const char* vd_version(void);
 typedef enum VdOption {
     VD_OPT_CULL_SPLIT_MIN = 1,    /* vd_cull_*: inputs of at least this many instances run the split form
                                      (pass 1 -> scan -> pass 2); default 2 Mi                            */
-    VD_OPT_CULL_VARIANT = 2,      /* cull kernel variant (A/B; a small SIGNED id taken as is); default 0  */
+    VD_OPT_CULL_VARIANT = 2,      /* > 0: vd_cull_* always run the fused form, the compacting one with this
+                                     many rounds per tile (1, 2, 4, 8, 16; others 32) - a tile-size A/B;
+                                     default 0: form and tile size by input size                          */
     VD_OPT_TLAS_INDEX = 10,       /* 0: never use the indexed TLAS build; default 1                       */
     VD_OPT_TLAS_INDEX_MIN = 11,   /* smallest n the indexed build takes; default 6800                     */
     VD_OPT_TLAS_PHASE2 = 12,      /* clusters left at which the indexed build hands over to plain scans;
@@ -200,9 +202,6 @@ typedef enum VdOption {
     VD_OPT_TLAS_GROUPS = 14,      /* workgroups of the plain chain (1 = single workgroup); default by n   */
     VD_OPT_TLAS_SPIN_LIMIT = 15,  /* polls before the several-workgroup chain gives up and the build is
                                      redone on one workgroup (0 forces the redo: tests)                   */
-    VD_OPT_TLAS_SPEC = 16,        /* 0: indexed build without the speculative helper waves; default 1;
-                                     2: the speculative query runs on a second workgroup of the same XCC
-                                     (measured slower: 205 vs 188 ms at 32 768)    */
     VD_OPT_TLAS_PROFILE = 17,     /* 1: the indexed build prints its in-kernel cycle counters             */
     VD_OPT_TLAS_CHAIN_LDS = 18,   /* 0: the single-workgroup chain reads its slot arrays from memory even when
                                      they would fit LDS (<= 5600 instances); default 1 (A/B)               */

@@ -1,11 +1,10 @@
 """A/B the forms of vd_cull_compact in ONE process (interleaved rounds, median + min).
-Variants: 0 = library default (split form from 2^20 instances on), 4/8/16/32 = fused single-pass
-kernel with that many rounds per wave per tile, m70 (-70) = split form with per-round id stores in pass 1,
-m71 (-71) / m74 (-74) = pass 2 forced to its LDS-staged / direct-store form (default: direct up to 12 Mi instances),
-m81 (-81) = staged form without the same-XCD prefetch, m80 (-80) = vd_cull_emit as one kernel (no split).
-(The r01 logs under profiles/ use the numbering of the variants that were pruned afterwards:
-LDS-DMA, strided loads, compact staging, persistent, wave-tile, ablations, stream probes.)
-Usage (on a GPU box): python tools/ab_cull.py [--variants 0,32,16,m70] [--n 10000000] [--dist baseline|small]"""
+Variants: 0 = library default (split form from 2 Mi instances on), 1/2/4/8/16/32 = fused single-pass
+kernel with that many rounds per wave per tile (VD_OPT_CULL_VARIANT).
+(The logs under profiles/ also hold variants that were measured and removed since, under the ids
+they had then: negative ids up to round 6, and the r01 numbering of LDS-DMA, strided loads, compact
+staging, persistent, wave-tile, ablations, stream probes.)
+Usage (on a GPU box): python tools/ab_cull.py [--variants 0,32,16] [--n 10000000] [--dist baseline|small]"""
 import argparse
 import ctypes as C
 import os
@@ -19,7 +18,7 @@ from voidin_amd import abi, synth  # noqa: E402
 from voidin_amd.runtime import Context  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--variants", default="0,32,16,m70")
+ap.add_argument("--variants", default="0,32,16")
 ap.add_argument("--n", type=int, default=10_000_000)
 ap.add_argument("--dist", default="baseline")
 ap.add_argument("--rounds", type=int, default=5)
@@ -35,12 +34,12 @@ n = args.n
 d_m, d_i = ctx.upload(meshes), ctx.upload(inst)
 d_out = ctx.empty(n * 20)
 d_cnt = torch.zeros(4, dtype=torch.int32, device="cuda")
-variants = [int(v) for v in args.variants.replace('m', '-').split(",")]
+variants = [int(v) for v in args.variants.split(",")]
 ref_bytes = None
 times = {v: [] for v in variants}
 for rnd in range(args.rounds):
     for v in variants:
-        lib.vd_ctx_set_option(ctx.h, 2, v)      # VD_OPT_CULL_VARIANT: signed ids, taken as is
+        lib.vd_ctx_set_option(ctx.h, abi.OPTIONS["cull.variant"], v)
         for _ in range(2):
             ctx.cull_compact_dev(cam, d_m, len(meshes), d_i, n, d_out, d_cnt)
         torch.cuda.synchronize()

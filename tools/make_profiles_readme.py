@@ -161,7 +161,7 @@ NOTES = {
     "tlas_nn_table_sim.log": "`tools/tlas_nn_table_sim.py`: hit rates of a nearest-neighbour table in the literal TLAS chain, by refresh interval",
     "blas_item_isa.txt": "the ISA of `a_ranks_kernel` before / after (every load, wait and barrier in program order) and the same-box A/B series of round 4's BLAS work "
                          "(`tools/gpu_blas_ab_multi.sh`): loads of an item in flight together, the segment head through the scalar cache, kernarg preload, DPP reductions, mid tier, a_child",
-    "blas_boundary.log": "in-kernel cycle stamps of `a_boundary_kernel` (-DVD_BOUNDARY_PROF) before / after it was spread over all CUs; `a_eval` / mid-tier evaluation staging",
+    "blas_boundary.log": "in-kernel cycle stamps of `a_boundary_kernel` (a profiling fork of the kernel, since removed) before / after it was spread over all CUs; `a_eval` / mid-tier evaluation staging",
     "blas_two_stream_experiment.log": "measured and NOT kept: a level's rounds as two halves on two streams; two halves of the build with their own level loops",
     "tlas_two_workgroups.log": "VERDICT r3 item 7, measured and not made the default: the indexed TLAS build's speculative query on a second workgroup of the same XCC (205 vs 188 ms) with the counters that say why; mailbox variants",
     "tlas_chain_lds.log": "`tools/tlas_chain_lds_ab.py`: TLAS builds of <= 4096 instances with the chain's slot arrays in LDS against reading them from memory",

@@ -91,12 +91,8 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // 24 B, by triangle id.  (32 B with two pad words - two aligned 16-byte loads - until the kernels that move boxes turned out
-// HBM-bound: a_child at 5.2 TB/s with 14 % VALU; 24 B: 26.8 -> 26.05 ms per build, -DVD_BOX32 for the A/B.)
-#ifdef VD_BOX32
-struct TriBox { float mn[3]; float pad0; float mx[3]; float pad1; };
-#else
+// HBM-bound: a_child at 5.2 TB/s with 14 % VALU; 24 B: 26.8 -> 26.05 ms per build.)
 struct TriBox { float mn[3]; float mx[3]; };
-#endif
 struct TmpNode { float mn[3]; unsigned left_first; float mx[3]; unsigned count; };   // == VdBvhNode layout
 
 enum : unsigned { ERR_DEGENERATE = 1u, ERR_BAD_INDEX = 2u, ERR_INTERNAL = 4u };
@@ -237,9 +233,6 @@ __global__ __launch_bounds__(256) void blas_precompute_kernel(const MeshDesc* __
             k12[9 + k] = max(k12[9 + k], vd_key_hi(ce[k]));
         }
         }
-#ifdef VD_BOX32
-        bx.pad0 = bx.pad1 = 0.0f;
-#endif
         const f32x4 c4 = {ce[0], ce[1], ce[2], __uint_as_float(g)};   // .w: the triangle's id travels with its centroid
         cent[g] = c4;
         boxes[g] = bx;
@@ -388,15 +381,9 @@ struct WaveScratch {                              // per-wave: the node this wav
 };
 // box keys (min xyz, max xyz) of a local element come from the per-triangle boxes in global memory (L2-resident for
 // the few hundred triangles of a subtree): keeping them in LDS cost 12 KB of the image and one root per CU
-#ifndef VD_BOX_IN_LDS
-#define VD_BOX_IN_LDS 0
-#endif
 struct BoxKeys { int k[6]; };
 struct WaveLds {
     float cent[3][kSmallMax];
-#if VD_BOX_IN_LDS
-    int box[6][kSmallMax];                        // order-preserving keys: min xyz, max xyz
-#endif
     unsigned gid[kSmallMax];                      // local element -> triangle id
     unsigned short perm[2][kSmallMax];            // arrangement ping-pong (position -> local element)
     unsigned short falsepos[kSmallMax + 2];       // indexed by ABSOLUTE position s + j: segments are disjoint,
@@ -406,14 +393,9 @@ struct WaveLds {
 };
 __device__ __forceinline__ BoxKeys box_keys(const WaveLds& L, const TriBox* __restrict__ boxes, unsigned e) {
     BoxKeys r;
-#if VD_BOX_IN_LDS
-#pragma unroll
-    for (int q = 0; q < 6; ++q) r.k[q] = L.box[q][e];
-#else
     const TriBox bx = boxes[L.gid[e]];
     r.k[0] = vd_key(bx.mn[0]); r.k[1] = vd_key(bx.mn[1]); r.k[2] = vd_key(bx.mn[2]);
     r.k[3] = vd_key(bx.mx[0]); r.k[4] = vd_key(bx.mx[1]); r.k[5] = vd_key(bx.mx[2]);
-#endif
     return r;
 }
 
@@ -525,9 +507,6 @@ struct WaveQueues {                      // entry = node | start << 10 | count <
     unsigned n_small, root_left, bad;
 #ifdef VD_TUNING
     unsigned cls[48];   // wave-cycles by node size class and step (blas_small_kernel: cls_prof)
-#endif
-#ifdef VD_PROF_SEL
-    unsigned prof[8];   // 0 root node done, 1 wave loop done, 2 lists drained, 3 renumber scan done, 4 group batches, 5 listed nodes, 6 wide nodes
 #endif
 };
 
@@ -649,7 +628,11 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
                        const unsigned* __restrict__ ids32, ArrSet set0, ArrSet set1,
                        TmpNode* __restrict__ subnodes, unsigned short* __restrict__ submap,
                        unsigned* __restrict__ sub_interior, unsigned* __restrict__ final_ids, unsigned* __restrict__ err,
-                       unsigned* __restrict__ dbg_cycles, const unsigned* __restrict__ order, unsigned long long* __restrict__ cls_prof) {
+                       unsigned* __restrict__ dbg_cycles, const unsigned* __restrict__ order
+#ifdef VD_TUNING
+                       , unsigned long long* __restrict__ cls_prof
+#endif
+                       ) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
     // -DVD_TUNING only (vd_debug_blas_small_classes -> profiles/r06_blas_small_classes.log): wave-cycles by node size class
@@ -681,9 +664,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
 
     for (unsigned x = tid; x < N; x += 64u * kSubWaves) {
         const unsigned id = (root.pad & 2u) ? ids32[base + x] : base + x;
-#if VD_BOX_IN_LDS
-        const TriBox bx = boxes[id];
-#endif
         const f32x4 c4 = cent[id];
         const float ce[3] = {c4.x, c4.y, c4.z};
         L.gid[x] = id;
@@ -693,10 +673,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             L.cent[k][x] = ce[k];
-#if VD_BOX_IN_LDS
-            L.box[k][x] = vd_key(bx.mn[k]);
-            L.box[3 + k][x] = vd_key(bx.mx[k]);
-#endif
         }
     }
     // Wave-wide nodes ping-pong their own segment between the two perm buffers an even number of
@@ -717,9 +693,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
         Q.s_pending = 0; Q.h16 = 0; Q.t16 = 0; Q.h32 = 0; Q.t32 = 0;
 #ifdef VD_TUNING
         for (int q = 0; q < 48; ++q) Q.cls[q] = 0u;
-#endif
-#ifdef VD_PROF_SEL
-        for (int q = 0; q < 8; ++q) Q.prof[q] = 0;
 #endif
         if (N > (unsigned)kLaneMax) Q.pending = 1; else { Q.small[0] = root_ent; Q.n_small = 1; Q.s_pending = 1; }
     }
@@ -760,9 +733,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
         if (count == 0u) return false;
         VD_CLS_T(tg0);
         VD_MARK("setup_begin");
-#ifdef VD_PROF_SEL
-        if (lane == 0) { atomicAdd(&Q.prof[4], 1u); atomicAdd(&Q.prof[5], count); }
-#endif
         const unsigned gw = 8u << cls, gmask = gw == 32u ? 0xffffffffu : (1u << gw) - 1u;
         const unsigned* list = cls == 2u ? Q.c32 : (cls == 1u ? Q.c16 : Q.small);
         const unsigned gl = lane & (gw - 1u), gb = lane & ~(gw - 1u), grp = lane >> (3u + cls);
@@ -1044,11 +1014,7 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
                 unsigned w_band = 0, w_act = 0;                                       // the window of the wave's own shuffles (wave_shuffle)
                 for (int c = 0; c < kCand; ++c) {                                     // blas.rs:144-147
                     unsigned tt, ue, up;
-#ifdef VD_NO_B_WINDOWS
-                    w_band = 0; w_act = 0;
-#else
                     if (c % 7 == 0) { w_band = 0; w_act = 0; }
-#endif
                     if (is_root && root_by_block) block_shuffle_leader(L, Q, cur, n, c / 7, W.pos[c], tt, ue, up);
                     else wave_shuffle_any(L, cur, s, n, c / 7, W.pos[c], w_band, w_act, tt, ue, up);
                     w_band = w_act; w_act = tt - up;                                  // this trial's pivot: where the next one on the axis starts
@@ -1212,10 +1178,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
                     }
                 }
                 if (n_wide != 1) atomicAdd(&Q.pending, n_wide - 1);         // this node is done, n_wide more exist
-#ifdef VD_PROF_SEL
-                if (is_root) Q.prof[0] = (unsigned)(__builtin_amdgcn_s_memtime() - t_begin);
-                atomicAdd(&Q.prof[6], 1u);
-#endif
                 W.next_ent = keep;
             }
             vd_wave_lds_sync();
@@ -1230,9 +1192,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
     VD_CLS_T(t_loop_end);
     __syncthreads();
 
-#ifdef VD_PROF_SEL
-    if (tid == 0) Q.prof[1] = (unsigned)(__builtin_amdgcn_s_memtime() - t_begin);
-#endif
     // ---------------- drain the lists ----------------
     {
         unsigned idle2 = 0;
@@ -1247,9 +1206,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
                              // fence would write back the whole L2 of the XCD, once per subtree)
     __syncthreads();
     if (Q.bad) { if (tid == 0) atomicOr(err, Q.bad == 2u ? ERR_INTERNAL : ERR_DEGENERATE); return; }
-#ifdef VD_PROF_SEL
-    if (tid == 0) Q.prof[2] = (unsigned)(__builtin_amdgcn_s_memtime() - t_begin);
-#endif
     const unsigned pool = Q.pool;
     const unsigned n_interior = pool / 2u;
 
@@ -1274,9 +1230,6 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
         R[j] = (unsigned short)r;
     }
     __syncthreads();
-#ifdef VD_PROF_SEL
-    if (tid == 0) Q.prof[3] = (unsigned)(__builtin_amdgcn_s_memtime() - t_begin);
-#endif
     // new local index of node j = 2 * r(parent) + side; parent's rank = R[left sibling] - 1
     for (unsigned j = tid; j < n_nodes; j += 64u * kSubWaves) {
         const unsigned rl = R[j & ~1u];                    // rank of the left sibling = r(parent) + 1
@@ -1286,11 +1239,7 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
     for (unsigned x = tid; x < N; x += 64u * kSubWaves) final_ids[base + x] = __float_as_uint(cent[L.gid[L.perm[0][x]]].w);   // the triangle's own id
     if (tid == 0) {
         sub_interior[root_i] = n_interior;
-#ifdef VD_PROF_SEL
-        if (dbg_cycles) { dbg_cycles[2 * root_i] = (unsigned)(__builtin_amdgcn_s_memtime() - t_begin); dbg_cycles[2 * root_i + 1] = Q.prof[VD_PROF_SEL]; }
-#else
         if (dbg_cycles) { dbg_cycles[2 * root_i] = (unsigned)(__builtin_amdgcn_s_memtime() - t_begin); dbg_cycles[2 * root_i + 1] = N; }
-#endif
     }
 #ifdef VD_TUNING
     { VD_CLS_T(t_end); VD_CLS_ADD(40, t_end - t_begin); VD_CLS_ADD(42, t_loaded - t_begin); VD_CLS_ADD(43, t_end - t_loop_end); VD_CLS_ADD(44, 1); }
@@ -1343,13 +1292,9 @@ struct ItemCtx { unsigned seg, rel0, n_here; };
 struct SegHead { unsigned start, count, node, item_first, n_items, best, Lst, ttot_cur, act[3], pad_act; };
 // The kernels read the head THROUGH the record (scalar loads, served by the scalar cache the segment's items share); a
 // copy of the 48 bytes into registers cost 8 ms per build as a struct assignment (three 16-byte VECTOR loads per lane, also
-// with a readfirstlane'd index) and 16 ms field by field (one s_load_dwordx8 + x2 + x1 batch): -DVD_HEAD_COPY,
+// with a readfirstlane'd index) and 16 ms field by field (one s_load_dwordx8 + x2 + x1 batch),
 // profiles/r04_blas_item_isa.txt.
-#ifdef VD_HEAD_COPY
-#define VD_HEAD_VIEW(sg, segs, ic) (void)0
-#else
 #define VD_HEAD_VIEW(sg, segs, ic) sg = reinterpret_cast<const SegHead*>((segs) + (ic).seg)
-#endif
 static_assert(offsetof(Seg, act) == offsetof(SegHead, act) && offsetof(Seg, ttot_cur) == offsetof(SegHead, ttot_cur), "SegHead mirrors the first words of Seg");
 __device__ __forceinline__ bool item_ctx(const Seg* segs, const unsigned* item_seg, const LevelCtl* ctl, ItemCtx& ic, SegHead& h) {
     const unsigned n_items = ctl->n_items, seg = item_seg[blockIdx.x];      // item_seg holds an entry for every workgroup of the grid
@@ -1464,11 +1409,7 @@ __device__ __forceinline__ void item_load(const SegHead* sg, const ItemCtx& ic, 
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
         const unsigned x = wave * (unsigned)(kItem / 4) + j * 64u + lane;
-#ifdef VD_OLD_LOAD
-        if (x < ic.n_here) vals[j] = base[x];
-#else
         vals[j] = base[x < ic.n_here ? x : 0u];
-#endif
     }
 }
 // predicates of the item's positions that lie in the shuffled window (positions below `act` stay out of the ballots)
@@ -1586,11 +1527,7 @@ __device__ __forceinline__ void prefix_load(const SegHead* sg, const unsigned* _
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const unsigned i = threadIdx.x + (unsigned)k * 256u;
-#ifdef VD_OLD_PREFIX
-        v[k] = 0u; if (i < ni) v[k] = cn[i];
-#else
         v[k] = cn[i < ni ? i : 0u];                          // unconditional: in flight together
-#endif
     }
 }
 template <bool SF>
@@ -1653,11 +1590,7 @@ __global__ __launch_bounds__(256) void a_ranks_kernel(const Seg* segs, const uns
             // originals at [0, pivot] in place and the back pointer those right of it, pivot = ttot - p(u) - a true left of
             // ttot - 1 and a false right of ttot + 1 is nobody's t_F / f_{T+1}, and two thirds of the table stores never happen
             // (tests/test_closed_form_shuffle.py holds this form against the literal loop, stale entries included)
-#ifdef VD_DENSE_TABLES
-            const bool wr = true;
-#else
             const bool wr = p ? x + 1u >= ttot : x <= ttot + 1u;
-#endif
             if (wr) {
                 if (p) truepos[s + (ttot - tl - 1u)] = x;     // index T: (T+1)-th true from the right
                 else falsepos[s + (x - tl)] = x;              // index F: (F+1)-th false from the left
@@ -1783,17 +1716,12 @@ __global__ __launch_bounds__(256) void a_apply_kernel(Seg* segs, const unsigned*
             const bool p = pp[j];
             const long long tF = FF[j] == 0u ? (long long)n : (need_t[j] ? (long long)tp[j] : -1ll);
             const unsigned fj = need_f[j] ? fp[j] : n;
-#ifdef VD_DENSE_TABLES
-            const bool left = (long long)x < tF;
-            const bool amb = true;
-#else
             // a_ranks writes only the entries the shuffle's swaps look up, so an entry is trusted only where it must be this
             // round's: the front pointer examines the originals at [0, pivot] in place and the back pointer the rest, pivot =
             // ttot or ttot - 1 - everything left of ttot is consumed from the left, everything right of it from the right, and
             // AT ttot the t_F entry decides (its writer sits right of ttot - 1); `u` is within one position of ttot
             const bool left = x < ttot || (x == ttot && (long long)x < tF);
             const bool amb = x + 1u - ttot <= 2u;
-#endif
             const unsigned fetch = left ? x + n - (unsigned)tF : (n - 1u - x) + fj + 1u;
             const bool is_u = amb && fetch == n - 1u;
             unsigned dest;
@@ -1887,11 +1815,7 @@ __global__ __launch_bounds__(256) void a_bin_kernel(Seg* segs, const unsigned* i
 #pragma unroll
         for (int j = 0; j < kPer; ++j) {
             const unsigned xr = threadIdx.x + 256u * (unsigned)j;
-#ifdef VD_BIN_GATHER
-            const unsigned ps = P::pos(pay[a0 + (xr < n_here ? xr : 0u)]);
-#else
             const unsigned ps = a0 + (xr < n_here ? xr : 0u);       // (n_here == 0: position 0 of the arrays, never used)
-#endif
             d.u[j] = is_u_flag[ps]; d.bx[j] = boxes[ps]; d.b21[j] = bits21[ps];
         }
     };
@@ -1985,9 +1909,8 @@ __global__ __launch_bounds__(256) void a_child_kernel(Seg* segs, const unsigned*
         const unsigned xr = threadIdx.x + 256u * (unsigned)j;
         if (xr < ic.n_here) { boxes_next[a0 + xr] = bxs[j]; cent_next[a0 + xr] = cs[j]; }
     }
-#ifndef VD_CHILD24
     // all but ONE item of a segment lie wholly on one side of the pivot: 12 running keys and 12 reductions instead of 24
-    // (27.6 ms per build against 27.85 with the 24-key form for every item, -DVD_CHILD24; before the loads of this kernel
+    // (27.6 ms per build against 27.85 with the 24-key form for every item; before the loads of this kernel
     // were issued together the same idea was SLOWER, 3.64 ms of a_child per build against 3.02)
     const bool all_left = ic.rel0 + ic.n_here <= Lst, all_right = ic.rel0 >= Lst;
     if (all_left || all_right) {
@@ -2017,7 +1940,6 @@ __global__ __launch_bounds__(256) void a_child_kernel(Seg* segs, const unsigned*
             if ((threadIdx.x & 63u) == 0u) { if (is_min) atomicMin(&s_k[slot], r); else atomicMax(&s_k[slot], r); }
         }
     } else
-#endif
     {
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
@@ -2145,15 +2067,8 @@ __global__ __launch_bounds__(1024) void a_boundary_kernel(const Seg* ended, Seg*
     constexpr unsigned kFirstLds = 8192u;
     __shared__ unsigned s_part[1024], s_first[kFirstLds], s_need[6], s_base[4], s_last;
     const unsigned tid = threadIdx.x;
-#ifdef VD_BOUNDARY_PROF
-    long long tp0 = clock64(), tp1 = tp0, tp2, tp3, tp4;
-    unsigned prof_ended = 0;
-#endif
     if (finalize) {
         const unsigned n_ended = ctl->n_seg;
-#ifdef VD_BOUNDARY_PROF
-        prof_ended = n_ended;
-#endif
         finalize_segments(ended, n_ended, segs, ctl, s_need, s_base, top, small, is_u_flag, top_cap, small_cap, mid, mid_cap, parity);
         // the last workgroup to arrive goes on (its own and everybody else's records and counters are complete: release
         // before the ticket, acquire after it)
@@ -2176,9 +2091,6 @@ __global__ __launch_bounds__(1024) void a_boundary_kernel(const Seg* ended, Seg*
         }
         __syncthreads();
     }
-#ifdef VD_BOUNDARY_PROF
-    tp1 = clock64();
-#endif
     const unsigned n = ctl->n_seg;
     const unsigned per = (n + 1023u) / 1024u;
     const unsigned lo = min(n, tid * per), hi = min(n, lo + per);
@@ -2186,9 +2098,6 @@ __global__ __launch_bounds__(1024) void a_boundary_kernel(const Seg* ended, Seg*
     for (unsigned i = lo; i < hi; ++i) sum += (segs[i].count + kItem - 1) / kItem;      // loads only; n_items is stored with item_first below
     s_part[tid] = sum;
     __syncthreads();
-#ifdef VD_BOUNDARY_PROF
-    tp2 = clock64();
-#endif
     for (unsigned off = 1; off < 1024u; off <<= 1) {
         const unsigned v = tid >= off ? s_part[tid - off] : 0u;
         __syncthreads();
@@ -2205,9 +2114,6 @@ __global__ __launch_bounds__(1024) void a_boundary_kernel(const Seg* ended, Seg*
     const unsigned n_items = s_part[1023];
     if (tid == 1023u) ctl->n_items = n_items;
     __syncthreads();
-#ifdef VD_BOUNDARY_PROF
-    tp3 = clock64();
-#endif
     // item -> segment: every thread takes items tid, tid + 1024, ... and finds the last segment that starts at or before it
     // (one segment of thousands of items at the first levels, thousands of small ones later: either way a few steps)
     // (the search runs on a copy of the first items in LDS: through the records in memory it was 12 dependent misses per item)
@@ -2224,12 +2130,6 @@ __global__ __launch_bounds__(1024) void a_boundary_kernel(const Seg* ended, Seg*
             item_seg[j] = a;
         }
     }
-#ifdef VD_BOUNDARY_PROF
-    __syncthreads();
-    tp4 = clock64();
-    if (tid == 0) printf("a_boundary: ended %u, next %u segments, %u items; cycles: finalize %lld, set-up %lld, scan %lld, items %lld\n", prof_ended, n, n_items,
-                         tp1 - tp0, tp2 - tp1, tp3 - tp2, tp4 - tp3);
-#endif
 }
 
 // =============================================================================================
@@ -2642,7 +2542,11 @@ int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_pac
                    unsigned *falsepos, *truepos, *final_ids, *stack, *idx_copy;
                    unsigned char* is_u; Seg *seg0, *seg1; MidRoot* mid; unsigned *item_seg, *item_cnt, *item_cnt1, *item_pre; TopNode* top; SmallRoot* small;
                    unsigned* sub_interior; TmpNode* subnodes; unsigned short* submap; LevelCtl* ctl; int* root_keys; TopOut* tout; unsigned* root_pair;
-                   MeshDesc* meshes; unsigned* bad_mesh; unsigned long long* cls_prof; } p;
+                   MeshDesc* meshes; unsigned* bad_mesh;
+#ifdef VD_TUNING
+                   unsigned long long* cls_prof;
+#endif
+                 } p;
         // payload ping-pong: 4 bytes per triangle up to 2^25 triangles, 8 beyond (allocated for the width in use)
         const size_t pay_words = wide_pay ? T : (T + 1) / 2;
         p.pay0 = a.take<u32x2>(pay_words); p.pay1 = a.take<u32x2>(pay_words);
@@ -2657,7 +2561,9 @@ int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_pac
         p.subnodes = a.take<TmpNode>(2 * T + 2); p.submap = a.take<unsigned short>(2 * T + 2); p.ctl = a.take<LevelCtl>(1); p.root_keys = a.take<int>(16 * (size_t)K);
         p.tout = a.take<TopOut>(top_cap); p.root_pair = a.take<unsigned>(small_cap);
         p.meshes = a.take<MeshDesc>(K); p.bad_mesh = a.take<unsigned>(1);
-        p.cls_prof = a.take<unsigned long long>(64 * 64);  // written by the -DVD_TUNING build only: 64 replicas of 64 counters
+#ifdef VD_TUNING
+        p.cls_prof = a.take<unsigned long long>(64 * 64);  // 64 replicas of 64 counters
+#endif
         return p;
     };
     (void)layout(probe, false);
@@ -2861,8 +2767,15 @@ int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_pac
     if (n_small) {
         hipLaunchKernelGGL(b_order_kernel, dim3(1), dim3(1024), 0, st, P.small, &P.ctl->n_small, P.root_pair);   // root_pair is free until phase C
         hipLaunchKernelGGL(blas_small_kernel, dim3(n_small), dim3(64 * kSubWaves), sizeof(WaveLds) + sizeof(WaveQueues), st, P.small, &P.ctl->n_small, P.ids32,
-                           sets[0], sets[1], P.subnodes, P.submap, P.sub_interior, P.final_ids, &P.ctl->err, P.stack, P.root_pair, P.cls_prof);
-        ctx->dbg_ptr = P.stack; ctx->dbg_count = 2 * n_small; ctx->dbg_ptr2 = P.cls_prof;
+                           sets[0], sets[1], P.subnodes, P.submap, P.sub_interior, P.final_ids, &P.ctl->err, P.stack, P.root_pair
+#ifdef VD_TUNING
+                           , P.cls_prof
+#endif
+                           );
+        ctx->dbg_ptr = P.stack; ctx->dbg_count = 2 * n_small;
+#ifdef VD_TUNING
+        ctx->dbg_ptr2 = P.cls_prof;
+#endif
     }
     // ---- phase C: DFS numbering of the top tree on the host ----
     // The top tree is final before phase B starts (the stream was synchronised after the last level / the mid tier), so

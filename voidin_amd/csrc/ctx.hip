@@ -281,7 +281,6 @@ int vd_ctx_set_option(VdCtx* ctx, int option, int64_t value) {
     if (option <= 0 || option >= VD_OPT_COUNT_) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_ctx_set_option: unknown option");
     ctx->opt[option] = value < 0 ? -1 : (long long)value;
     if (option == VD_OPT_CULL_SPLIT_MIN) ctx->split_min = value < 0 ? (2u << 20) : (unsigned)value;
-    if (option == VD_OPT_CULL_VARIANT) ctx->cull_variant = (int)value;     // variants are small signed ids, 0 = default
     return VD_OK;
 }
 

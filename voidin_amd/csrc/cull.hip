@@ -280,8 +280,8 @@ constexpr int compact_lds_bytes() { return kWavesPerBlock * kSlabBytes + ROUNDS 
 // ------------------------------------------------------------------------------------------
 // Multi-GPU wire format: cull -> one bit per instance; expand bits -> ordered draw list.
 // ------------------------------------------------------------------------------------------
-// IdT != void: also write the (clamped) mesh id of every instance as IdT (u8 / u16 / u32 by table
-// size) for the expansion pass of the split single-GPU path.
+// ids_out != nullptr: also write the (clamped) mesh id of every instance as IdT (vd_cull_mask_dev
+// passes none; the split single-GPU path uses cull_mask_tiled_kernel below).
 template <typename IdT>
 __global__ __launch_bounds__(kBlock, 3) void cull_mask_kernel(CullCamera cam, const VdMeshInfo* __restrict__ meshes,
                                                                unsigned n_mesh, const VdInstance* __restrict__ inst,
@@ -692,7 +692,7 @@ __global__ __launch_bounds__(kBlock) void expand_mask_kernel(const vd_u64* __res
 //     otherwise it is staged in LDS at the destination's 16-B phase and leaves in 16-B-per-lane runs.
 // The dword that holds the last valid id may extend past n_total: an aligned dword that contains one valid byte
 // never crosses a page, and the extra bytes belong to instances whose mask bit is 0.
-template <bool DIRECT, int PF>
+template <bool DIRECT>
 __global__ __launch_bounds__(kBlock) void expand_mask_u8_kernel(const vd_u64* __restrict__ mask, unsigned n_words, unsigned wps,
                                                                 unsigned shard_size, unsigned n_total, unsigned first_instance,
                                                                 const unsigned char* __restrict__ mesh_ids,
@@ -732,9 +732,10 @@ __global__ __launch_bounds__(kBlock) void expand_mask_u8_kernel(const vd_u64* __
     }
     unsigned s_shard = w0 / wps, s_r = w0 - s_shard * wps;   // scalar walk over the wave's words
     unsigned word_first = s_shard * shard_size + 64u * s_r;
-    // PF > 0: touch the mask words and ids of chunk c + 8 PF.  Workgroups are dealt to the 8 XCDs round-robin, so that
-    // chunk will be expanded on this XCD and finds its inputs in this L2: behind a write-saturated L2 a load MISS
+    // staged form: touch the mask words and ids of chunk c + 8 PF.  Workgroups are dealt to the 8 XCDs round-robin, so
+    // that chunk will be expanded on this XCD and finds its inputs in this L2: behind a write-saturated L2 a load MISS
     // waits for an eviction (tens of microseconds), and these misses are nobody's critical path.
+    constexpr unsigned PF = DIRECT ? 0u : 32u;
     unsigned pf = 0;
     if (PF > 0) {
         const unsigned pw = (chunk + 8u * PF) * kChunkWords + (threadIdx.x >> 1);
@@ -1016,15 +1017,13 @@ static int launch_expand(VdCtx* ctx, const vd_u64* d_mask, unsigned n_words, uns
                       (reinterpret_cast<uintptr_t>(d_ids) & 3u) == 0u;
     if (fast) {
         // up to ~250 MB of commands (the Infinity Cache absorbs them) the direct form is at the write ceiling; past
-        // that the L2 merges fewer of its 4-byte pieces in time and the LDS-staged 16-byte runs win (A/B: -71 / -74)
-        const bool direct = ctx->cull_variant == -74 || (ctx->cull_variant > -71 && n_total <= (12u << 20));
-#define VD_EXPAND_U8(D, P)                                                                                                \
-        hipLaunchKernelGGL((expand_mask_u8_kernel<D, P>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps,  \
+        // that the L2 merges fewer of its 4-byte pieces in time and the LDS-staged 16-byte runs win
+#define VD_EXPAND_U8(D)                                                                                                   \
+        hipLaunchKernelGGL((expand_mask_u8_kernel<D>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps,  \
                            shard_size, n_total, first_instance, reinterpret_cast<const unsigned char*>(d_ids), d_meshes,    \
                            n_mesh, d_out, offsets)
-        if (direct) VD_EXPAND_U8(true, 0);
-        else if (ctx->cull_variant == -81) VD_EXPAND_U8(false, 0);          // A/B: without the same-XCD prefetch
-        else VD_EXPAND_U8(false, 32);
+        if (n_total <= (12u << 20)) VD_EXPAND_U8(true);
+        else VD_EXPAND_U8(false);
 #undef VD_EXPAND_U8
         return VD_OK;
     }
@@ -1201,26 +1200,14 @@ static int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdM
     vd_u64* d_mask = reinterpret_cast<vd_u64*>(ctx->scratch);
     void* d_ids = reinterpret_cast<char*>(ctx->scratch) + (((size_t)n_words * 8 + 255) & ~(size_t)255);
     vd_time_begin(ctx);
-    const unsigned n_wave_tiles = n_words;
-    unsigned blocks = (n_wave_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned cap = (unsigned)ctx->num_cus * 4u;
-    if (blocks > cap) blocks = cap;
+    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
+    unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
 #define VD_SPLIT(IdT)                                                                                              \
-    do {                                                                                                         \
-        if (ctx->cull_variant == -70) {                                                                          \
-            hipLaunchKernelGGL(cull_mask_kernel<IdT>, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes,   \
-                               ctx->stream, make_cam(camera), d_meshes, n_mesh, d_instances, n_inst, d_mask,     \
-                               reinterpret_cast<IdT*>(d_ids), n_wave_tiles);                                     \
-        } else {                                                                                                 \
-            const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);                    \
-            unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;                                          \
-            if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;                              \
-            hipLaunchKernelGGL(cull_mask_tiled_kernel<IdT>, dim3(mb), dim3(kBlock),                              \
-                               kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),           \
-                               ctx->stream, make_cam(camera), d_meshes, n_mesh, d_instances, n_inst, d_mask,     \
-                               reinterpret_cast<IdT*>(d_ids), n_mt);                                             \
-        }                                                                                                        \
-    } while (0)
+    hipLaunchKernelGGL(cull_mask_tiled_kernel<IdT>, dim3(mb), dim3(kBlock),                                        \
+                       kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
+                       ctx->stream, make_cam(camera), d_meshes, n_mesh, d_instances, n_inst, d_mask,               \
+                       reinterpret_cast<IdT*>(d_ids), n_mt)
     if (id_bytes == 1u) VD_SPLIT(unsigned char);
     else if (id_bytes == 2u) VD_SPLIT(unsigned short);
     else VD_SPLIT(unsigned);
@@ -1238,7 +1225,7 @@ int vd_cull_emit_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMe
     if (!camera || !d_meshes || n_mesh == 0) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null camera/meshes or n_mesh == 0");
     if (n_inst == 0) return VD_OK;
     if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null instances/out");
-    if (ctx->cull_variant <= 0 && ctx->cull_variant != -80 && n_inst >= ctx->split_min) {
+    if (ctx->option(VD_OPT_CULL_VARIANT, 0) <= 0 && n_inst >= ctx->split_min) {
         // split form, as for the compacted list: the 20-byte stores leave the read stream
         vd_u64* d_mask; void* d_ids; unsigned id_bytes;
         int rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes);
@@ -1289,11 +1276,11 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
         return VD_OK;
     }
     if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact: null instances/out");
-    int variant = ctx->cull_variant;
+    const int variant = (int)ctx->option(VD_OPT_CULL_VARIANT, 0);
     vd_u64* ticket; vd_u64* states;
     int rc = vd_scan_check_fault(ctx);       // an EARLIER launch's scan gave up: said once, here
     if (rc) return rc;
-    if ((variant <= 0) && n_inst >= ctx->split_min) {
+    if (variant <= 0 && n_inst >= ctx->split_min) {
         // Split form (default for large inputs): pass 1 streams the instances and writes only one bit
         // + a compact mesh id per instance (reads run at ~6.4 TB/s when no 20-byte commands are stored
         // in the same kernel); pass 2 expands the bits into the ordered command list.  Mixing the

@@ -22,7 +22,6 @@ struct VdCtx {
     bool timing_enabled = false;        // event pairs around kernels cost a few us of GPU idle each: opt-in
     char err[512] = {0};
     int num_cus = 256;
-    int cull_variant = 0;               // kernel variant for A/B tuning (VD_OPT_CULL_VARIANT)
     unsigned split_min = 2u << 20;      // inputs of at least this many instances run the split form of the cull
                                         // (VD_OPT_CULL_SPLIT_MIN): below, the fused single launch is faster (tools/ab_split_min.py:
                                         // 1 Mi 39 vs 47 us, 2 Mi 65 vs 65, 3 Mi 97 vs 93, 10 M 312 vs 256)
@@ -55,7 +54,7 @@ struct VdCtx {
     VdBvhBuildStats bvh_stats = {};                            // vd_bvh_last_build_stats
     bool tlas_chain_lds_opt_in[2] = {false, false};              // tlas_build_kernel<VdTlasNode / VdTlasNodeWide>: dynamic LDS for the slot arrays
     bool mid_lds_opt_in = false;                               // blas_mid_kernel's dynamic-LDS attribute set on this device
-    bool tlas_ix_lds_opt_in[8] = {false, false, false, false, false, false, false, false};  // tlas_build_indexed_kernel<VdTlasNode / VdTlasNodeWide> x {plain, with helper waves}, likewise
+    bool tlas_ix_lds_opt_in[2] = {false, false};               // tlas_build_indexed_kernel<VdTlasNode / VdTlasNodeWide>, likewise
 };
 
 // Every extern "C" entry point runs on the context's device: allocations, event records and launches otherwise go to

@@ -54,8 +54,7 @@ class Context:
 
     def set_option(self, name: str, value: int | None):
         """vd_ctx_set_option (include/voidin_abi.h VdOption) by name, e.g. "tlas.spin_limit"; None = default."""
-        dflt = 0 if name == "cull.variant" else -1            # the variant is a signed id taken as is (0 = default)
-        self._chk(self.lib.vd_ctx_set_option(self.h, abi.OPTIONS[name], dflt if value is None else int(value)))
+        self._chk(self.lib.vd_ctx_set_option(self.h, abi.OPTIONS[name], -1 if value is None else int(value)))
 
     def apply_env_options(self):
         """A/B scripts under tools/ select variants with VD_* environment variables; the LIBRARY reads none of them -
