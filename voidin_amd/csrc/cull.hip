@@ -12,12 +12,17 @@
 //     and mesh id; the next round's loads are already in flight (register prefetch);
 //   * emit path (reference format): the 20-byte commands of a wave (1280 contiguous bytes) go
 //     through the same slab and leave as 16-B-per-lane stores;
-//   * compact path, large inputs (split form): pass 1 `cull_mask_tiled_kernel` writes only one
-//     ballot bit + a compact mesh id per instance, so the read stream runs at ~6.3 TB/s; pass 2 =
-//     `mask_scan_kernel` (survivors per 8192-instance chunk, scanned by the last workgroup to
-//     arrive) + `expand_mask_u8_kernel` / `expand_mask_kernel` (workgroup c expands chunk c to
-//     out[offset[c]...): no ticket, no look-back, every load issued before the first store).
+//   * compact path, large inputs (split form), two launches: pass 1 `cull_mask_tiled_kernel`
+//     writes only one ballot bit + a compact mesh id per instance and the survivors of every
+//     1024-instance tile, so the read stream runs at ~6.5 TB/s; pass 2 `expand_mask_u8_kernel` /
+//     `expand_mask_kernel`: workgroup c sums the tile counts before its 8192-instance chunk and
+//     expands the chunk to out[offset[c]...): no ticket, no look-back, no wait on another
+//     workgroup, every load issued before the first store.
 //     (Storing the 20-byte commands from inside the read stream costs ~3x per byte: DESIGN.md §3.1);
+//   * masks that pass 1 of the same call did not write carry no tile counts: for them
+//     `mask_scan_kernel` (survivors per chunk, scanned by the last workgroup to arrive) runs in
+//     front of the expansion - vd_expand_mask_dev and the dist.hip steps (all-gathered masks, the
+//     occlusion path's second mask among them) - and of vd_mask_to_indices_dev;
 //   * compact path, small inputs (fused form): `cull_compact_kernel<ROUNDS>`, one launch, a
 //     decoupled look-back over 8-byte {epoch,status,value} granules ranks the tiles while
 //     per-round (mesh id | visible) words wait in LDS;
@@ -408,12 +413,15 @@ __global__ __launch_bounds__(kBlock, 3) void occlusion_mask_kernel(OccCamera cam
 // Tiled form of pass 1: a wave owns kMaskRounds CONSECUTIVE rounds (1024 instances), keeps their
 // mesh ids and ballot words on chip and flushes them once per tile as wide stores, so the read
 // stream is interrupted by one 1-KB store per 147 KB read instead of a 64-B store per 9 KB.
+// With the flush goes the number of the tile's survivors, tile_count[t]: a plain store, ordered before pass 2 by the
+// kernel boundary.  The expansion of the single-GPU step sums these to place its chunk (expand_mask_u8_kernel<.., true>).
 constexpr int kMaskRounds = 16;
 template <typename IdT>
 __global__ __launch_bounds__(kBlock, 3) void cull_mask_tiled_kernel(CullCamera cam, const VdMeshInfo* __restrict__ meshes,
                                                                      unsigned n_mesh, const VdInstance* __restrict__ inst,
                                                                      unsigned n_inst, vd_u64* __restrict__ mask,
-                                                                     IdT* __restrict__ ids_out, unsigned n_tiles) {
+                                                                     IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
+                                                                     unsigned n_tiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     constexpr int kIdBytes = kMaskRounds * kWave * (int)sizeof(IdT);
@@ -460,6 +468,10 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_tiled_kernel(CullCamera c
         const size_t w0 = (size_t)t * kMaskRounds;
         const size_t n_words = ((size_t)n_inst + 63) / 64;
         if (lane < (unsigned)kMaskRounds && w0 + lane < n_words) mask[w0 + lane] = my_word;
+        unsigned survivors = (unsigned)__popcll(my_word);                // 0 in lanes >= kMaskRounds
+#pragma unroll
+        for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
+        if (lane == 0u) tile_count[t] = survivors;
         const size_t id_base = tile_first * sizeof(IdT);                 // bytes; tile_first % 1024 == 0 -> 16-B aligned
         const size_t id_end = min((size_t)n_inst, tile_first + (size_t)kWave * kMaskRounds) * sizeof(IdT);
         char* gids = reinterpret_cast<char*>(ids_out);
@@ -488,8 +500,9 @@ constexpr int kExpandGroup = 4;                      // mask words staged and st
 constexpr int kExpandWords = 32;                     // mask words (64 instances each) per wave
 constexpr int kChunkWords = kWavesPerBlock * kExpandWords;   // per workgroup: 128 words = 8192 instances
 
-// Pass 2a of the split form: survivors per 8192-instance chunk, then (last workgroup to finish) their exclusive
-// scan in place and the total.  Keeping the scan out of pass 2b leaves that kernel without tickets, look-back or
+// Pass 2a for masks without pass 1's tile counts (vd_expand_mask_dev, vd_mask_to_indices_dev, the dist.hip steps; the
+// single-GPU vd_cull_compact* does not launch it): survivors per 8192-instance chunk, then (last workgroup to finish) their
+// exclusive scan in place and the total.  Keeping the scan out of pass 2b leaves that kernel without tickets, look-back or
 // any other load that depends on another workgroup: under a saturated store stream every dependent load costs
 // microseconds (on gfx950 loads and stores share vmcnt and the same queue), and 2b had four of them in a chain.
 //
@@ -570,19 +583,54 @@ __global__ __launch_bounds__(kScanBlock) void mask_scan_kernel(const vd_u64* __r
     }
 }
 
+constexpr int kChunkTiles = kChunkWords / kMaskRounds;      // a chunk of pass 2 is 8 tiles of pass 1
+
+// Second source of a chunk's offset (single-GPU step: the mask is pass 1's own, one shard): this thread's share of
+// tile_count[0, n_before), the survivors of all tiles before the chunk.  At most ~10 independent 16-byte loads per thread
+// at 10 M instances (4 per batch in flight), issued ahead of the kernel's mask / id loads and its first store - a load
+// miss behind a write-saturated L2 costs microseconds.  The block-wide sum goes through LDS at the barrier the
+// kernel has anyway.  The table is 16-byte aligned and padded to a multiple of 4 entries; entries at or past n_before
+// may hold anything and are left out.
+__device__ __forceinline__ unsigned tile_prefix_partial(const unsigned* __restrict__ tile_count, unsigned n_before) {
+    constexpr unsigned kBatch = 4;
+    unsigned sum = 0;
+    for (unsigned i0 = threadIdx.x * 4u; i0 < n_before; i0 += kBatch * kBlock * 4u) {
+        u32x4 v[kBatch];
+#pragma unroll
+        for (unsigned k = 0; k < kBatch; ++k) {
+            const unsigned i = i0 + k * kBlock * 4u;
+            v[k] = *reinterpret_cast<const u32x4*>(tile_count + (i < n_before ? i : i0));   // unconditional: no branch between the loads
+        }
+#pragma unroll
+        for (unsigned k = 0; k < kBatch; ++k) {
+            const unsigned i = i0 + k * kBlock * 4u;
+            sum += (i < n_before ? v[k].x : 0u) + (i + 1u < n_before ? v[k].y : 0u) + (i + 2u < n_before ? v[k].z : 0u) +
+                   (i + 3u < n_before ? v[k].w : 0u);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    return sum;                                           // the wave's share
+}
+
 // Pass 2b: workgroup c expands the 128 mask words of chunk c to out[chunk_offset[c] ...); word w belongs to shard
 // w / wps and holds the instances shard*shard_size + 64*(w % wps) + bit.  Every load is issued before the first
 // store (one round trip per workgroup).
+//   TILES = false: chunk_offset[c] = chunk_entry[c], written by mask_scan_kernel (any mask: vd_expand_mask_dev, dist.hip).
+//   TILES = true:  chunk_offset[c] = sum of pass 1's tile_count[] over the tiles before the chunk; no scan launch, no
+//                  cross-workgroup wait and hence no "gave up" state.  The last workgroup also writes *out_count.
 // General form (any id width, any shard size); expand_mask_u8_kernel below is the tuned common case.
 //   TAB:  the mesh table fits the LDS copy (no global loads in the store loop).
-template <typename IdT, bool TAB>
+template <typename IdT, bool TAB, bool TILES>
 __global__ __launch_bounds__(kBlock) void expand_mask_kernel(const vd_u64* __restrict__ mask, unsigned n_words, unsigned wps,
                                                              unsigned shard_size, unsigned n_total, unsigned first_instance,
                                                              const IdT* __restrict__ mesh_ids,
                                                              const VdMeshInfo* __restrict__ meshes, unsigned n_mesh,
                                                              VdDrawIndexedIndirect* __restrict__ out,
-                                                             const vd_u64* __restrict__ chunk_entry) {
+                                                             const vd_u64* __restrict__ chunk_entry,
+                                                             const unsigned* __restrict__ tile_count, unsigned* __restrict__ out_count) {
     constexpr int kGroups = kExpandWords / kExpandGroup;
+    __shared__ unsigned s_prefix[kWavesPerBlock];
     constexpr unsigned kTab = TAB ? 512 : 1;              // mesh tables up to 512 entries are served from LDS
     __shared__ unsigned s_tab[kTab][3];                   // {index_count, base_index, vertex_offset}
     constexpr int kStageBytes = kExpandGroup * 1280 + 32;
@@ -591,8 +639,14 @@ __global__ __launch_bounds__(kBlock) void expand_mask_kernel(const vd_u64* __res
     const unsigned chunk = blockIdx.x;
     const unsigned cw0 = chunk * kChunkWords;
     const unsigned w0 = __builtin_amdgcn_readfirstlane(cw0 + wave * kExpandWords);   // wave-uniform: scalar index math
-    unsigned base = (unsigned)chunk_entry[chunk];
-    if (base == 0xffffffffu) return;                       // the scan gave up (mask_scan_kernel): no list
+    unsigned base = 0;
+    if (TILES) {
+        const unsigned part = tile_prefix_partial(tile_count, chunk * kChunkTiles);
+        if (lane == 0) s_prefix[wave] = part;
+    } else {
+        base = (unsigned)chunk_entry[chunk];
+        if (base == 0xffffffffu) return;                   // the scan gave up (mask_scan_kernel): no list
+    }
     // survivors of the chunk's earlier waves: lane l looks at words cw0 + l and cw0 + 64 + l
     unsigned before = 0;
     if (lane < wave * kExpandWords && cw0 + lane < n_words) before = (unsigned)__popcll(mask[cw0 + lane]);
@@ -629,6 +683,16 @@ __global__ __launch_bounds__(kBlock) void expand_mask_kernel(const vd_u64* __res
     for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
     base += before;
     __syncthreads();
+    if (TILES) {
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) base += s_prefix[w];
+        if (chunk == gridDim.x - 1u && wave == kWavesPerBlock - 1u) {   // the total: everything before this wave + its own words
+            unsigned mine = (unsigned)__popcll(my_word);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+            if (lane == 0) *out_count = base + mine;
+        }
+    }
     // survivors of kExpandGroup mask words are staged in LDS at the destination's 16-B phase and leave as
     // 16-B-per-lane stores in one contiguous run (this kernel is write-dominated: 20 B out per ~1 B in)
     char* stage = s_stage[wave];
@@ -692,14 +756,16 @@ __global__ __launch_bounds__(kBlock) void expand_mask_kernel(const vd_u64* __res
 //     otherwise it is staged in LDS at the destination's 16-B phase and leaves in 16-B-per-lane runs.
 // The dword that holds the last valid id may extend past n_total: an aligned dword that contains one valid byte
 // never crosses a page, and the extra bytes belong to instances whose mask bit is 0.
-template <bool DIRECT>
+template <bool DIRECT, bool TILES>
 __global__ __launch_bounds__(kBlock) void expand_mask_u8_kernel(const vd_u64* __restrict__ mask, unsigned n_words, unsigned wps,
                                                                 unsigned shard_size, unsigned n_total, unsigned first_instance,
                                                                 const unsigned char* __restrict__ mesh_ids,
                                                                 const VdMeshInfo* __restrict__ meshes, unsigned n_mesh,
                                                                 VdDrawIndexedIndirect* __restrict__ out,
-                                                                const vd_u64* __restrict__ chunk_entry) {
+                                                                const vd_u64* __restrict__ chunk_entry,
+                                                                const unsigned* __restrict__ tile_count, unsigned* __restrict__ out_count) {
     constexpr int kGroups = kExpandWords / kExpandGroup;
+    __shared__ unsigned s_prefix[kWavesPerBlock];
     __shared__ __attribute__((aligned(16))) unsigned s_tab[256][4];
     constexpr int kStageBytes = DIRECT ? 16 : kExpandGroup * 1280 + 32;
     __shared__ __attribute__((aligned(16))) char s_stage[kWavesPerBlock][kStageBytes];
@@ -708,8 +774,14 @@ __global__ __launch_bounds__(kBlock) void expand_mask_u8_kernel(const vd_u64* __
     const unsigned chunk = blockIdx.x;
     const unsigned cw0 = chunk * kChunkWords;
     const unsigned w0 = cw0 + wave * kExpandWords;
-    unsigned base = (unsigned)chunk_entry[chunk];
-    if (base == 0xffffffffu) return;                       // the scan gave up (mask_scan_kernel): no list
+    unsigned base = 0;
+    if (TILES) {
+        const unsigned part = tile_prefix_partial(tile_count, chunk * kChunkTiles);
+        if (lane == 0) s_prefix[wave] = part;
+    } else {
+        base = (unsigned)chunk_entry[chunk];
+        if (base == 0xffffffffu) return;                   // the scan gave up (mask_scan_kernel): no list
+    }
     // survivors of the chunk's earlier waves: lane l looks at words cw0 + l and cw0 + 64 + l
     unsigned before = 0;
     if (lane < wave * kExpandWords && cw0 + lane < n_words) before = (unsigned)__popcll(mask[cw0 + lane]);
@@ -758,6 +830,17 @@ __global__ __launch_bounds__(kBlock) void expand_mask_u8_kernel(const vd_u64* __
     for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
     base = __builtin_amdgcn_readfirstlane(base + before);
     __syncthreads();
+    if (TILES) {
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) base += s_prefix[w];
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (chunk == gridDim.x - 1u && wave == kWavesPerBlock - 1u) {   // the total: everything before this wave + its own words
+            unsigned mine = (unsigned)__popcll(my_word);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+            if (lane == 0) *out_count = base + mine;
+        }
+    }
     const unsigned max_mid = n_mesh - 1u;
     const unsigned inst_lane = first_instance + lane;
     const unsigned id_shift = 8u * (lane & 3u);
@@ -982,7 +1065,8 @@ __global__ __launch_bounds__(kBlock) void indices_to_draws_kernel(const unsigned
 }
 
 // Host side of pass 2 (shared by vd_cull_compact* and vd_expand_mask_dev).
-// Pass 2a: per-chunk survivor counts -> exclusive offsets (ctx->expand_state) and the total (*d_out_count).
+// Pass 2a (vd_expand_mask_dev, vd_mask_to_indices_dev; not vd_cull_compact*): per-chunk survivor counts -> exclusive
+// offsets (ctx->expand_state) and the total (*d_out_count).
 static int launch_mask_scan(VdCtx* ctx, const vd_u64* d_mask, unsigned n_words, unsigned* d_out_count, vd_u64** out_entries) {
     const unsigned n_chunks = (n_words + kChunkWords - 1) / kChunkWords;
     const size_t need = sizeof(ScanState) + (size_t)n_chunks * 8;
@@ -1003,13 +1087,19 @@ static int launch_mask_scan(VdCtx* ctx, const vd_u64* d_mask, unsigned n_words, 
     return VD_OK;
 }
 
+// Pass 2b behind it.  d_tile_count = pass 1's survivors per tile of THIS mask as one shard (launch_mask_pass): then the
+// expansion places its chunks from that table and no scan is launched.  Null (a mask that pass 1 of this call did not
+// write: vd_expand_mask_dev): mask_scan_kernel first.
 static int launch_expand(VdCtx* ctx, const vd_u64* d_mask, unsigned n_words, unsigned wps, unsigned shard_size,
                          unsigned n_total, unsigned first_instance, const void* d_ids, unsigned id_bytes,
-                         const VdMeshInfo* d_meshes, unsigned n_mesh, VdDrawIndexedIndirect* d_out, unsigned* d_out_count) {
+                         const VdMeshInfo* d_meshes, unsigned n_mesh, VdDrawIndexedIndirect* d_out, unsigned* d_out_count,
+                         const unsigned* d_tile_count = nullptr) {
     const unsigned n_chunks = (n_words + kChunkWords - 1) / kChunkWords;
-    vd_u64* offsets;
-    int rc_scan = launch_mask_scan(ctx, d_mask, n_words, d_out_count, &offsets);
-    if (rc_scan) return rc_scan;
+    vd_u64* offsets = nullptr;
+    if (!d_tile_count) {
+        int rc_scan = launch_mask_scan(ctx, d_mask, n_words, d_out_count, &offsets);
+        if (rc_scan) return rc_scan;
+    }
     const bool one_shard = wps >= n_words;
     const bool tab = n_mesh <= 512u;
     // fast path: 1-byte ids that can be fetched as aligned dwords (every word's first instance is a multiple of 4)
@@ -1018,23 +1108,26 @@ static int launch_expand(VdCtx* ctx, const vd_u64* d_mask, unsigned n_words, uns
     if (fast) {
         // up to ~250 MB of commands (the Infinity Cache absorbs them) the direct form is at the write ceiling; past
         // that the L2 merges fewer of its 4-byte pieces in time and the LDS-staged 16-byte runs win
-#define VD_EXPAND_U8(D)                                                                                                   \
-        hipLaunchKernelGGL((expand_mask_u8_kernel<D>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps,  \
-                           shard_size, n_total, first_instance, reinterpret_cast<const unsigned char*>(d_ids), d_meshes,    \
-                           n_mesh, d_out, offsets)
-        if (n_total <= (12u << 20)) VD_EXPAND_U8(true);
-        else VD_EXPAND_U8(false);
+#define VD_EXPAND_U8(D, T)                                                                                                  \
+        hipLaunchKernelGGL((expand_mask_u8_kernel<D, T>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps, \
+                           shard_size, n_total, first_instance, reinterpret_cast<const unsigned char*>(d_ids), d_meshes,      \
+                           n_mesh, d_out, offsets, d_tile_count, d_out_count)
+        const bool direct = n_total <= (12u << 20);
+        if (d_tile_count) { if (direct) VD_EXPAND_U8(true, true); else VD_EXPAND_U8(false, true); }
+        else { if (direct) VD_EXPAND_U8(true, false); else VD_EXPAND_U8(false, false); }
 #undef VD_EXPAND_U8
         return VD_OK;
     }
-#define VD_EXPAND(IdT, T)                                                                                               \
-    hipLaunchKernelGGL((expand_mask_kernel<IdT, T>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps,  \
+#define VD_EXPAND_T(IdT, T, S)                                                                                             \
+    hipLaunchKernelGGL((expand_mask_kernel<IdT, T, S>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps, \
                        shard_size, n_total, first_instance, reinterpret_cast<const IdT*>(d_ids), d_meshes, n_mesh, d_out,    \
-                       offsets)
+                       offsets, d_tile_count, d_out_count)
+#define VD_EXPAND(IdT, T) do { if (d_tile_count) VD_EXPAND_T(IdT, T, true); else VD_EXPAND_T(IdT, T, false); } while (0)
     if (id_bytes == 1u) { if (tab) VD_EXPAND(unsigned char, true); else VD_EXPAND(unsigned char, false); }
     else if (id_bytes == 2u) { if (tab) VD_EXPAND(unsigned short, true); else VD_EXPAND(unsigned short, false); }
     else { if (tab) VD_EXPAND(unsigned, true); else VD_EXPAND(unsigned, false); }
 #undef VD_EXPAND
+#undef VD_EXPAND_T
     return VD_OK;
 }
 
@@ -1189,31 +1282,36 @@ int vd_cull_emit_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
     return vd_cull_emit_shard_dev(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, 0u, d_out);
 }
 
-// Pass 1 of the split forms: instances -> one bit + a compact mesh id each, in ctx scratch.
+// Pass 1 of the split forms: instances -> one bit + a compact mesh id each, and the survivors of every 1024-instance
+// tile (*out_tile_count, padded to whole 16-byte groups; the emit path ignores it), in ctx scratch.
 static int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                            const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids, unsigned* out_id_bytes) {
+                            const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids, unsigned* out_id_bytes,
+                            unsigned** out_tile_count) {
     const unsigned n_words = (n_inst + 63u) / 64u;
     const unsigned id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
-    const size_t need = (size_t)n_words * 8 + (size_t)n_inst * id_bytes + 512;
+    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
+    const size_t ids_off = ((size_t)n_words * 8 + 255) & ~(size_t)255;
+    const size_t counts_off = (ids_off + (size_t)n_inst * id_bytes + 15) & ~(size_t)15;
+    const size_t need = counts_off + (((size_t)n_mt + 3) & ~(size_t)3) * 4 + 512;
     int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, need);
     if (rc) return rc;
     vd_u64* d_mask = reinterpret_cast<vd_u64*>(ctx->scratch);
-    void* d_ids = reinterpret_cast<char*>(ctx->scratch) + (((size_t)n_words * 8 + 255) & ~(size_t)255);
+    void* d_ids = reinterpret_cast<char*>(ctx->scratch) + ids_off;
+    unsigned* d_counts = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctx->scratch) + counts_off);
     vd_time_begin(ctx);
-    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
     unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
     if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
 #define VD_SPLIT(IdT)                                                                                              \
     hipLaunchKernelGGL(cull_mask_tiled_kernel<IdT>, dim3(mb), dim3(kBlock),                                        \
                        kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
                        ctx->stream, make_cam(camera), d_meshes, n_mesh, d_instances, n_inst, d_mask,               \
-                       reinterpret_cast<IdT*>(d_ids), n_mt)
+                       reinterpret_cast<IdT*>(d_ids), d_counts, n_mt)
     if (id_bytes == 1u) VD_SPLIT(unsigned char);
     else if (id_bytes == 2u) VD_SPLIT(unsigned short);
     else VD_SPLIT(unsigned);
 #undef VD_SPLIT
     vd_time_mid(ctx);
-    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = id_bytes;
+    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = id_bytes; *out_tile_count = d_counts;
     return VD_OK;
 }
 
@@ -1227,8 +1325,8 @@ int vd_cull_emit_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMe
     if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null instances/out");
     if (ctx->option(VD_OPT_CULL_VARIANT, 0) <= 0 && n_inst >= ctx->split_min) {
         // split form, as for the compacted list: the 20-byte stores leave the read stream
-        vd_u64* d_mask; void* d_ids; unsigned id_bytes;
-        int rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes);
+        vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
+        int rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
         if (rc) return rc;
         const unsigned quads = (n_inst + 3u) / 4u;
         unsigned eb = (quads + kBlock - 1) / kBlock;
@@ -1283,15 +1381,16 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
     if (variant <= 0 && n_inst >= ctx->split_min) {
         // Split form (default for large inputs): pass 1 streams the instances and writes only one bit
         // + a compact mesh id per instance (reads run at ~6.4 TB/s when no 20-byte commands are stored
-        // in the same kernel); pass 2 expands the bits into the ordered command list.  Mixing the
-        // command stores into the read stream costs more than the 1-5 B/instance round trip
+        // in the same kernel) and the survivors per tile; pass 2 expands the bits into the ordered
+        // command list, placing each chunk from the tile counts: two launches, no scan kernel.  Mixing
+        // the command stores into the read stream costs more than the 1-5 B/instance round trip
         // (A/B: profiles/).
-        vd_u64* d_mask; void* d_ids; unsigned id_bytes;
-        rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes);
+        vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
+        rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
         if (rc) return rc;
         const unsigned n_words = (n_inst + 63u) / 64u;
         rc = launch_expand(ctx, d_mask, n_words, n_words, n_inst, n_inst, first_instance, d_ids, id_bytes, d_meshes, n_mesh,
-                           d_out, d_out_count);
+                           d_out, d_out_count, d_tile_count);
         if (rc) return rc;
         vd_time_end(ctx);
         if (pad_tail) {
