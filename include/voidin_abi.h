@@ -159,7 +159,7 @@ typedef enum VdStatus {
     VD_ERR_NO_DEVICE = -5,       /* no gfx950 device / extension built for another arch  */
     VD_ERR_STACK_OVERFLOW = -6,  /* traversal stack exceeded (reference has no check:
                                     shaders/utils/stack.wgsl:1-20).  vd_trace*: only for a
-                                    stack of more than 8 Mi entries (see there);
+                                    stack of more than 128 + 4 Mi entries (see there);
                                     vd_traverse_iter / vd_traverse: beyond 128           */
     VD_ERR_OOM = -7,
     VD_ERR_COMM = -8             /* RCCL: library not found, communicator or collective failed;
@@ -510,7 +510,7 @@ typedef struct VdTraceScene {
  * by a second pass whose stack goes on in global memory (grow-only scratch of the context,
  * allocated when first needed: 1 Ki entries per lane, then 4 Ki, ... under a 256 MB budget) -
  * same visits, same arithmetic, same record as an unbounded stack gives; calls without such a
- * ray pay nothing.  VD_ERR_STACK_OVERFLOW is left for a stack deeper than 8 Mi entries or than
+ * ray pay nothing.  VD_ERR_STACK_OVERFLOW is left for a stack deeper than 128 + 4 Mi entries or than
  * the scene has nodes (cyclic node arrays).  BLAS leaves hold at most 3 triangles
  * (what BvhBuilder makes, blas.rs:108); anything else is VD_ERR_INVALID_ARG, and so is a TLAS
  * leaf a ray ENTERS whose instance index, whose mesh's BLAS root or whose root's children lie

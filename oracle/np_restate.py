@@ -304,11 +304,14 @@ def _tri(eye, d, v0, v1, v2, hit):
     return t if (t > 0 and t < hit) else None
 
 
-def trace(scene, rays):
-    """scene = (tlas_nodes, instances, meshes, bvh_nodes, vertices[*,3], indices)."""
+def trace(scene, rays, depths=False):
+    """scene = (tlas_nodes, instances, meshes, bvh_nodes, vertices[*,3], indices).  depths=True: also each ray's shared far-only
+    depth (uint32) - the most entries pending right after a pop, TLAS entries counted underneath the BLAS ones (the walk pushes
+    {far, near} and pops near at once, so what is left after a pop are the pending far children)."""
     tl, inst, meshes, bn, verts, idx = scene
     verts = np.asarray(verts, F).reshape(-1, 3)
     out = np.zeros(len(rays), dtype=abi.HIT)
+    far = np.zeros(len(rays), dtype=np.uint32)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         for ri, ray in enumerate(rays):
             eye, d = ray["eye"].astype(F), ray["dir"].astype(F)
@@ -317,6 +320,7 @@ def trace(scene, rays):
             st = [0]
             while st:
                 node = tl[st.pop()]
+                far[ri] = max(far[ri], len(st))
                 if node["left_right"] == 0:
                     I = inst[node["instance_idx"]]
                     mesh = meshes[min(int(I["mesh"]), len(meshes) - 1)]
@@ -328,6 +332,7 @@ def trace(scene, rays):
                     h = dist
                     while bs:
                         nd = bn[bs.pop()]
+                        far[ri] = max(far[ri], len(st) + len(bs))
                         if nd["count"] > 0:
                             for i in range(int(nd["count"])):
                                 t3 = int(nd["left_first"]) + i
@@ -360,7 +365,7 @@ def trace(scene, rays):
                         st.append(b)
                     st.append(a)
             out[ri]["dist"], out[ri]["hit"] = dist, hit
-    return out
+    return (out, far) if depths else out
 
 
 # ---- the CPU harness: per-pixel rays + Bvh::traverse_iter (src/bin/bvh_cpu.rs:71-96, blas.rs:247-295) ----

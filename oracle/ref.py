@@ -41,8 +41,11 @@ def load() -> C.CDLL:
             "vd_ref_tlas_refit": (_I, [_P, _U, _P, _U, _P]),
             "vd_ref_tlas_refit_wide": (_I, [_P, _U, _P, _U, _P]),
             "vd_ref_trace": (_I, [C.POINTER(abi.TraceScene), _P, _U, _P, _P, _I]),
+            "vd_ref_trace_depths": (_I, [C.POINTER(abi.TraceScene), _P, _U, _P, _P, _P, _P, _I]),
             "vd_ref_traverse_iter": (_I, [_P, _U, _P, _P, _P, _U, _P]),
+            "vd_ref_traverse_iter_depths": (_I, [_P, _U, _P, _P, _P, _U, _P, _P]),
             "vd_ref_traverse": (_I, [_P, _U, _P, _P, _P, _U, C.c_float, _P]),
+            "vd_ref_traverse_depths": (_I, [_P, _U, _P, _P, _P, _U, C.c_float, _P, _P]),
             "vd_ref_shadow_rays": (_I, [_P, _P, _U, _P, _P]),
             "vd_ref_primary_rays": (_I, [_P, _U, _U, _P]),
             "vd_ref_hiz_layout": (_I, [_U, _U, _P]),
@@ -157,14 +160,22 @@ def make_scene(tlas_nodes, instances, meshes, bvh_nodes, vertices, indices):
     return s, arrs
 
 
-def trace(scene_arrays, rays, threads=1):
-    """scene_arrays = (tlas_nodes, instances, meshes, bvh_nodes, vertices, indices)."""
+def trace(scene_arrays, rays, threads=1, depths=False, first_hit=False):
+    """scene_arrays = (tlas_nodes, instances, meshes, bvh_nodes, vertices, indices).  Returns (hits, deepest use of an oracle
+    stack); with depths=True also each ray's shared far-only depth (uint32; see vd_ref_trace_depths in vd_oracle.h) - the
+    unit vd_trace's 128 entries are stated in: a ray takes the second pass iff its depth is above 128; with first_hit=True
+    (implies depths) also the pending entries, same unit, when the ray's first triangle was accepted (0xffffffff: none)."""
     s, keep = make_scene(*scene_arrays)
     rays = _c(rays, abi.RAY)
     out = np.zeros(len(rays), dtype=abi.HIT)
     ms = C.c_uint32(0)
-    _chk(load().vd_ref_trace(C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data, C.addressof(ms), threads))
-    return out, ms.value
+    if not depths and not first_hit:
+        _chk(load().vd_ref_trace(C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data, C.addressof(ms), threads))
+        return out, ms.value
+    far, at_hit = np.zeros(len(rays), dtype=np.uint32), np.zeros(len(rays), dtype=np.uint32)
+    _chk(load().vd_ref_trace_depths(C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data, C.addressof(ms), far.ctypes.data,
+                                    at_hit.ctypes.data if first_hit else None, threads))
+    return (out, ms.value, far, at_hit) if first_hit else (out, ms.value, far)
 
 
 def shadow_rays(positions, normals, light_position):
@@ -205,20 +216,24 @@ def occlusion_mask(camera, meshes, instances, pyramid, width, height, mask_in):
     return out
 
 
-def traverse_iter(nodes, verts, indices, rays):
+def traverse_iter(nodes, verts, indices, rays, depths=False):
+    """depths=True: also the entries each ray's walk asks of its stack under its own push rule (vd_ref_traverse_iter_depths)."""
     nodes, verts = _c(nodes, abi.BVH_NODE), _c(verts, np.float32).reshape(-1)
     indices, rays = _c(indices, np.uint32).reshape(-1), _c(rays, abi.RAY)
     out = np.zeros(len(rays), dtype=np.float32)
-    _chk(load().vd_ref_traverse_iter(nodes.ctypes.data, len(nodes), verts.ctypes.data,
-                                     indices.ctypes.data, rays.ctypes.data, len(rays), out.ctypes.data))
-    return out
+    need = np.zeros(len(rays), dtype=np.uint32)
+    _chk(load().vd_ref_traverse_iter_depths(nodes.ctypes.data, len(nodes), verts.ctypes.data, indices.ctypes.data, rays.ctypes.data,
+                                            len(rays), out.ctypes.data, need.ctypes.data if depths else None))
+    return (out, need) if depths else out
 
 
-def traverse_recursive(nodes, verts, indices, rays, t0=1e30):
-    """Bvh::traverse (blas.rs:211-245, R3; dead code in the reference): Hit(t) -> t (t0 itself if nothing nearer), Miss -> -1."""
+def traverse_recursive(nodes, verts, indices, rays, t0=1e30, depths=False):
+    """Bvh::traverse (blas.rs:211-245, R3; dead code in the reference): Hit(t) -> t (t0 itself if nothing nearer), Miss -> -1.
+    depths=True: also each ray's largest number of pending right children (vd_ref_traverse_depths)."""
     nodes, verts = _c(nodes, abi.BVH_NODE), _c(verts, np.float32).reshape(-1)
     indices, rays = _c(indices, np.uint32).reshape(-1), _c(rays, abi.RAY)
     out = np.zeros(len(rays), dtype=np.float32)
-    _chk(load().vd_ref_traverse(nodes.ctypes.data, len(nodes), verts.ctypes.data, indices.ctypes.data, rays.ctypes.data, len(rays),
-                                float(t0), out.ctypes.data))
-    return out
+    pend = np.zeros(len(rays), dtype=np.uint32)
+    _chk(load().vd_ref_traverse_depths(nodes.ctypes.data, len(nodes), verts.ctypes.data, indices.ctypes.data, rays.ctypes.data, len(rays),
+                                       float(t0), out.ctypes.data, pend.ctypes.data if depths else None))
+    return (out, pend) if depths else out

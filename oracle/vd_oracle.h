@@ -60,6 +60,16 @@ int vd_ref_tlas_refit_wide(const VdInstance* instances, uint32_t n, const VdMesh
  * receives the deepest stack use seen (the reference's 24-entry stack is unchecked).    */
 int vd_ref_trace(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
                  uint32_t* out_max_stack, int threads);
+/* The same walk; out_far_depth (optional, one per ray) receives the ray's SHARED FAR-ONLY depth: the largest number of
+ * pending entries when TLAS and BLAS entries are counted on one stack and only the far child is pushed (the near child is
+ * walked at once).  A pure function of this walk: the reference pushes {far, near} and pops near at once, so what is left
+ * after a pop are the pending far children, and inside an instance the TLAS entries pending when its leaf was popped lie
+ * underneath.  This is the unit of vd_trace's "128 entries" (include/voidin_abi.h).  The oracle's own stacks hold 32 768
+ * entries each: more than a scene of the 16-bit TLAS layout has leaves.
+ * out_hit_pending (optional, one per ray): that same count of pending entries at the moment the ray's FIRST triangle was
+ * accepted - where an occlusion walk (vd_trace_any*) stops - or 0xffffffff for a ray that hits nothing.                  */
+int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
+                        uint32_t* out_max_stack, uint32_t* out_far_depth, uint32_t* out_hit_pending, int threads);
 /* crates/bvh/src/blas.rs:247-295 + intersection.rs:47-92 (R2, BLAS only, Rust CPU harness).
  * out_dist[i] = t, or -1 for Dist::Miss.                                                 */
 /* Shadow rays of src/bin/raytraced_shadows.wgsl:90-97: eye = pos + nor * 0.0001, dir = light - pos. */
@@ -72,11 +82,21 @@ int vd_ref_primary_rays(const VdCameraUniform* camera, uint32_t width, uint32_t 
 int vd_ref_traverse_iter(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz,
                          const uint32_t* indices, const VdRay* rays, uint32_t n_rays,
                          float* out_dist);
+/* out_need (optional, one per ray): the entries the walk's own push rule asks for - the largest `head + 2` at a push
+ * (blas.rs:289-291 pushes the near child and, when hit, the far one; room for both is checked before either).  A stack of
+ * K entries serves the ray iff out_need <= K.                                                                            */
+int vd_ref_traverse_iter_depths(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz,
+                                const uint32_t* indices, const VdRay* rays, uint32_t n_rays,
+                                float* out_dist, uint32_t* out_need);
 
 /* crates/bvh/src/blas.rs:211-245 (R3): the recursive Bvh::traverse, unused in the reference (bvh_cpu.rs:86 is commented
  * out).  out_dist[i] = t of Hit(t) - which is t0 itself when the root box is entered and no triangle is nearer - or -1 for Miss. */
 int vd_ref_traverse(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz,
                     const uint32_t* indices, const VdRay* rays, uint32_t n_rays, float t0, float* out_dist);
+/* out_pending (optional, one per ray): the largest number of right children waiting for their left sibling's subtree to
+ * return - what an explicit stack of pending right children must hold.  (The recursion itself is cut at 4096 levels.)  */
+int vd_ref_traverse_depths(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, const uint32_t* indices,
+                           const VdRay* rays, uint32_t n_rays, float t0, float* out_dist, uint32_t* out_pending);
 
 /* CPU twin of the HiZ occlusion extension (no reference code exists: SURVEY.md 8a C4); definitions in voidin_abi.h */
 int vd_ref_hiz_layout(uint32_t width, uint32_t height, VdHizLayout* out);

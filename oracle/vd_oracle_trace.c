@@ -15,7 +15,18 @@
 #include <pthread.h>
 #include <stdlib.h>
 
-#define REF_STACK 256
+/* Entries of each oracle stack.  The 16-bit TLAS layout has fewer than 32 768 leaves and a walk never holds more entries than
+ * the tree has leaves, so the top-level walk cannot overflow it; 2 x 128 KiB of thread stack per ray walk. */
+#define REF_STACK 32768
+
+/* What a walk reports besides the record.  max_stack: the deepest use of either oracle stack (both children pushed, as the
+ * reference does).  far_depth: the SHARED FAR-ONLY depth of the current ray - the largest number of pending entries when
+ * TLAS and BLAS entries are counted on one stack and only the far child is pushed (the near child is walked at once): the
+ * quantity include/voidin_abi.h states vd_trace's 128 entries in.  The reference pushes {far, near} and pops near at
+ * once, so the entries left right after a pop are exactly the pending far children; inside an instance the TLAS entries
+ * pending when its leaf was popped (tl_pending) lie underneath.  hit_pending: that same count at the moment the ray's FIRST
+ * triangle was accepted (where an occlusion walk stops), 0xffffffff while none was. */
+typedef struct { uint32_t max_stack, far_depth, tl_pending, hit_pending; } walk_stat;
 
 typedef struct { v3 eye, dir, inv_dir; } ray_t;
 
@@ -64,13 +75,14 @@ static inline v3 fetch_vertex(const VdTraceScene* s, uint32_t idx, const VdMeshI
 
 /* bvh.wgsl:35-76 */
 static int traverse_bvh(const VdTraceScene* s, const ray_t* ray, const VdMeshInfo* mesh,
-                        VdHit* res, uint32_t inst_id, uint32_t* max_stack) {
+                        VdHit* res, uint32_t inst_id, walk_stat* ws) {
     uint32_t stack[REF_STACK];
     uint32_t head = 0;
     stack[head++] = mesh->bvh_index;
     float hit = res->dist;
     while (head > 0) {
         VdBvhNode node = s->bvh_nodes[stack[--head]];
+        if (ws->tl_pending + head > ws->far_depth) ws->far_depth = ws->tl_pending + head;
         if (node.count > 0) {
             for (uint32_t i = 0; i < node.count; ++i) {
                 uint32_t idx = node.left_first + i;
@@ -78,6 +90,7 @@ static int traverse_bvh(const VdTraceScene* s, const ray_t* ray, const VdMeshInf
                 v3 v1 = fetch_vertex(s, 3u * idx + 1u, mesh);
                 v3 v2 = fetch_vertex(s, 3u * idx + 2u, mesh);
                 if (intersect_trig_wgsl(ray, v0, v1, v2, &hit)) {
+                    if (ws->hit_pending == 0xffffffffu) ws->hit_pending = ws->tl_pending + head;
                     res->dist = hit; res->hit = 1; res->instance = inst_id; res->triangle = idx;
                 }
             }
@@ -96,7 +109,7 @@ static int traverse_bvh(const VdTraceScene* s, const ray_t* ray, const VdMeshInf
             if (head + 2 > REF_STACK) return VD_ERR_STACK_OVERFLOW;
             if (max_dist <= hit) stack[head++] = max_index;
             stack[head++] = min_index;
-            if (head > *max_stack) *max_stack = head;
+            if (head > ws->max_stack) ws->max_stack = head;
         }
     }
     return VD_OK;
@@ -104,7 +117,7 @@ static int traverse_bvh(const VdTraceScene* s, const ray_t* ray, const VdMeshInf
 
 /* bvh.wgsl:78-87 */
 static int instance_intersect(const VdTraceScene* s, const ray_t* ray, uint32_t inst_id,
-                              VdHit* res, uint32_t* max_stack) {
+                              VdHit* res, walk_stat* ws) {
     const VdInstance* instance = &s->instances[inst_id];
     uint32_t mid = instance->mesh < s->n_meshes ? instance->mesh : s->n_meshes - 1;
     const VdMeshInfo* mesh = &s->meshes[mid];
@@ -119,19 +132,21 @@ static int instance_intersect(const VdTraceScene* s, const ray_t* ray, uint32_t 
     nr.eye = v3_make(e[0], e[1], e[2]);
     nr.dir = v3_make(d[0], d[1], d[2]);
     nr.inv_dir = v3_make(1.0f / nr.dir.x, 1.0f / nr.dir.y, 1.0f / nr.dir.z);
-    return traverse_bvh(s, &nr, mesh, res, inst_id, max_stack);
+    return traverse_bvh(s, &nr, mesh, res, inst_id, ws);
 }
 
 /* bvh.wgsl:89-123 */
-static int traverse_tlas(const VdTraceScene* s, const ray_t* ray, VdHit* res, uint32_t* max_stack) {
+static int traverse_tlas(const VdTraceScene* s, const ray_t* ray, VdHit* res, walk_stat* ws) {
     uint32_t stack[REF_STACK];
     uint32_t head = 0;
     stack[head++] = 0u;
     res->dist = VD_REF_MAX_DIST; res->hit = 0; res->instance = 0xffffffffu; res->triangle = 0xffffffffu;
     while (head > 0) {
         VdTlasNode node = s->tlas_nodes[stack[--head]];
+        if (head > ws->far_depth) ws->far_depth = head;
         if (node.left_right == 0u) {
-            int rc = instance_intersect(s, ray, node.instance_idx, res, max_stack);
+            ws->tl_pending = head;
+            int rc = instance_intersect(s, ray, node.instance_idx, res, ws);
             if (rc) return rc;
         } else {
             uint32_t min_index = node.left_right & 0xffffu;
@@ -148,34 +163,44 @@ static int traverse_tlas(const VdTraceScene* s, const ray_t* ray, VdHit* res, ui
             if (head + 2 > REF_STACK) return VD_ERR_STACK_OVERFLOW;
             if (max_dist < res->dist) stack[head++] = max_index;
             stack[head++] = min_index;
-            if (head > *max_stack) *max_stack = head;
+            if (head > ws->max_stack) ws->max_stack = head;
         }
     }
     return VD_OK;
 }
 
 typedef struct {
-    const VdTraceScene* s; const VdRay* rays; uint32_t begin, end; VdHit* out;
+    const VdTraceScene* s; const VdRay* rays; uint32_t begin, end; VdHit* out; uint32_t* far_depth; uint32_t* hit_pending;
     uint32_t max_stack; int rc;
 } trace_job;
 
 static void* trace_thread(void* p) {
     trace_job* j = (trace_job*)p;
     j->rc = VD_OK; j->max_stack = 0;
+    walk_stat ws = {0u, 0u, 0u, 0xffffffffu};
     for (uint32_t i = j->begin; i < j->end; ++i) {
         ray_t r;
         r.eye = v3_load(j->rays[i].eye);
         r.dir = v3_load(j->rays[i].dir);
         /* intersections.wgsl:9-11 ray_new: inv_dir = 1. / dir */
         r.inv_dir = v3_make(1.0f / r.dir.x, 1.0f / r.dir.y, 1.0f / r.dir.z);
-        int rc = traverse_tlas(j->s, &r, &j->out[i], &j->max_stack);
+        ws.far_depth = 0u; ws.tl_pending = 0u; ws.hit_pending = 0xffffffffu;
+        int rc = traverse_tlas(j->s, &r, &j->out[i], &ws);
         if (rc && !j->rc) j->rc = rc;
+        if (j->far_depth) j->far_depth[i] = ws.far_depth;
+        if (j->hit_pending) j->hit_pending[i] = ws.hit_pending;
     }
+    j->max_stack = ws.max_stack;
     return NULL;
 }
 
 int vd_ref_trace(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
                  uint32_t* out_max_stack, int threads) {
+    return vd_ref_trace_depths(scene, rays, n_rays, out, out_max_stack, NULL, NULL, threads);
+}
+
+int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
+                        uint32_t* out_max_stack, uint32_t* out_far_depth, uint32_t* out_hit_pending, int threads) {
     if (!scene || !scene->tlas_nodes || !scene->instances || !scene->meshes || !scene->bvh_nodes ||
         !scene->vertices || !scene->indices || (n_rays && (!rays || !out)))
         return VD_ERR_INVALID_ARG;
@@ -185,7 +210,7 @@ int vd_ref_trace(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, 
     pthread_t tid[256];
     trace_job job[256];
     for (int t = 0; t < threads; ++t) {
-        job[t].s = scene; job[t].rays = rays; job[t].out = out;
+        job[t].s = scene; job[t].rays = rays; job[t].out = out; job[t].far_depth = out_far_depth; job[t].hit_pending = out_hit_pending;
         job[t].begin = (uint32_t)((uint64_t)n_rays * t / threads);
         job[t].end = (uint32_t)((uint64_t)n_rays * (t + 1) / threads);
         if (threads == 1 || pthread_create(&tid[t], NULL, trace_thread, &job[t]) != 0) {
@@ -249,6 +274,12 @@ static inline int dist_gt(dist_t a, dist_t b) {
 int vd_ref_traverse_iter(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz,
                          const uint32_t* indices, const VdRay* rays, uint32_t n_rays,
                          float* out_dist) {
+    return vd_ref_traverse_iter_depths(nodes, n_nodes, verts_xyz, indices, rays, n_rays, out_dist, NULL);
+}
+
+int vd_ref_traverse_iter_depths(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz,
+                                const uint32_t* indices, const VdRay* rays, uint32_t n_rays,
+                                float* out_dist, uint32_t* out_need) {
     if (!nodes || !verts_xyz || !indices || (n_rays && (!rays || !out_dist)) || n_nodes == 0)
         return VD_ERR_INVALID_ARG;
     for (uint32_t r = 0; r < n_rays; ++r) {
@@ -257,6 +288,7 @@ int vd_ref_traverse_iter(const VdBvhNode* nodes, uint32_t n_nodes, const float* 
         uint32_t head = 0;
         stack[head++] = 0;
         float hit = -1.0f; /* Miss */
+        uint32_t need = 1;
         while (head > 0) {
             VdBvhNode node = nodes[stack[--head]];
             if (node.count > 0) {
@@ -279,11 +311,13 @@ int vd_ref_traverse_iter(const VdBvhNode* nodes, uint32_t n_nodes, const float* 
                 }
                 if (!min_dist.hit) continue; /* blas.rs:285-288 */
                 if (head + 2 > REF_STACK) return VD_ERR_STACK_OVERFLOW;
+                if (head + 2 > need) need = head + 2;
                 stack[head++] = min_index;
                 if (max_dist.hit) stack[head++] = max_index; /* blas.rs:289-291 */
             }
         }
         out_dist[r] = hit;
+        if (out_need) out_need[r] = need;
     }
     return VD_OK;
 }
@@ -295,7 +329,7 @@ int vd_ref_traverse_iter(const VdBvhNode* nodes, uint32_t n_nodes, const float* 
  * GIVEN when nothing closer was found, so the top-level call returns Hit(1e30) for a ray that enters the root box and
  * hits no triangle, and Miss only when the root box itself is missed.                                               */
 static dist_t traverse_rec(const VdBvhNode* nodes, const float* verts_xyz, const uint32_t* indices, v3 orig, v3 dir,
-                           uint32_t node_idx, float t, uint32_t depth, int* overflow) {
+                           uint32_t node_idx, float t, uint32_t depth, int* overflow, uint32_t pending, uint32_t* max_pending) {
     dist_t miss = {0, 0.0f};
     if (depth > 4096u) { *overflow = 1; return miss; }
     const VdBvhNode* node = &nodes[node_idx];
@@ -309,9 +343,11 @@ static dist_t traverse_rec(const VdBvhNode* nodes, const float* verts_xyz, const
             if (d >= 0.0f) t = fminf(t, d);
         }
     } else {                                                     /* blas.rs:236-243 */
-        dist_t l = traverse_rec(nodes, verts_xyz, indices, orig, dir, node->left_first, t, depth + 1u, overflow);
+        /* while the left subtree is walked this node's right child is one more pending call */
+        if (pending + 1u > *max_pending) *max_pending = pending + 1u;
+        dist_t l = traverse_rec(nodes, verts_xyz, indices, orig, dir, node->left_first, t, depth + 1u, overflow, pending + 1u, max_pending);
         if (l.hit) t = fminf(t, l.t);
-        dist_t r = traverse_rec(nodes, verts_xyz, indices, orig, dir, node->left_first + 1u, t, depth + 1u, overflow);
+        dist_t r = traverse_rec(nodes, verts_xyz, indices, orig, dir, node->left_first + 1u, t, depth + 1u, overflow, pending, max_pending);
         if (r.hit) t = fminf(t, r.t);
     }
     dist_t h = {1, t};
@@ -320,11 +356,18 @@ static dist_t traverse_rec(const VdBvhNode* nodes, const float* verts_xyz, const
 
 int vd_ref_traverse(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, const uint32_t* indices,
                     const VdRay* rays, uint32_t n_rays, float t0, float* out_dist) {
+    return vd_ref_traverse_depths(nodes, n_nodes, verts_xyz, indices, rays, n_rays, t0, out_dist, NULL);
+}
+
+int vd_ref_traverse_depths(const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, const uint32_t* indices,
+                           const VdRay* rays, uint32_t n_rays, float t0, float* out_dist, uint32_t* out_pending) {
     if (!nodes || !verts_xyz || !indices || (n_rays && (!rays || !out_dist)) || n_nodes == 0) return VD_ERR_INVALID_ARG;
     for (uint32_t r = 0; r < n_rays; ++r) {
         int overflow = 0;
-        dist_t d = traverse_rec(nodes, verts_xyz, indices, v3_load(rays[r].eye), v3_load(rays[r].dir), 0u, t0, 0u, &overflow);
+        uint32_t max_pending = 0;
+        dist_t d = traverse_rec(nodes, verts_xyz, indices, v3_load(rays[r].eye), v3_load(rays[r].dir), 0u, t0, 0u, &overflow, 0u, &max_pending);
         if (overflow) return VD_ERR_STACK_OVERFLOW;
+        if (out_pending) out_pending[r] = max_pending;
         out_dist[r] = d.hit ? d.t : -1.0f;
     }
     return VD_OK;

@@ -5,6 +5,7 @@ options are checked against that absolute tolerance in tests/test_gpu_trace_tigh
 import numpy as np
 import pytest
 
+from chain_scenes import chain_blas_scene as _chain_blas_scene, chain_scene as _chain_scene
 from conftest import fields_equal, golden
 from voidin_amd import abi, synth
 from voidin_amd.runtime import VoidinError
@@ -794,72 +795,6 @@ def test_indexed_build_declines_when_every_area_ties(ctx, oracle):
         dt = time.perf_counter() - t
         assert fields_equal(got, want)
         assert dt < 3.0, f"{dt:.1f} s: the build did not fall back to the plain chain"
-
-
-def _chain_scene(oracle, n_leaves=200):
-    """A TLAS that is one long chain - interior node k = {interior k - 1, leaf k}, spheres one unit apart along +x - in the
-    reference's node layout (leaves at 1..N, interior nodes behind them, node 0 = a copy of the root).  A ray from x = -5
-    along +x finds the chain as its NEAR child at every level and pushes the leaf: N - 1 pending entries when it reaches
-    sphere 0 - more than the 128 a lane holds (trace.hip), fewer than the oracle's 256."""
-    v, i = synth.uv_sphere(0.4, 2)
-    v = np.asarray(v, np.float32).reshape(-1, 3)
-    nodes, idx = oracle.bvh_build(v, i)
-    infos = np.zeros(1, dtype=abi.MESH_INFO)
-    infos[0]["min"], infos[0]["max"] = synth.mesh_bounds(v)
-    infos[0]["index_count"] = len(idx)
-    N = n_leaves
-    inst = np.zeros(N, dtype=abi.INSTANCE)
-    T = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
-    T[:, 3, 0] = np.arange(N, dtype=np.float32)            # column-major storage: translation in elements 12..14
-    inst["transform"] = T.reshape(N, 16)
-    Ti = T.copy(); Ti[:, 3, 0] *= np.float32(-1)
-    inst["inv_transform"] = Ti.reshape(N, 16)
-    tl = np.zeros(2 * N, dtype=abi.TLAS_NODE)
-    mn, mx = infos[0]["min"], infos[0]["max"]
-    for k in range(N):
-        tl[1 + k]["min"] = mn + np.array([k, 0, 0], np.float32)
-        tl[1 + k]["max"] = mx + np.array([k, 0, 0], np.float32)
-        tl[1 + k]["left_right"], tl[1 + k]["instance_idx"] = 0, k
-    prev = 1
-    for k in range(1, N):
-        me = N + k
-        tl[me]["min"] = np.minimum(tl[prev]["min"], tl[1 + k]["min"])
-        tl[me]["max"] = np.maximum(tl[prev]["max"], tl[1 + k]["max"])
-        tl[me]["left_right"], tl[me]["instance_idx"] = prev | ((1 + k) << 16), 0xFFFFFFFF
-        prev = me
-    tl[0] = tl[prev]
-    return (tl, inst, infos, nodes, v, idx)
-
-
-def _chain_blas_scene(oracle, n_tris=190):
-    """ONE instance whose BLAS is a hand-made chain in the reference's node layout (node 0 the root, node 1 unused, child pairs
-    behind): every interior node splits off the FARTHEST triangle as a one-triangle leaf and keeps the rest.  A ray from
-    x = -1 along +x takes the rest as its near child at every level and pushes the leaf (bvh.wgsl:56-74 pushes the far child
-    while nothing is hit): n - 3 pending BLAS entries before the first triangle test."""
-    n = n_tris
-    tri = np.zeros((n, 3, 3), np.float32)
-    tri[:, :, 0] = np.arange(n, dtype=np.float32)[:, None]
-    tri[:, 0, 1:] = [-0.5, -0.5]; tri[:, 1, 1:] = [0.0, 0.6]; tri[:, 2, 1:] = [0.5, -0.5]
-    verts, idx = tri.reshape(-1, 3).copy(), np.arange(3 * n, dtype=np.uint32)
-    levels = n - 3
-    nodes = np.zeros(2 + 2 * levels, dtype=abi.BVH_NODE)
-    box = lambda a, b: (tri[a:b].reshape(-1, 3).min(axis=0), tri[a:b].reshape(-1, 3).max(axis=0))
-    cur, hi = 0, n
-    for j in range(levels):
-        pair = 2 + 2 * j
-        nodes[cur]["min"], nodes[cur]["max"] = box(0, hi)
-        nodes[cur]["left_first"], nodes[cur]["count"] = pair, 0
-        nodes[pair + 1]["min"], nodes[pair + 1]["max"] = box(hi - 1, hi)
-        nodes[pair + 1]["left_first"], nodes[pair + 1]["count"] = hi - 1, 1
-        cur, hi = pair, hi - 1
-    nodes[cur]["min"], nodes[cur]["max"] = box(0, hi)
-    nodes[cur]["left_first"], nodes[cur]["count"] = 0, hi
-    infos = np.zeros(1, dtype=abi.MESH_INFO)
-    infos[0]["min"], infos[0]["max"] = synth.mesh_bounds(verts)
-    infos[0]["index_count"] = len(idx)
-    inst = np.zeros(1, dtype=abi.INSTANCE)
-    inst["transform"] = inst["inv_transform"] = np.eye(4, dtype=np.float32).reshape(16)
-    return (oracle.tlas_build(inst, infos), inst, infos, nodes, verts, idx)
 
 
 @pytest.mark.parametrize("kind", ["tlas chain", "blas chain"])

@@ -604,11 +604,14 @@ void trace_deep_kernel(Scene s, const VdRay* __restrict__ rays, const unsigned* 
     const RaySource src{list, n, 1u, n, next_ray};
     trace_body<ANY, PREP, false, false, true>(s, rays, src, out, out_any, overflow);
 }
-// bitmap of the first pass -> list of ray ids (any order: a ray's record depends on the ray alone)
-__global__ __launch_bounds__(256) void ovf_list_kernel(const unsigned* __restrict__ bits, unsigned n_words, unsigned* __restrict__ list, unsigned* __restrict__ count) {
+// bitmap of the first pass -> list of ray ids (any order: a ray's record depends on the ray alone).  n_words = ceil(n_rays / 32);
+// bits of the last word that name no ray of this call are dropped: the list holds n_rays ids, rays[] and out[] n_rays records.
+__global__ __launch_bounds__(256) void ovf_list_kernel(const unsigned* __restrict__ bits, unsigned n_words, unsigned n_rays, unsigned* __restrict__ list,
+                                                       unsigned* __restrict__ count) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_words) return;
     unsigned w = bits[i];
+    if (n_rays - i * 32u < 32u) w &= (1u << (n_rays - i * 32u)) - 1u;      // i < n_words: at least one ray in this word
     if (w == 0u) return;
     unsigned at = atomicAdd(count, (unsigned)__popc(w));
     while (w) { const unsigned b = (unsigned)__builtin_ctz(w); list[at++] = i * 32u + b; w &= w - 1u; }
@@ -1251,10 +1254,10 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
     // and again after a call that set any, so a call that overflows nowhere pays nothing for it.
     const unsigned ovf_words = (n_rays + 31u) / 32u;
     {
-        const void* before = ctx->trace_ovf;
+        const size_t before = ctx->trace_ovf_bytes;      // the size, not the pointer: a grown buffer may come back at the address just freed
         rc = vd_ensure(ctx, &ctx->trace_ovf, &ctx->trace_ovf_bytes, (size_t)ovf_words * 4u + 4u);
         if (rc) return rc;
-        if (ctx->trace_ovf != before || ctx->trace_ovf_dirty) VD_HIP_CHECK(ctx, hipMemsetAsync(ctx->trace_ovf, 0, ctx->trace_ovf_bytes, ctx->stream));
+        if (ctx->trace_ovf_bytes != before || ctx->trace_ovf_dirty) VD_HIP_CHECK(ctx, hipMemsetAsync(ctx->trace_ovf, 0, ctx->trace_ovf_bytes, ctx->stream));
         ctx->trace_ovf_dirty = true;       // until this call has ended cleanly
     }
     unsigned* d_ovf = reinterpret_cast<unsigned*>(ctx->trace_ovf);
@@ -1349,7 +1352,7 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
         // Some rays needed more than the 128 entries a lane holds (the reference's own 24-entry stack is unchecked,
         // shaders/utils/stack.wgsl:1-20: it has no answer there at all).  They are walked again, from their start, with the entries
         // beyond 128 in a slab of global memory - same visits, same arithmetic, so the records are the ones an unbounded stack gives
-        // (tests/test_gpu_tlas_trace.py holds them against the oracle's 256-entry walk).  Entries per lane grow 1 Ki -> 4 Ki -> ...
+        // (tests/test_gpu_trace_deep.py holds them against the oracle through the first four sizes).  Entries per lane grow 1 Ki -> 4 Ki -> ...
         // until nothing overflows; the slab is waves x 64 lanes x entries x 4 B under a 256 MB budget (fewer waves as it deepens),
         // and a stack cannot hold more entries than the scene has nodes.
         const bool prep_walked = d_tris && (!gate || ctx->host_pinned[2] == 0u);
@@ -1358,7 +1361,7 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
         const size_t budget = (size_t)256 << 20;
         for (size_t cap = 1024;; cap *= 4) {
             const size_t per_wave = cap * 64u * 4u;
-            if (per_wave > ((size_t)2 << 30)) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_trace: a ray's traversal stack needs more than 8 Mi entries");
+            if (per_wave > ((size_t)2 << 30)) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_trace: a ray's traversal stack needs more than 128 + 4 Mi entries");
             const unsigned waves_d = (unsigned)std::max<size_t>(1, std::min<size_t>(waves, budget / per_wave));
             rc = vd_ensure(ctx, &ctx->trace_deep, &ctx->trace_deep_bytes, 256 + list_bytes + (size_t)waves_d * per_wave);
             if (rc) return rc;
@@ -1366,7 +1369,7 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
             unsigned* list = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctl) + 256);
             VD_HIP_CHECK(ctx, hipMemsetAsync(ctl, 0, 256, ctx->stream));
             VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-            hipLaunchKernelGGL(ovf_list_kernel, dim3((ovf_words + 255u) / 256u), dim3(256), 0, ctx->stream, d_ovf, ovf_words, list, ctl);
+            hipLaunchKernelGGL(ovf_list_kernel, dim3((ovf_words + 255u) / 256u), dim3(256), 0, ctx->stream, d_ovf, ovf_words, n_rays, list, ctl);
             Scene sd = s;
             sd.ovf_bits = nullptr;
             sd.deep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(list) + list_bytes);
