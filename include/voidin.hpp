@@ -441,6 +441,13 @@ struct EmitDrawsResource {                            // visibility.rs:225-228
     bool pad_tail = false;
 };
 
+struct EmitDrawsViewsResource {                       // EmitDrawsResource for several cameras of one scene (no reference counterpart)
+    DrawIndexedIndirect* draw_cmd_buffer;             // device buffer: view v's list starts at command v * view_stride
+    uint64_t view_stride;                             // in commands, >= n_instances (== n_instances packs the lists)
+    uint32_t* draw_counts;                            // device, one u32 per view
+    bool pad_tail = false;
+};
+
 class EmitDraws {
    public:
     explicit EmitDraws(Gpu& gpu) : gpu_(gpu) {}       // EmitDraws::new(&World) -> Result<Self> (visibility.rs:200-222)
@@ -455,6 +462,15 @@ class EmitDraws {
         else
             gpu_.check(vd_cull_emit_dev(gpu_.ctx(), world.camera, world.d_mesh_info, world.n_meshes, world.d_instances,
                                         world.n_instances, resources.draw_cmd_buffer));
+    }
+    // The compacted emission for n_views cameras (a contiguous array on the host, 1..VD_MAX_VIEWS; world.camera is not
+    // used) in ONE read of the instances: every view's list and count are what record() leaves for that camera.
+    void record_views(const World& world, ProfilerCommandEncoder& encoder, const CameraUniform* cameras, uint32_t n_views,
+                      EmitDrawsViewsResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_compact_views_dev(gpu_.ctx(), cameras, n_views, world.d_mesh_info, world.n_meshes, world.d_instances,
+                                             world.n_instances, resources.draw_cmd_buffer, resources.view_stride,
+                                             resources.draw_counts, resources.pad_tail ? 1 : 0));
     }
 
    private:

@@ -364,6 +364,35 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera /* host 
                               const VdInstance* d_instances, uint32_t n_inst, uint32_t first_instance,
                               VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail);
 
+/* Several views of one scene (NEW; no reference counterpart - the reference renders one view): the main camera plus
+ * shadow cascades or cube-map faces, a stereo pair, the jittered and the unjittered camera of a TAA pair.  The
+ * instances are read ONCE for all n_views cameras (2..VD_MAX_VIEWS; 1 forwards to vd_cull_compact_dev), then the
+ * ordered list of every view is written as vd_cull_compact_dev writes it.  Pinned exactly, because views are independent:
+ *   view v's list   = d_out[v * out_stride .. + d_out_counts[v]),  ascending instance order, base_instance = index
+ *                   == the bytes vd_cull_compact_dev(cameras[v], ..., d_out + v * out_stride, d_out_counts + v, pad_tail) writes;
+ *   pad_tail != 0   zeroes [count, n_inst) of every view.  Nothing else in d_out is written: not the slots
+ *                   [n_inst, out_stride) of a view and, without pad_tail, not the slots behind its count.
+ * out_stride (in commands, >= n_inst) separates two views' lists: n_inst packs them, a larger value gives every view its
+ * own buffer region (an EmitDrawsResource per view).  Always the two-pass form, at every size: one multi-view
+ * cull-to-bitmask pass, then one expansion per view - n_views + 1 launches (2 n_views + 1 with pad_tail), no scan, no wait
+ * between workgroups, hence no "gave up" state.  Like the other per-frame entry points it only enqueues kernels on the
+ * context's stream once its scratch exists (first call, or a larger scene), so it can be captured into a HIP graph; the
+ * cameras are baked in by value.  vd_last_gpu_ms_stage: 0 = the shared pass, 1 = all expansions.
+ * VD_ERR_INVALID_ARG: null ctx / cameras / meshes / counts, n_views == 0 or > VD_MAX_VIEWS, n_mesh == 0,
+ * out_stride < n_inst, null instances / out with n_inst > 0.  n_inst == 0 sets all n_views counts to 0.
+ * What the shared pass costs per view, and where it stops being free (K = 4): DESIGN.md §3.1, profiles/cull_views.md. */
+#define VD_MAX_VIEWS 8
+int vd_cull_compact_views_dev(VdCtx* ctx, const VdCameraUniform* cameras /* host, n_views */, uint32_t n_views,
+                              const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                              const VdInstance* d_instances, uint32_t n_inst,
+                              VdDrawIndexedIndirect* d_out, uint64_t out_stride /* commands between two views' lists, >= n_inst */,
+                              uint32_t* d_out_counts /* device, n_views words */, int pad_tail);
+/* host-pointer form, staged through the context and synchronous, like vd_cull_compact */
+int vd_cull_compact_views(VdCtx* ctx, const VdCameraUniform* cameras, uint32_t n_views,
+                          const VdMeshInfo* meshes, uint32_t n_mesh,
+                          const VdInstance* instances, uint32_t n_inst,
+                          VdDrawIndexedIndirect* out, uint64_t out_stride, uint32_t* out_counts, int pad_tail);
+
 /* Multi-GPU wire format (NEW): the exchange between GPUs carries ONE BIT per
  * instance instead of a 20-byte command.
  *   vd_cull_mask_dev    runs the cull and writes bit i%64 of d_mask[i/64] = emit_draws(i).instance_count

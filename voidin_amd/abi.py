@@ -46,6 +46,7 @@ assert TLAS_NODE_WIDE.itemsize == 48 and RAY.itemsize == 32 and HIT.itemsize == 
 MAX_DIST = np.float32(1e30)
 CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run their split form from this many instances
 TLAS_MAX_INSTANCES = 32768
+MAX_VIEWS = 8             # VD_MAX_VIEWS: cameras per vd_cull_compact_views* call
 
 VD_OK = 0
 VD_ERR_INVALID_ARG = -1
@@ -138,6 +139,8 @@ PROTOTYPES = {
     "vd_cull_compact_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _P, _I]),
     "vd_cull_emit_shard_dev": (_I, [_P, _P, _P, _U, _P, _U, _U, _P]),
     "vd_cull_compact_shard_dev": (_I, [_P, _P, _P, _U, _P, _U, _U, _P, _P, _I]),
+    "vd_cull_compact_views_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P, C.c_uint64, _P, _I]),
+    "vd_cull_compact_views": (_I, [_P, _P, _U, _P, _U, _P, _U, _P, C.c_uint64, _P, _I]),
     "vd_cull_mask_dev": (_I, [_P, _P, _P, _U, _P, _U, _P]),
     "vd_expand_mask_dev": (_I, [_P, _P, _U, _U, _P, _U, _P, _U, _P, _P]),
     "vd_mask_to_indices_dev": (_I, [_P, _P, _U, _U, _P, _P]),

@@ -496,6 +496,152 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_tiled_kernel(CullCamera c
     }
 }
 
+// Pass 1 for several cameras in ONE read of the instances (vd_cull_compact_views*): the load path, tile ownership and id
+// table of cull_mask_tiled_kernel above, with the view-dependent part of is_visible evaluated once per camera while the
+// instance is in registers.  The test costs ~250 vector instructions per view and instance, under 15 % of the vector
+// budget at the HBM rate, so a further view is close to free until the vector unit fills up.
+//   * ONE instantiation per id width serves every view count: the view loop is a run-time loop (not unrolled), and its
+//     22 camera dwords are fetched by scalar loads from the kernel-argument segment at a wave-uniform offset (eight
+//     cameras are 176 dwords: more than the scalar registers of a wave, and nothing a lane should hold);
+//   * the 16 ballot words of view v live in the lanes 16 (v & 3) .. + 15 of one of two 64-bit registers (v >> 2): no LDS
+//     beyond the single-view kernel's, hence the same occupancy; the flush is one 8-byte store per lane and register;
+//   * per tile: n_views x 16 mask words (view v's mask = mask + v * mask_stride), n_views survivor counts
+//     (tile_count + v * count_stride) and the mesh ids ONCE, compared before they are stored, as above.
+// No atomics, no fences, no wait on another workgroup: the kernel boundary orders all of it before the expansions.
+constexpr int kMaxViews = VD_MAX_VIEWS;
+static_assert(kMaxViews * kMaskRounds == 2 * kWave, "two ballot registers per lane hold every (view, round) word of a tile");
+struct ViewCameras { CullCamera cam[kMaxViews]; };
+
+// The part of is_visible() that depends on the camera: the same expressions in the same order, from the mesh centre
+// (c0) and max_scale the caller computed once per instance exactly as is_visible() does.
+__device__ __forceinline__ bool is_visible_view(const CullCamera& cam, const MeshRec& m, const float c0x, const float c0y, const float c0z,
+                                                const float max_scale, const float4 T0, const float4 T1, const float4 T2, const float4 T3) {
+    const float* V = cam.view;
+    float c[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float v0 = V[r], v1 = V[4 + r], v2 = V[8 + r], v3 = V[12 + r];
+        const float m0 = ((v0 * T0.x + v1 * T0.y) + v2 * T0.z) + v3 * T0.w;
+        const float m1 = ((v0 * T1.x + v1 * T1.y) + v2 * T1.z) + v3 * T1.w;
+        const float m2 = ((v0 * T2.x + v1 * T2.y) + v2 * T2.z) + v3 * T2.w;
+        const float m3 = ((v0 * T3.x + v1 * T3.y) + v2 * T3.z) + v3 * T3.w;
+        c[r] = ((m0 * c0x + m1 * c0y) + m2 * c0z) + m3 * 1.0f;
+    }
+    const float d0 = len3(m.mnx - c[0], m.mny - c[1], m.mnz - c[2]);
+    const float d1 = len3(m.mxx - c[0], m.mxy - c[1], m.mxz - c[2]);
+    const float radius = fmaxf(d0, d1) * max_scale;
+    if (c[2] * cam.frustum[1] - fabsf(c[0]) * cam.frustum[0] < -radius) return false;
+    if (c[2] * cam.frustum[3] - fabsf(c[1]) * cam.frustum[2] < -radius) return false;
+    if (c[2] + radius > cam.znear && c[2] - radius > cam.zfar) return false;
+    return true;
+}
+
+// The id table's part of a pass-1 tile, as cull_mask_tiled_kernel has it inline (that kernel is left as it is; a change
+// to the flush belongs in both places): the tile's rows as the table holds them now, and - after the rounds - the store of
+// every row that differs, or of the whole ragged last tile.
+template <typename IdT> struct TileIds {
+    static constexpr int kBytes = kMaskRounds * kWave * (int)sizeof(IdT);
+    static constexpr int kRows = kBytes / (kWave * 16);
+    u32x4 old_ids[kRows];
+    bool full_tile;
+    __device__ __forceinline__ void load(const IdT* __restrict__ ids_out, size_t tile_first, unsigned n_inst, unsigned lane) {
+        full_tile = tile_first + (size_t)kWave * kMaskRounds <= (size_t)n_inst;
+        if (full_tile) {
+#pragma unroll
+            for (int r = 0; r < kRows; ++r)
+                old_ids[r] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ids_out) + tile_first * sizeof(IdT) + (size_t)r * kWave * 16 + lane * 16u);
+        }
+    }
+    __device__ __forceinline__ void flush(IdT* __restrict__ ids_out, const IdT* s_ids, size_t tile_first, unsigned n_inst, unsigned lane) const {
+        const size_t id_base = tile_first * sizeof(IdT);                 // bytes; tile_first % 1024 == 0 -> 16-B aligned
+        const size_t id_end = min((size_t)n_inst, tile_first + (size_t)kWave * kMaskRounds) * sizeof(IdT);
+        char* gids = reinterpret_cast<char*>(ids_out);
+        if (full_tile) {
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                const unsigned b0 = (unsigned)r * kWave * 16u + lane * 16u;
+                const u32x4 nv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(s_ids) + b0);
+                const bool diff = nv.x != old_ids[r].x || nv.y != old_ids[r].y || nv.z != old_ids[r].z || nv.w != old_ids[r].w;
+                if (__any(diff)) *reinterpret_cast<u32x4*>(gids + id_base + b0) = nv;
+            }
+        } else {
+            for (unsigned b0 = lane * 16u; b0 < (unsigned)kBytes; b0 += kWave * 16u) {
+                if (id_base + b0 + 16u <= id_end) {
+                    *reinterpret_cast<u32x4*>(gids + id_base + b0) = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(s_ids) + b0);
+                } else {
+                    for (unsigned q = 0; q < 16u && id_base + b0 + q < id_end; ++q) gids[id_base + b0 + q] = reinterpret_cast<const char*>(s_ids)[b0 + q];
+                }
+            }
+        }
+    }
+};
+
+template <typename IdT>
+__global__ __launch_bounds__(kBlock, 3) void cull_mask_views_kernel(ViewCameras cams, unsigned n_views, const VdMeshInfo* __restrict__ meshes,
+                                                                     unsigned n_mesh, const VdInstance* __restrict__ inst,
+                                                                     unsigned n_inst, vd_u64* __restrict__ mask, size_t mask_stride,
+                                                                     IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
+                                                                     unsigned count_stride, unsigned n_tiles) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr int kIdBytes = TileIds<IdT>::kBytes;
+    char* slab = smem + wave * (kSlabBytes + kIdBytes);
+    IdT* s_ids = reinterpret_cast<IdT*>(slab + kSlabBytes);
+    const unsigned waves_total = gridDim.x * kWavesPerBlock;
+    auto valid_at = [&](size_t f) -> unsigned { return f < n_inst ? (unsigned)min((size_t)64, (size_t)n_inst - f) : 0u; };
+    u32x4 regs[kChunksPerLane];
+    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < n_tiles; t += waves_total) {
+        const size_t tile_first = (size_t)t * (kWave * kMaskRounds);
+        slab_fill<true>(inst, tile_first, valid_at(tile_first), lane, regs);
+        TileIds<IdT> tile_ids;                 // the id table's rows of this tile as they are now: only rows that differ are stored
+        tile_ids.load(ids_out, tile_first, n_inst, lane);
+        vd_u64 word_lo = 0, word_hi = 0;      // lane l: the ballot of view (l >> 4) [+ 4] in round l & 15
+#pragma unroll 1
+        for (int r = 0; r < kMaskRounds; ++r) {
+            const size_t first = tile_first + (size_t)r * kWave;
+            const unsigned n_valid = valid_at(first);
+            slab_store(slab, lane, regs);
+            if (r + 1 < kMaskRounds) slab_fill<true>(inst, first + kWave, valid_at(first + kWave), lane, regs);
+            vd_wave_lds_sync();
+            const LaneInst li = slab_read(slab, lane);
+            vd_wave_lds_sync();
+            const unsigned mid = min(li.mesh, n_mesh - 1u);
+            const MeshRec m = load_mesh(meshes, mid);
+            // once per instance, as is_visible() has them: center = (mesh.max + mesh.min) / 2, extract_scale, max_scale
+            const float c0x = (m.mxx + m.mnx) / 2.0f, c0y = (m.mxy + m.mny) / 2.0f, c0z = (m.mxz + m.mnz) / 2.0f;
+            const float sx = len3(li.T0.x, li.T0.y, li.T0.z), sy = len3(li.T1.x, li.T1.y, li.T1.z), sz = len3(li.T2.x, li.T2.y, li.T2.z);
+            const float max_scale = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
+            const bool live = lane < n_valid;
+#pragma unroll 1
+            for (unsigned v = 0; v < n_views; ++v) {
+                const bool vis = live && is_visible_view(cams.cam[v], m, c0x, c0y, c0z, max_scale, li.T0, li.T1, li.T2, li.T3);
+                const unsigned long long b = __ballot(vis);
+                const unsigned slot = (v & 3u) * (unsigned)kMaskRounds + (unsigned)r;
+                if (lane == slot) { if (v < 4u) word_lo = b; else word_hi = b; }
+            }
+            s_ids[r * kWave + lane] = (IdT)mid;
+        }
+        vd_wave_lds_sync();
+        // flush: every lane stores its word of each register into its view's mask; the survivors of a view are the
+        // bits of its 16 lanes
+        const size_t w0 = (size_t)t * kMaskRounds;
+        const size_t n_words = ((size_t)n_inst + 63) / 64;
+        const unsigned slot_view = lane >> 4, slot_round = lane & 15u;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned v = (unsigned)h * 4u + slot_view;
+            const vd_u64 my_word = h ? word_hi : word_lo;                // 0 where no view wrote it
+            if (v < n_views && w0 + slot_round < n_words) mask[(size_t)v * mask_stride + w0 + slot_round] = my_word;
+            unsigned survivors = (unsigned)__popcll(my_word);
+#pragma unroll
+            for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
+            if (slot_round == 0u && v < n_views) tile_count[(size_t)v * count_stride + t] = survivors;
+        }
+        tile_ids.flush(ids_out, s_ids, tile_first, n_inst, lane);
+        vd_wave_lds_sync();
+    }
+}
+
 constexpr int kExpandGroup = 4;                      // mask words staged and stored as one contiguous run
 constexpr int kExpandWords = 32;                     // mask words (64 instances each) per wave
 constexpr int kChunkWords = kWavesPerBlock * kExpandWords;   // per workgroup: 128 words = 8192 instances
@@ -1432,6 +1578,72 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
     return VD_OK;
 }
 
+// K views of one scene: ONE pass over the instances (cull_mask_views_kernel) writes K masks, K tile-count tables and the
+// id table; then the unchanged expansion runs once per view, placed from that view's table.  Always the split form:
+// K + 1 launches (2K + 1 with pad_tail), whatever the size.  Own arena (ctx->views_scratch), laid out
+// [id table | K masks | K count tables]: the id table sits at offset 0 whatever K is, so a renderer that varies its view
+// count keeps the table's rows warm, and single-view calls (ctx->scratch) in between leave it alone.  Whatever the arena
+// holds - fresh, regrown, or laid out for another size - pass 1 rewrites every id row that differs from this call's.
+int vd_cull_compact_views_dev(VdCtx* ctx, const VdCameraUniform* cameras, uint32_t n_views, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                              const VdInstance* d_instances, uint32_t n_inst, VdDrawIndexedIndirect* d_out, uint64_t out_stride,
+                              uint32_t* d_out_counts, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (!cameras || !d_meshes || n_mesh == 0 || !d_out_counts)
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null cameras/meshes/counts or n_mesh == 0");
+    if (n_views == 0 || n_views > (uint32_t)VD_MAX_VIEWS) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: n_views must be 1..VD_MAX_VIEWS");
+    if (out_stride < n_inst) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: out_stride < n_inst");
+    if (n_inst == 0) {
+        VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_counts, 0, 4 * (size_t)n_views, ctx->stream));
+        return VD_OK;
+    }
+    if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null instances/out");
+    if (n_views == 1) return vd_cull_compact_dev(ctx, cameras, d_meshes, n_mesh, d_instances, n_inst, d_out, d_out_counts, pad_tail);
+    const unsigned n_words = (n_inst + 63u) / 64u;
+    const unsigned id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
+    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
+    const size_t mask_off = ((size_t)n_inst * id_bytes + 255) & ~(size_t)255;        // (the expansion reads ids as aligned dwords)
+    const size_t mask_stride = (((size_t)n_words * 8 + 255) & ~(size_t)255) / 8;      // words between two views' masks
+    const size_t count_stride = ((size_t)n_mt + 3) & ~(size_t)3;                      // entries: whole 16-byte groups (tile_prefix_partial)
+    const size_t counts_off = mask_off + (size_t)n_views * mask_stride * 8;
+    const size_t need = counts_off + (size_t)n_views * count_stride * 4 + 512;
+    int rc = vd_ensure(ctx, &ctx->views_scratch, &ctx->views_scratch_bytes, need);
+    if (rc) return rc;
+    char* base = reinterpret_cast<char*>(ctx->views_scratch);
+    void* d_ids = base;
+    vd_u64* d_mask = reinterpret_cast<vd_u64*>(base + mask_off);
+    unsigned* d_counts = reinterpret_cast<unsigned*>(base + counts_off);
+    ViewCameras cams;
+    memset(&cams, 0, sizeof(cams));
+    for (uint32_t v = 0; v < n_views; ++v) cams.cam[v] = make_cam(cameras + v);
+    vd_time_begin(ctx);
+    unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
+#define VD_VIEWS(IdT)                                                                                              \
+    hipLaunchKernelGGL(cull_mask_views_kernel<IdT>, dim3(mb), dim3(kBlock),                                        \
+                       kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
+                       ctx->stream, cams, n_views, d_meshes, n_mesh, d_instances, n_inst, d_mask, mask_stride,     \
+                       reinterpret_cast<IdT*>(d_ids), d_counts, (unsigned)count_stride, n_mt)
+    if (id_bytes == 1u) VD_VIEWS(unsigned char);
+    else if (id_bytes == 2u) VD_VIEWS(unsigned short);
+    else VD_VIEWS(unsigned);
+#undef VD_VIEWS
+    vd_time_mid(ctx);
+    for (uint32_t v = 0; v < n_views; ++v) {
+        rc = launch_expand(ctx, d_mask + (size_t)v * mask_stride, n_words, n_words, n_inst, n_inst, 0u, d_ids, id_bytes, d_meshes, n_mesh,
+                           d_out + (size_t)v * out_stride, d_out_counts + v, d_counts + (size_t)v * count_stride);
+        if (rc) return rc;
+    }
+    vd_time_end(ctx);
+    if (pad_tail) {
+        const unsigned pblocks = (unsigned)ctx->num_cus * 4u;
+        for (uint32_t v = 0; v < n_views; ++v)
+            hipLaunchKernelGGL(pad_tail_kernel, dim3(pblocks), dim3(kBlock), 0, ctx->stream, d_out + (size_t)v * out_stride, d_out_counts + v, n_inst);
+    }
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
+}
+
 int vd_cull_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
                      const VdInstance* d_instances, uint32_t n_inst, uint64_t* d_mask) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
@@ -1656,6 +1868,53 @@ int vd_cull_compact(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo*
         VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n_copy * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
         VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return VD_OK;
+}
+
+int vd_cull_compact_views(VdCtx* ctx, const VdCameraUniform* cameras, uint32_t n_views, const VdMeshInfo* meshes, uint32_t n_mesh,
+                          const VdInstance* instances, uint32_t n_inst, VdDrawIndexedIndirect* out, uint64_t out_stride,
+                          uint32_t* out_counts, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (!cameras || !meshes || n_mesh == 0 || !out_counts)
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null cameras/meshes/counts or n_mesh == 0");
+    if (n_views == 0 || n_views > (uint32_t)VD_MAX_VIEWS) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: n_views must be 1..VD_MAX_VIEWS");
+    if (out_stride < n_inst) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: out_stride < n_inst");
+    if (n_inst > 0 && (!instances || !out)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null instances/out");
+    for (uint32_t v = 0; v < n_views; ++v) out_counts[v] = 0;      // (a refused call writes nothing)
+    if (n_inst == 0) return VD_OK;
+    // staged like vd_cull_compact: instances, meshes behind a 64-byte header that takes the counts, n_views lists of n_inst commands
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
+    if (rc) return rc;
+    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, (size_t)n_mesh * sizeof(VdMeshInfo) + 64);
+    if (rc) return rc;
+    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_views * n_inst * sizeof(VdDrawIndexedIndirect) + 16);
+    if (rc) return rc;
+    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
+    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + 64);
+    VdDrawIndexedIndirect* dout = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(ctx->stage_aux);
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
+    rc = vd_cull_compact_views_dev(ctx, cameras, n_views, dm, n_mesh, di, n_inst, dout, n_inst, d_counts, pad_tail);
+    if (rc) return rc;
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_counts, 4 * (size_t)n_views, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t v = 0; v < n_views; ++v) {
+        const uint32_t c = ctx->host_pinned[v];
+        if (c > n_inst || ctx->host_pinned[kScanFaultWord] != 0u) {   // n_views == 1 below the split size runs the fused form, whose scan can give up (vd_cull_compact)
+            ctx->host_pinned[kScanFaultWord] = 0u;
+            if (ctx->scan_state) (void)hipMemsetAsync(ctx->scan_state, 0, ctx->scan_state_bytes, ctx->stream);
+            VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_views: the compaction scan gave up waiting for a workgroup");
+        }
+        out_counts[v] = c;
+        const size_t n_copy = pad_tail ? n_inst : c;
+        if (n_copy)
+            VD_HIP_CHECK(ctx, hipMemcpyAsync(out + (size_t)v * out_stride, dout + (size_t)v * n_inst, n_copy * sizeof(VdDrawIndexedIndirect),
+                                             hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return VD_OK;
 }
 

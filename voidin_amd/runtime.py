@@ -115,6 +115,16 @@ class Context:
                                                      abi.ptr(d_inst), n_inst, first_instance, abi.ptr(d_out),
                                                      abi.ptr(d_count), int(pad_tail)))
 
+    def cull_compact_views_dev(self, cameras, d_meshes, n_mesh, d_inst, n_inst, d_out, d_counts, pad_tail: bool = False,
+                               out_stride: int | None = None):
+        """vd_cull_compact_views_dev: the instances are read once for all cameras (1..abi.MAX_VIEWS of them); view v's
+        list goes to d_out[v * out_stride ...) (in commands; default n_inst = packed), its count to d_counts[v]."""
+        cams = np.ascontiguousarray(cameras, dtype=abi.CAMERA).reshape(-1)
+        self._chk(self.lib.vd_cull_compact_views_dev(self.h, cams.ctypes.data, len(cams), abi.ptr(d_meshes), n_mesh,
+                                                     abi.ptr(d_inst), n_inst, abi.ptr(d_out),
+                                                     n_inst if out_stride is None else int(out_stride), abi.ptr(d_counts),
+                                                     int(pad_tail)))
+
     def cull_mask_dev(self, camera: np.ndarray, d_meshes, n_mesh, d_inst, n_inst, d_mask):
         cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
         self._chk(self.lib.vd_cull_mask_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst,
@@ -174,6 +184,20 @@ class Context:
                                            instances.ctypes.data, len(instances), out.ctypes.data,
                                            C.addressof(cnt), int(pad_tail)))
         return out, cnt.value
+
+    def cull_compact_views(self, cameras, meshes, instances, pad_tail=False):
+        """Host arrays in, (lists [n_views, n_inst], counts [n_views]) out; only [0, count) of a list is defined
+        (everything with pad_tail)."""
+        cams = np.ascontiguousarray(cameras, dtype=abi.CAMERA).reshape(-1)
+        meshes = np.ascontiguousarray(meshes, dtype=abi.MESH_INFO)
+        instances = np.ascontiguousarray(instances, dtype=abi.INSTANCE)
+        out = np.zeros((len(cams), len(instances)), dtype=abi.DRAW)
+        out.view(np.uint8)[:] = 0xAB
+        cnt = np.zeros(len(cams), dtype=np.uint32)
+        self._chk(self.lib.vd_cull_compact_views(self.h, cams.ctypes.data, len(cams), meshes.ctypes.data, len(meshes),
+                                                 instances.ctypes.data, len(instances), out.ctypes.data, len(instances),
+                                                 cnt.ctypes.data, int(pad_tail)))
+        return out, cnt
 
     # -- BLAS -------------------------------------------------------------------------------
     def bvh_build(self, verts, indices):
@@ -389,6 +413,13 @@ class EmitDraws:
                          draw_count_buf, pad_tail=False):
         self.ctx.cull_compact_dev(camera, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer,
                                   draw_count_buf, pad_tail)
+
+    def record_views(self, cameras, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer, draw_count_buf,
+                     pad_tail=False, out_stride=None):
+        """record_compacted for several cameras of one scene in one read of the instances: view v's list starts at
+        command v * out_stride of draw_cmd_buffer (default: n_inst), its count is word v of draw_count_buf."""
+        self.ctx.cull_compact_views_dev(cameras, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer,
+                                        draw_count_buf, pad_tail, out_stride)
 
 
 class Bvh:
