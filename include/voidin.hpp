@@ -473,6 +473,32 @@ class EmitDraws {
                                              resources.draw_counts, resources.pad_tail ? 1 : 0));
     }
 
+    // EXTENSION (occlusion culling; voidin_abi.h "Occlusion culling"): record() with draw_count set, with the occlusion test
+    // against a depth pyramid (HizPyramid, below) folded into the same read of the instances.
+    void record_hiz(const World& world, ProfilerCommandEncoder& encoder, const float* d_pyramid, uint32_t width, uint32_t height,
+                    EmitDrawsResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_compact_hiz_dev(gpu_.ctx(), world.camera, world.d_mesh_info, world.n_meshes, world.d_instances,
+                                           world.n_instances, d_pyramid, width, height, resources.draw_cmd_buffer,
+                                           resources.draw_count, resources.pad_tail ? 1 : 0));
+    }
+    // Two-pass occlusion culling.  record_early before the geometry pass: what was visible last frame (d_visible, one bit
+    // per instance in 64-bit words: OcclusionState) and is still in the frustum.  record_late after it, against the
+    // pyramid of the depth that pass drew: what the pyramid reveals, and d_visible becomes this frame's unoccluded set.
+    void record_early(const World& world, ProfilerCommandEncoder& encoder, const uint64_t* d_visible, EmitDrawsResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_early_dev(gpu_.ctx(), world.camera, world.d_mesh_info, world.n_meshes, world.d_instances,
+                                     world.n_instances, d_visible, resources.draw_cmd_buffer, resources.draw_count,
+                                     resources.pad_tail ? 1 : 0));
+    }
+    void record_late(const World& world, ProfilerCommandEncoder& encoder, const float* d_pyramid, uint32_t width, uint32_t height,
+                     uint64_t* d_visible, EmitDrawsResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_late_dev(gpu_.ctx(), world.camera, world.d_mesh_info, world.n_meshes, world.d_instances,
+                                    world.n_instances, d_pyramid, width, height, d_visible, d_visible, resources.draw_cmd_buffer,
+                                    resources.draw_count, resources.pad_tail ? 1 : 0));
+    }
+
    private:
     Gpu& gpu_;
 };
@@ -559,6 +585,7 @@ class DistEmitDraws {
 // EXTENSION (no reference counterpart: README.md:33 only links "Two-Pass Occlusion Culling"): the second pass of that
 // scheme.  `build` turns the depth buffer the first pass rendered into a min pyramid; `refine` clears, in a frustum
 // mask made by vd_cull_mask_dev, the bits of instances hidden behind it; vd_expand_mask_dev then makes the draw list.
+// (The lists themselves, in one read of the instances: pass::EmitDraws::record_hiz / record_early / record_late.)
 class HizPyramid {
    public:
     HizPyramid(const Gpu& gpu, uint32_t width, uint32_t height) : gpu_(gpu) { gpu.check(vd_hiz_layout(width, height, &layout_)); }
@@ -577,6 +604,33 @@ class HizPyramid {
    private:
     const Gpu& gpu_;
     VdHizLayout layout_{};
+};
+
+// The visibility bits the two-pass scheme carries from frame to frame (pass::EmitDraws::record_early / record_late): one bit
+// per instance in 64-bit words, owned here and zeroed - nothing was visible before the first frame, so that frame's early
+// list is empty and its late list is everything unoccluded.  The header itself stays free of the HIP runtime, so the two
+// functions that allocate (zeroed) and free device memory are the caller's: hipMalloc + hipMemset and hipFree in a HIP host,
+// the renderer's own allocator when the bits live in an imported buffer.
+class OcclusionState {
+   public:
+    using Alloc = void* (*)(size_t bytes);            // returns ZEROED device memory, or nullptr
+    using Free = void (*)(void* ptr);
+    OcclusionState(uint32_t n_instances, Alloc alloc_zeroed, Free free_fn) : n_(n_instances), free_(free_fn) {
+        bits_ = static_cast<uint64_t*>(alloc_zeroed(bytes()));
+        if (!bits_) throw Error(VD_ERR_OOM, "OcclusionState: no device memory for the visibility bits");
+    }
+    ~OcclusionState() { if (bits_ && free_) free_(bits_); }
+    OcclusionState(const OcclusionState&) = delete;
+    OcclusionState& operator=(const OcclusionState&) = delete;
+    uint64_t* visible() const { return bits_; }
+    uint32_t n_instances() const { return n_; }
+    size_t words() const { return n_ ? ((size_t)n_ + 63) / 64 : 1; }
+    size_t bytes() const { return words() * sizeof(uint64_t); }
+
+   private:
+    uint32_t n_;
+    Free free_;
+    uint64_t* bits_ = nullptr;
 };
 
 // The shadow pass's occlusion test (src/bin/raytraced_shadows.wgsl:90-102) for one point light: one ray per G-buffer

@@ -705,8 +705,9 @@ int vd_dist_allgather_dev(VdDist* dist, const void* d_send, void* d_recv, uint64
 /* ------------------------------------------------------------------------------------ */
 /* voidin has no occlusion culling: its README (README.md:33) only links "Two-Pass Occlusion
  * Culling".  These entry points are the building blocks of that scheme on top of the cull
- * path, defined here and nowhere else; they are OFF in every parity run (nothing in
- * vd_cull_* calls them).  All device pointers.
+ * path, defined here and nowhere else; they are OFF in every parity run: no vd_cull_* call of the
+ * sections above reaches them, and vd_cull_compact_hiz*, vd_cull_early_dev and vd_cull_late_dev below
+ * are the extension's own.  All device pointers (vd_cull_compact_hiz takes host pointers).
  *
  * Depth convention: the reference's camera (perspective_infinite_reverse_rh, camera.rs:130-148):
  * right-handed view space looking down -z, reverse Z — depth = ndc z, 1 at the near plane, 0 at
@@ -745,6 +746,55 @@ int vd_occlusion_mask_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */,
                           const VdInstance* d_instances, uint32_t n_inst,
                           const float* d_pyramid, uint32_t width, uint32_t height,
                           const uint64_t* d_mask_in, uint64_t* d_mask_out);
+
+/* Occlusion-culled draw lists: the ordered list of the instances that pass the frustum test AND are not occluded, from ONE
+ * read of the instances (the composition vd_cull_mask_dev -> vd_occlusion_mask_dev -> vd_expand_mask_dev reads them twice
+ * and needs a caller-built mesh-id table).  Pinned by what exists.  With
+ *   F = the bits vd_cull_mask_dev writes,   V = vd_occlusion_mask_dev(F),
+ *   P = d_prev_visible (bit i % 64 of word i / 64 = instance i, ceil(n_inst / 64) words; padding bits are ignored):
+ *   vd_cull_compact_hiz_dev   list of V, ascending instance order; the commands are the ones vd_cull_compact_dev writes
+ *                             for those instances (base_instance = index).
+ *   vd_cull_early_dev         first half of the two-pass scheme: list of E = F & P - what was visible last frame and
+ *                             is still in the frustum.  The caller draws it, then builds the pyramid of that depth.
+ *   vd_cull_late_dev          second half: list of L = V & ~P - what the new pyramid reveals - and d_visible_out = V
+ *                             (padding bits 0), next frame's P.  EVERY instance of F is tested against the pyramid, E
+ *                             included: an instance drawn this frame but hidden now leaves next frame's early list.
+ *                             d_visible_out may be d_prev_visible (in place).  F is recomputed, so nothing but the
+ *                             caller's buffers is carried from the early call; other vd_cull_* calls may run in between.
+ * Hence E and L are disjoint, E | L covers V; P = 0: late == hiz and early is empty; P = all ones: early ==
+ * vd_cull_compact_dev and late is empty.  pad_tail as in vd_cull_compact_dev (zeroes [count, n_inst)); without it nothing
+ * behind the count is written.  Always two launches (three with pad_tail), at every size: one pass over the instances
+ * that writes a bitmask, then the expansion; no scan, no wait between workgroups, hence no "gave up" state.  Like the
+ * other per-frame entry points they only enqueue kernels on the context's stream once their scratch exists (first call, or
+ * a larger scene), so an early -> vd_hiz_build_dev -> late frame can be captured into a HIP graph; the camera is baked
+ * in by value.  vd_last_gpu_ms_stage: 0 = the pass over the instances, 1 = the expansion.
+ * VD_ERR_INVALID_ARG: null ctx / camera / meshes / count, n_mesh == 0; where a pyramid is taken: null pyramid, a size
+ * vd_hiz_layout refuses, a projection that is not the kind vd_occlusion_mask_dev accepts; with n_inst > 0: null
+ * instances / out / visibility masks.  n_inst == 0 sets the count to 0 and touches nothing else.
+ * Bytes moved and measured times: DESIGN.md 3.6, profiles/cull_occlusion.md.                                           */
+int vd_cull_compact_hiz_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */,
+                            const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                            const VdInstance* d_instances, uint32_t n_inst,
+                            const float* d_pyramid, uint32_t width, uint32_t height,
+                            VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail);
+int vd_cull_early_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */,
+                      const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                      const VdInstance* d_instances, uint32_t n_inst,
+                      const uint64_t* d_prev_visible,
+                      VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail);
+int vd_cull_late_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */,
+                     const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                     const VdInstance* d_instances, uint32_t n_inst,
+                     const float* d_pyramid, uint32_t width, uint32_t height,
+                     const uint64_t* d_prev_visible, uint64_t* d_visible_out /* may alias d_prev_visible */,
+                     VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail);
+/* host-pointer form of vd_cull_compact_hiz_dev (the pyramid too: total_texels floats), staged through the context and
+ * synchronous, like vd_cull_compact                                                                                   */
+int vd_cull_compact_hiz(VdCtx* ctx, const VdCameraUniform* camera,
+                        const VdMeshInfo* meshes, uint32_t n_mesh,
+                        const VdInstance* instances, uint32_t n_inst,
+                        const float* pyramid, uint32_t width, uint32_t height,
+                        VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail);
 
 /* ------------------------------------------------------------------------------------ */
 /* Instance animation  (SURVEY.md §8f N2 — the upstream mutator of the cull / TLAS input)  */

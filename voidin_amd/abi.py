@@ -185,6 +185,10 @@ PROTOTYPES = {
     "vd_hiz_layout": (_I, [_U, _U, _P]),
     "vd_hiz_build_dev": (_I, [_P, _P, _U, _U, _P]),
     "vd_occlusion_mask_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _U, _U, _P, _P]),
+    "vd_cull_compact_hiz_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _U, _U, _P, _P, _I]),
+    "vd_cull_compact_hiz": (_I, [_P, _P, _P, _U, _P, _U, _P, _U, _U, _P, _P, _I]),
+    "vd_cull_early_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _P, _P, _I]),
+    "vd_cull_late_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _U, _U, _P, _P, _P, _P, _I]),
     "vd_compute_update_dev": (_I, [_P, _P, _U, _P, _U, C.c_float, C.c_float, _I]),
     "vd_ctx_set_timing": (_I, [_P, _I]),
     "vd_last_gpu_ms": (C.c_float, [_P]),

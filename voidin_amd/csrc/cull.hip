@@ -642,6 +642,154 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_views_kernel(ViewCameras 
     }
 }
 
+// Pass 1 of the occlusion-culled draw lists (vd_cull_compact_hiz*, vd_cull_early_dev, vd_cull_late_dev; extension, no
+// reference counterpart): the load path, tile ownership, id table and flush of cull_mask_tiled_kernel, with the frustum test
+// AND - where a pyramid is bound - the occlusion test evaluated while the instance is in registers, so the list of
+// unoccluded instances costs one read of the instances instead of two (vd_cull_mask_dev, then vd_occlusion_mask_dev).
+// With F = is_visible, V = F and not is_occluded, P = the caller's visible-last-frame bits:
+//   HIZ,  no PREV (hiz):    list = V
+//   PREV, no HIZ  (early):  list = F & P
+//   HIZ and PREV  (late):   list = V & ~P, and V itself goes to visible_out (which may be the buffer P came from: a wave
+//                           reads its tile's 16 words of P before it stores anything, and no other wave touches them)
+// The view-space centre and max_scale are computed once and feed both tests: the expressions, in the order is_visible()
+// and is_occluded() have them (-ffp-contract=off keeps them bit-identical).  Instances that fail the frustum test do not
+// fetch pyramid texels, and a round none of whose instances passes skips the occlusion test altogether.  The pyramid is
+// read through the ordinary cached path: only the instance stream is nontemporal.
+struct OccProj { float p00, p11, p20, p21, p22, p32; };
+struct ViewCentre { float c[3]; float max_scale; };
+
+__device__ __forceinline__ ViewCentre view_centre(const float* V, const MeshRec& m, const float4 T0, const float4 T1, const float4 T2,
+                                                  const float4 T3) {
+    const float c0x = (m.mxx + m.mnx) / 2.0f, c0y = (m.mxy + m.mny) / 2.0f, c0z = (m.mxz + m.mnz) / 2.0f;
+    ViewCentre vc;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float v0 = V[r], v1 = V[4 + r], v2 = V[8 + r], v3 = V[12 + r];
+        const float m0 = ((v0 * T0.x + v1 * T0.y) + v2 * T0.z) + v3 * T0.w;
+        const float m1 = ((v0 * T1.x + v1 * T1.y) + v2 * T1.z) + v3 * T1.w;
+        const float m2 = ((v0 * T2.x + v1 * T2.y) + v2 * T2.z) + v3 * T2.w;
+        const float m3 = ((v0 * T3.x + v1 * T3.y) + v2 * T3.z) + v3 * T3.w;
+        vc.c[r] = ((m0 * c0x + m1 * c0y) + m2 * c0z) + m3 * 1.0f;
+    }
+    const float sx = len3(T0.x, T0.y, T0.z), sy = len3(T1.x, T1.y, T1.z), sz = len3(T2.x, T2.y, T2.z);
+    vc.max_scale = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
+    return vc;
+}
+
+// is_visible() from its view-space centre on
+__device__ __forceinline__ bool frustum_visible(const CullCamera& cam, const MeshRec& m, const ViewCentre& vc) {
+    const float* c = vc.c;
+    const float d0 = len3(m.mnx - c[0], m.mny - c[1], m.mnz - c[2]);
+    const float d1 = len3(m.mxx - c[0], m.mxy - c[1], m.mxz - c[2]);
+    const float radius = fmaxf(d0, d1) * vc.max_scale;
+    if (c[2] * cam.frustum[1] - fabsf(c[0]) * cam.frustum[0] < -radius) return false;
+    if (c[2] * cam.frustum[3] - fabsf(c[1]) * cam.frustum[2] < -radius) return false;
+    if (c[2] + radius > cam.znear && c[2] - radius > cam.zfar) return false;
+    return true;
+}
+
+// is_occluded() from its view-space centre on
+__device__ __forceinline__ bool sphere_occluded(const OccProj& P, const float znear, const HizView& hz, const MeshRec& m, const ViewCentre& vc) {
+    const float* c = vc.c;
+    const float r = (len3(m.mxx - m.mnx, m.mxy - m.mny, m.mxz - m.mnz) * 0.5f) * vc.max_scale;
+    const float d = -c[2];
+    const float dn = d - r;
+    if (!(dn > znear)) return false;
+    const float rr = r * r, dd = d * d, rd = r * d;
+    const float tx = sqrtf((c[0] * c[0] + dd) - rr), ty = sqrtf((c[1] * c[1] + dd) - rr);
+    const float dxm = d * tx + c[0] * r, dxp = d * tx - c[0] * r, dym = d * ty + c[1] * r, dyp = d * ty - c[1] * r;
+    if (!(dxm > 0.0f && dxp > 0.0f && dym > 0.0f && dyp > 0.0f)) return false;
+    const float sx0 = (c[0] * tx - rd) / dxm, sx1 = (c[0] * tx + rd) / dxp;
+    const float sy0 = (c[1] * ty - rd) / dym, sy1 = (c[1] * ty + rd) / dyp;
+    const float nxa = P.p00 * sx0 - P.p20, nxb = P.p00 * sx1 - P.p20, nya = P.p11 * sy0 - P.p21, nyb = P.p11 * sy1 - P.p21;
+    const float nx_lo = fminf(nxa, nxb), nx_hi = fmaxf(nxa, nxb), ny_lo = fminf(nya, nyb), ny_hi = fmaxf(nya, nyb);
+    const float W = (float)hz.width, H = (float)hz.height;
+    const float u0 = (nx_lo * 0.5f + 0.5f) * W - 0.5f, u1 = (nx_hi * 0.5f + 0.5f) * W + 0.5f;
+    const float v0 = (0.5f - ny_hi * 0.5f) * H - 0.5f, v1 = (0.5f - ny_lo * 0.5f) * H + 0.5f;
+    if (!(u1 >= 0.0f && v1 >= 0.0f && u0 < W && v0 < H)) return false;
+    const unsigned x0 = (unsigned)floorf(fmaxf(u0, 0.0f)), x1 = (unsigned)floorf(fminf(u1, W - 1.0f));
+    const unsigned y0 = (unsigned)floorf(fmaxf(v0, 0.0f)), y1 = (unsigned)floorf(fminf(v1, H - 1.0f));
+    const unsigned span = max(x1 - x0, y1 - y0);
+    const unsigned lvl = min(span ? 32u - (unsigned)__clz((int)span) : 0u, hz.n_levels - 1u);
+    const float* t = hz.base + hz.off[lvl];
+    const unsigned lw = ((hz.width - 1u) >> lvl) + 1u;
+    const unsigned ax = x0 >> lvl, bx = x1 >> lvl, ay = y0 >> lvl, by = y1 >> lvl;
+    const float h0 = fminf(t[(size_t)ay * lw + ax], t[(size_t)ay * lw + bx]);
+    const float h1 = fminf(t[(size_t)by * lw + ax], t[(size_t)by * lw + bx]);
+    const float hmin = fminf(h0, h1);
+    const float depth = (P.p32 - P.p22 * dn) / dn;
+    return depth < hmin;
+}
+
+template <typename IdT, bool HIZ, bool PREV>
+__global__ __launch_bounds__(kBlock, 3) void cull_mask_occ_kernel(CullCamera cam, OccProj proj, HizView hz, const VdMeshInfo* __restrict__ meshes,
+                                                                   unsigned n_mesh, const VdInstance* __restrict__ inst, unsigned n_inst,
+                                                                   vd_u64* __restrict__ mask, const vd_u64* prev, vd_u64* visible_out,
+                                                                   IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
+                                                                   unsigned n_tiles) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr int kIdBytes = TileIds<IdT>::kBytes;
+    char* slab = smem + wave * (kSlabBytes + kIdBytes);
+    IdT* s_ids = reinterpret_cast<IdT*>(slab + kSlabBytes);
+    const unsigned waves_total = gridDim.x * kWavesPerBlock;
+    const size_t n_words = ((size_t)n_inst + 63) / 64;
+    auto valid_at = [&](size_t f) -> unsigned { return f < n_inst ? (unsigned)min((size_t)64, (size_t)n_inst - f) : 0u; };
+    u32x4 regs[kChunksPerLane];
+    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < n_tiles; t += waves_total) {
+        const size_t tile_first = (size_t)t * (kWave * kMaskRounds);
+        const size_t w0 = (size_t)t * kMaskRounds;
+        const bool my_slot = lane < (unsigned)kMaskRounds && w0 + lane < n_words;      // lane r holds the words of round r
+        slab_fill<true>(inst, tile_first, valid_at(tile_first), lane, regs);
+        // this tile's 16 words of P, before anything of the tile is written (visible_out may be the same buffer)
+        unsigned p_lo = 0u, p_hi = 0u;
+        if (PREV && my_slot) { const vd_u64 p = prev[w0 + lane]; p_lo = (unsigned)p; p_hi = (unsigned)(p >> 32); }
+        TileIds<IdT> tile_ids;                 // the id table's rows of this tile as they are now: only rows that differ are stored
+        tile_ids.load(ids_out, tile_first, n_inst, lane);
+        vd_u64 list_word = 0, vis_word = 0;
+#pragma unroll 1
+        for (int r = 0; r < kMaskRounds; ++r) {
+            const size_t first = tile_first + (size_t)r * kWave;
+            const unsigned n_valid = valid_at(first);
+            slab_store(slab, lane, regs);
+            if (r + 1 < kMaskRounds) slab_fill<true>(inst, first + kWave, valid_at(first + kWave), lane, regs);
+            vd_wave_lds_sync();
+            const LaneInst li = slab_read(slab, lane);
+            vd_wave_lds_sync();
+            const unsigned mid = min(li.mesh, n_mesh - 1u);
+            const MeshRec m = load_mesh(meshes, mid);
+            const ViewCentre vc = view_centre(cam.view, m, li.T0, li.T1, li.T2, li.T3);
+            bool keep = lane < n_valid && frustum_visible(cam, m, vc);
+            if (HIZ) {
+                if (__ballot(keep) != 0ull) {                              // wave-uniform: a round wholly outside the frustum fetches no texel
+                    if (keep) keep = !sphere_occluded(proj, cam.znear, hz, m, vc);
+                }
+            }
+            vd_u64 b = __ballot(keep);
+            if (PREV) {
+                const vd_u64 p = (vd_u64)(unsigned)__builtin_amdgcn_readlane((int)p_lo, r) |
+                                 ((vd_u64)(unsigned)__builtin_amdgcn_readlane((int)p_hi, r) << 32);
+                if (HIZ) { if (lane == (unsigned)r) vis_word = b; b &= ~p; }
+                else b &= p;
+            }
+            if (lane == (unsigned)r) list_word = b;
+            s_ids[r * kWave + lane] = (IdT)mid;
+        }
+        vd_wave_lds_sync();
+        // flush: the list's ballot words (and V's), the tile's survivor count, the id rows that changed
+        if (my_slot) {
+            mask[w0 + lane] = list_word;
+            if (HIZ && PREV) visible_out[w0 + lane] = vis_word;
+        }
+        unsigned survivors = (unsigned)__popcll(list_word);               // 0 in lanes >= kMaskRounds
+#pragma unroll
+        for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
+        if (lane == 0u) tile_count[t] = survivors;
+        tile_ids.flush(ids_out, s_ids, tile_first, n_inst, lane);
+        vd_wave_lds_sync();
+    }
+}
+
 constexpr int kExpandGroup = 4;                      // mask words staged and stored as one contiguous run
 constexpr int kExpandWords = 32;                     // mask words (64 instances each) per wave
 constexpr int kChunkWords = kWavesPerBlock * kExpandWords;   // per workgroup: 128 words = 8192 instances
@@ -1644,6 +1792,113 @@ int vd_cull_compact_views_dev(VdCtx* ctx, const VdCameraUniform* cameras, uint32
     return VD_OK;
 }
 
+// Occlusion-culled draw lists: ONE pass over the instances (cull_mask_occ_kernel: frustum test, occlusion test against the
+// pyramid and / or the visible-last-frame bits) writes the list's mask, its tile counts and the id table; then the
+// unchanged expansion, placed from the tile counts.  Always the two-launch form (three with pad_tail), whatever the size:
+// no scan kernel, no wait between workgroups.  Own arena (ctx->occ_scratch), laid out [id table | mask | tile counts]: the
+// three entry points share the id table, so after vd_cull_early_dev the late call finds every row equal and stores none,
+// and vd_cull_compact* / vd_cull_compact_views* calls in between (ctx->scratch, ctx->views_scratch) leave it alone.
+enum OccMode { kOccHiz = 0, kOccEarly = 1, kOccLate = 2 };
+static int cull_occ_list(VdCtx* ctx, OccMode mode, const char* name, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                         const VdInstance* d_instances, uint32_t n_inst, const float* d_pyramid, uint32_t width, uint32_t height,
+                         const uint64_t* d_prev, uint64_t* d_visible_out, VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail) {
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    const bool hiz = mode != kOccEarly, prev = mode != kOccHiz;
+    char msg[256];
+#define VD_OCC_FAIL(text) do { snprintf(msg, sizeof(msg), "%s: %s", name, text); VD_FAIL(ctx, VD_ERR_INVALID_ARG, msg); } while (0)
+    if (!camera || !d_meshes || n_mesh == 0 || !d_out_count) VD_OCC_FAIL("null camera/meshes/count or n_mesh == 0");
+    VdHizLayout L = {};
+    if (hiz) {
+        if (!d_pyramid) VD_OCC_FAIL("null pyramid");
+        if (vd_hiz_layout(width, height, &L)) VD_OCC_FAIL("bad pyramid size");
+        if (!(camera->projection[11] == -1.0f && camera->projection[15] == 0.0f))
+            VD_OCC_FAIL("projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)");
+    }
+    if (n_inst == 0) {
+        VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_count, 0, 4, ctx->stream));
+        return VD_OK;
+    }
+    if (!d_instances || !d_out) VD_OCC_FAIL("null instances/out");
+    if (prev && !d_prev) VD_OCC_FAIL("null visibility mask");
+    if (mode == kOccLate && !d_visible_out) VD_OCC_FAIL("null visibility mask (out)");
+#undef VD_OCC_FAIL
+    const unsigned n_words = (n_inst + 63u) / 64u;
+    const unsigned id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
+    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
+    const size_t mask_off = ((size_t)n_inst * id_bytes + 255) & ~(size_t)255;        // (the expansion reads ids as aligned dwords)
+    const size_t counts_off = mask_off + (((size_t)n_words * 8 + 255) & ~(size_t)255);
+    const size_t need = counts_off + (((size_t)n_mt + 3) & ~(size_t)3) * 4 + 512;    // whole 16-byte groups of counts (tile_prefix_partial)
+    int rc = vd_ensure(ctx, &ctx->occ_scratch, &ctx->occ_scratch_bytes, need);
+    if (rc) return rc;
+    char* base = reinterpret_cast<char*>(ctx->occ_scratch);
+    void* d_ids = base;
+    vd_u64* d_mask = reinterpret_cast<vd_u64*>(base + mask_off);
+    unsigned* d_counts = reinterpret_cast<unsigned*>(base + counts_off);
+    OccProj proj = {};
+    HizView hz = {};
+    if (hiz) {
+        const float* P = camera->projection;
+        proj.p00 = P[0]; proj.p11 = P[5]; proj.p20 = P[8]; proj.p21 = P[9]; proj.p22 = P[10]; proj.p32 = P[14];
+        hz.base = d_pyramid; hz.width = width; hz.height = height; hz.n_levels = L.n_levels;
+        for (int k = 0; k < 17; ++k) hz.off[k] = L.level_offset[k];
+    }
+    vd_time_begin(ctx);
+    unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
+#define VD_OCC(IdT, H, P)                                                                                          \
+    hipLaunchKernelGGL((cull_mask_occ_kernel<IdT, H, P>), dim3(mb), dim3(kBlock),                                  \
+                       kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
+                       ctx->stream, make_cam(camera), proj, hz, d_meshes, n_mesh, d_instances, n_inst, d_mask,     \
+                       reinterpret_cast<const vd_u64*>(d_prev), reinterpret_cast<vd_u64*>(d_visible_out),          \
+                       reinterpret_cast<IdT*>(d_ids), d_counts, n_mt)
+#define VD_OCC_MODE(IdT)                                                                                           \
+    do {                                                                                                           \
+        if (mode == kOccHiz) VD_OCC(IdT, true, false);                                                             \
+        else if (mode == kOccEarly) VD_OCC(IdT, false, true);                                                      \
+        else VD_OCC(IdT, true, true);                                                                              \
+    } while (0)
+    if (id_bytes == 1u) VD_OCC_MODE(unsigned char);
+    else if (id_bytes == 2u) VD_OCC_MODE(unsigned short);
+    else VD_OCC_MODE(unsigned);
+#undef VD_OCC_MODE
+#undef VD_OCC
+    vd_time_mid(ctx);
+    rc = launch_expand(ctx, d_mask, n_words, n_words, n_inst, n_inst, 0u, d_ids, id_bytes, d_meshes, n_mesh, d_out, d_out_count, d_counts);
+    if (rc) return rc;
+    vd_time_end(ctx);
+    if (pad_tail) {
+        const unsigned pblocks = (unsigned)ctx->num_cus * 4u;
+        hipLaunchKernelGGL(pad_tail_kernel, dim3(pblocks), dim3(kBlock), 0, ctx->stream, d_out, d_out_count, n_inst);
+    }
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
+}
+
+int vd_cull_compact_hiz_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                            const VdInstance* d_instances, uint32_t n_inst, const float* d_pyramid, uint32_t width, uint32_t height,
+                            VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    return cull_occ_list(ctx, kOccHiz, "vd_cull_compact_hiz", camera, d_meshes, n_mesh, d_instances, n_inst, d_pyramid, width, height,
+                         nullptr, nullptr, d_out, d_out_count, pad_tail);
+}
+
+int vd_cull_early_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                      const VdInstance* d_instances, uint32_t n_inst, const uint64_t* d_prev_visible,
+                      VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    return cull_occ_list(ctx, kOccEarly, "vd_cull_early", camera, d_meshes, n_mesh, d_instances, n_inst, nullptr, 0u, 0u,
+                         d_prev_visible, nullptr, d_out, d_out_count, pad_tail);
+}
+
+int vd_cull_late_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                     const VdInstance* d_instances, uint32_t n_inst, const float* d_pyramid, uint32_t width, uint32_t height,
+                     const uint64_t* d_prev_visible, uint64_t* d_visible_out, VdDrawIndexedIndirect* d_out, uint32_t* d_out_count,
+                     int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    return cull_occ_list(ctx, kOccLate, "vd_cull_late", camera, d_meshes, n_mesh, d_instances, n_inst, d_pyramid, width, height,
+                         d_prev_visible, d_visible_out, d_out, d_out_count, pad_tail);
+}
+
 int vd_cull_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
                      const VdInstance* d_instances, uint32_t n_inst, uint64_t* d_mask) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
@@ -1915,6 +2170,52 @@ int vd_cull_compact_views(VdCtx* ctx, const VdCameraUniform* cameras, uint32_t n
                                              hipMemcpyDeviceToHost, ctx->stream));
     }
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VD_OK;
+}
+
+int vd_cull_compact_hiz(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* meshes, uint32_t n_mesh,
+                        const VdInstance* instances, uint32_t n_inst, const float* pyramid, uint32_t width, uint32_t height,
+                        VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (!camera || !meshes || n_mesh == 0 || !out_count || !pyramid)
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: null camera/meshes/count/pyramid or n_mesh == 0");
+    VdHizLayout L;
+    if (vd_hiz_layout(width, height, &L)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: bad pyramid size");
+    if (!(camera->projection[11] == -1.0f && camera->projection[15] == 0.0f))
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)");
+    if (n_inst > 0 && (!instances || !out)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: null instances/out");
+    *out_count = 0;                                                  // (a refused call writes nothing)
+    if (n_inst == 0) return VD_OK;
+    // staged like vd_cull_compact: instances; a 16-byte header that takes the count, the meshes and the pyramid; n_inst commands
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t pyr_off = (16 + (size_t)n_mesh * sizeof(VdMeshInfo) + 255) & ~(size_t)255;
+    const size_t pyr_bytes = (size_t)L.total_texels * sizeof(float);
+    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
+    if (rc) return rc;
+    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, pyr_off + pyr_bytes);
+    if (rc) return rc;
+    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16);
+    if (rc) return rc;
+    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
+    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + 16);
+    float* dp = reinterpret_cast<float*>(reinterpret_cast<char*>(ctx->stage_aux) + pyr_off);
+    VdDrawIndexedIndirect* dout = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(ctx->stage_aux);
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(dp, pyramid, pyr_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = vd_cull_compact_hiz_dev(ctx, camera, dm, n_mesh, di, n_inst, dp, width, height, dout, d_count, pad_tail);
+    if (rc) return rc;
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->host_pinned[0] > n_inst) VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_hiz: the expansion wrote no count");
+    *out_count = ctx->host_pinned[0];
+    const size_t n_copy = pad_tail ? n_inst : *out_count;
+    if (n_copy) {
+        VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n_copy * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
+        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return VD_OK;
 }
 

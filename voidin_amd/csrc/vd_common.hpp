@@ -31,6 +31,7 @@ struct VdCtx {
     // grow-only device scratch arenas
     void* scratch = nullptr;     size_t scratch_bytes = 0;     // general purpose
     void* views_scratch = nullptr; size_t views_scratch_bytes = 0;   // vd_cull_compact_views*: id table, K masks, K tile-count tables
+    void* occ_scratch = nullptr; size_t occ_scratch_bytes = 0;       // vd_cull_compact_hiz* / vd_cull_early_dev / vd_cull_late_dev: id table, mask, tile counts
     void* scan_state = nullptr;  size_t scan_state_bytes = 0;  // look-back granules + ticket word (epoch-tagged)
     void* expand_state = nullptr; size_t expand_state_bytes = 0;  // mask_scan_kernel: done counter + chunk offsets
     void* trace_ovf = nullptr;   size_t trace_ovf_bytes = 0;      // traversal: one bit per ray of the call = "its 128-entry stack overflowed"

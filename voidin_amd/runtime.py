@@ -395,6 +395,46 @@ class Context:
         self._chk(self.lib.vd_occlusion_mask_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n,
                                                  abi.ptr(d_pyramid), width, height, abi.ptr(d_mask_in), abi.ptr(d_mask_out)))
 
+    # occlusion-culled draw lists: one read of the instances (frustum + pyramid and / or last frame's visibility bits)
+    def cull_compact_hiz_dev(self, camera, d_meshes, n_mesh, d_inst, n_inst, d_pyramid, width, height, d_out, d_count,
+                             pad_tail: bool = False):
+        """vd_cull_compact_hiz_dev: the ordered list of the instances that pass the frustum test and are not occluded."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_cull_compact_hiz_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst,
+                                                   abi.ptr(d_pyramid), width, height, abi.ptr(d_out), abi.ptr(d_count), int(pad_tail)))
+
+    def cull_early_dev(self, camera, d_meshes, n_mesh, d_inst, n_inst, d_prev_visible, d_out, d_count, pad_tail: bool = False):
+        """vd_cull_early_dev: in the frustum AND visible last frame (d_prev_visible: one bit per instance, u64 words)."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_cull_early_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst,
+                                             abi.ptr(d_prev_visible), abi.ptr(d_out), abi.ptr(d_count), int(pad_tail)))
+
+    def cull_late_dev(self, camera, d_meshes, n_mesh, d_inst, n_inst, d_pyramid, width, height, d_prev_visible, d_visible_out,
+                      d_out, d_count, pad_tail: bool = False):
+        """vd_cull_late_dev: unoccluded now and NOT visible last frame; d_visible_out (may be d_prev_visible) = the
+        unoccluded set, next frame's d_prev_visible."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_cull_late_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst,
+                                            abi.ptr(d_pyramid), width, height, abi.ptr(d_prev_visible), abi.ptr(d_visible_out),
+                                            abi.ptr(d_out), abi.ptr(d_count), int(pad_tail)))
+
+    def cull_compact_hiz(self, camera, meshes, instances, pyramid, width, height, pad_tail=False):
+        """Host arrays in (the pyramid as vd_hiz_layout lays it out), (list, count) out; only [0, count) is defined
+        (everything with pad_tail)."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        meshes = np.ascontiguousarray(meshes, dtype=abi.MESH_INFO)
+        instances = np.ascontiguousarray(instances, dtype=abi.INSTANCE)
+        pyramid = np.ascontiguousarray(pyramid, dtype=np.float32).reshape(-1)
+        if len(pyramid) != self.hiz_layout(width, height).total_texels:
+            raise ValueError("pyramid does not hold vd_hiz_layout(width, height).total_texels floats")
+        out = np.zeros(len(instances), dtype=abi.DRAW)
+        out.view(np.uint8)[:] = 0xAB
+        cnt = C.c_uint32(0)
+        self._chk(self.lib.vd_cull_compact_hiz(self.h, cam.ctypes.data, meshes.ctypes.data, len(meshes), instances.ctypes.data,
+                                               len(instances), pyramid.ctypes.data, width, height, out.ctypes.data,
+                                               C.addressof(cnt), int(pad_tail)))
+        return out, cnt.value
+
 
 # ------------------------------------------------------------------------------------------
 # Reference-shaped façade
@@ -420,6 +460,39 @@ class EmitDraws:
         command v * out_stride of draw_cmd_buffer (default: n_inst), its count is word v of draw_count_buf."""
         self.ctx.cull_compact_views_dev(cameras, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer,
                                         draw_count_buf, pad_tail, out_stride)
+
+    def record_hiz(self, camera, mesh_info_buf, n_mesh, instances_buf, n_inst, pyramid_buf, width, height, draw_cmd_buffer,
+                   draw_count_buf, pad_tail=False):
+        """record_compacted with the occlusion test against a depth pyramid folded into the same read of the instances."""
+        self.ctx.cull_compact_hiz_dev(camera, mesh_info_buf, n_mesh, instances_buf, n_inst, pyramid_buf, width, height,
+                                      draw_cmd_buffer, draw_count_buf, pad_tail)
+
+    def record_early(self, camera, mesh_info_buf, n_mesh, instances_buf, n_inst, state: "OcclusionState", draw_cmd_buffer,
+                     draw_count_buf, pad_tail=False):
+        """Two-pass occlusion culling, first half: what was visible last frame and is still in the frustum."""
+        self.ctx.cull_early_dev(camera, mesh_info_buf, n_mesh, instances_buf, n_inst, state.visible, draw_cmd_buffer,
+                                draw_count_buf, pad_tail)
+
+    def record_late(self, camera, mesh_info_buf, n_mesh, instances_buf, n_inst, pyramid_buf, width, height,
+                    state: "OcclusionState", draw_cmd_buffer, draw_count_buf, pad_tail=False):
+        """Second half, against the pyramid of the depth the early list produced: what it reveals; the state's bits become
+        this frame's unoccluded set (in place)."""
+        self.ctx.cull_late_dev(camera, mesh_info_buf, n_mesh, instances_buf, n_inst, pyramid_buf, width, height,
+                               state.visible, state.visible, draw_cmd_buffer, draw_count_buf, pad_tail)
+
+
+class OcclusionState:
+    """The visibility bits the two-pass scheme carries from frame to frame: one bit per instance in 64-bit words, zeroed
+    (nothing was visible before the first frame, so that frame's early list is empty and its late list is everything
+    unoccluded)."""
+
+    def __init__(self, ctx: Context, n_inst: int):
+        import torch
+        self.n_inst = int(n_inst)
+        self.visible = torch.zeros(max((self.n_inst + 63) // 64, 1), dtype=torch.int64, device=ctx.torch_device)
+
+    def reset(self):
+        self.visible.zero_()
 
 
 class Bvh:
