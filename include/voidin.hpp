@@ -448,6 +448,12 @@ struct EmitDrawsViewsResource {                       // EmitDrawsResource for s
     bool pad_tail = false;
 };
 
+struct EmitDrawsBatchedResource {                     // the instanced form (no reference counterpart): one command per mesh
+    DrawIndexedIndirect* draw_cmd_buffer;             // device buffer of n_meshes commands; instance_count = visible instances of the mesh
+    uint32_t* visible_ids;                            // device buffer of n_instances u32: the survivors' ids grouped by mesh, [0, *draw_count)
+    uint32_t* draw_count;                             // device u32: the number of survivors
+};
+
 class EmitDraws {
    public:
     explicit EmitDraws(Gpu& gpu) : gpu_(gpu) {}       // EmitDraws::new(&World) -> Result<Self> (visibility.rs:200-222)
@@ -471,6 +477,15 @@ class EmitDraws {
         gpu_.check(vd_cull_compact_views_dev(gpu_.ctx(), cameras, n_views, world.d_mesh_info, world.n_meshes, world.d_instances,
                                              world.n_instances, resources.draw_cmd_buffer, resources.view_stride,
                                              resources.draw_counts, resources.pad_tail ? 1 : 0));
+    }
+
+    // EXTENSION (voidin_abi.h "Instanced draw lists"): one command per mesh and the survivors' ids grouped by mesh, in one read
+    // of the instances.  The consumer is multi_draw_indexed_indirect(draw_cmd_buffer, 0, n_meshes) with
+    // shaders/visibility.wgsl:33 reading instances[visible_ids[in.instance_index]].  At most VD_BATCH_MAX_MESHES meshes.
+    void record_batched(const World& world, ProfilerCommandEncoder& encoder, EmitDrawsBatchedResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_batch_dev(gpu_.ctx(), world.camera, world.d_mesh_info, world.n_meshes, world.d_instances,
+                                     world.n_instances, resources.draw_cmd_buffer, resources.visible_ids, resources.draw_count));
     }
 
     // EXTENSION (occlusion culling; voidin_abi.h "Occlusion culling"): record() with draw_count set, with the occlusion test

@@ -429,6 +429,60 @@ int vd_indices_to_draws_dev(VdCtx* ctx, const uint32_t* d_indices, uint32_t n_in
 int vd_compact_draws_dev(VdCtx* ctx, const VdDrawIndexedIndirect* d_in, uint32_t n,
                          VdDrawIndexedIndirect* d_out, uint32_t* d_out_count);
 
+/* Instanced draw lists (NEW; no reference counterpart - the reference submits one single-instance command per instance):
+ * ONE command per MESH with instance_count = the visible instances of that mesh, and a 4-byte instance id per survivor,
+ * grouped by mesh, that the vertex shader indexes with instance_index (shaders/visibility.wgsl:33 becomes
+ * `instances[visible_ids[in.instance_index]]`: INTEGRATION.md).  n_mesh commands + 4 B per survivor instead of 20 B per
+ * survivor, and n_mesh draws for the consumer instead of one per survivor.  A pure function of the existing list:
+ *   S      = the ascending list of instances i with emit_draws(i).instance_count == 1
+ *            (vd_batch_mask_dev: the set bits of d_mask, bit i % 64 of word i / 64 = instance i);
+ *   mid(i) = min(mesh id of i, n_mesh - 1) - the clamp emit_draws, the oracle and the id table already apply;
+ *   S_m    = the sub-list of S with mid == m, still ascending.
+ *   d_out_instance_ids[0 .. |S|)  = S_0 || S_1 || ... || S_{n_mesh-1}: a STABLE sort of S by mesh.  Words [|S|, n_inst)
+ *                                   are NOT written.
+ *   d_out_cmds[m]                 = { meshes[m].index_count, |S_m|, meshes[m].base_index, meshes[m].vertex_offset,
+ *                                   sum of |S_k| over k < m } for EVERY m < n_mesh: empty meshes are included with
+ *                                   instance_count = 0, so multi_draw_indexed_indirect(buf, 0, n_mesh) is valid as it
+ *                                   stands.  Exactly n_mesh commands are written.
+ *   *d_out_count                  = |S|.
+ * n_inst == 0: the n_mesh commands are written with instance_count = 0 and base_instance = 0, the count is 0.
+ * VD_ERR_INVALID_ARG: null ctx / camera / meshes / cmds / count; n_mesh == 0 or n_mesh > VD_BATCH_MAX_MESHES (the limit
+ * of the one-digit counting sort: a wave-private table of n_mesh counters lives in LDS; a second digit is future work);
+ * id_bytes not 1, 2 or 4; null instances / mask / ids / instance-ids with n_inst > 0.  A refused call writes nothing.
+ * The padding bits of the last mask word are zero on input, as vd_cull_mask_dev writes them.
+ *   vd_batch_mask_dev  groups ANY visibility mask (vd_cull_mask_dev, vd_occlusion_mask_dev, ...) with a caller-supplied
+ *                      mesh-id table (n_inst ids of id_bytes = 1, 2 or 4 bytes; clamped to n_mesh - 1 as above).
+ *   vd_cull_batch_dev  cull + group in ONE read of the instances: pass 1 of the two-launch step (cull to bitmask, mesh-id
+ *                      table, unchanged), then the grouping below.  Always this split form, at every size.
+ *   vd_cull_batch      host pointers, staged through the context and synchronous, like vd_cull_compact; out_instance_ids
+ *                      holds n_inst words of which [0, *out_count) are written.
+ * The grouping is a stable counting sort in four launches: every wave owns one contiguous range of instances and counts
+ * its survivors per mesh in LDS (one row of a [wave][mesh] table); a scan down the rows of every column; a scan over the
+ * mesh totals by ONE workgroup, which also writes the n_mesh commands and the count; every wave walks its range again and
+ * stores each id at cursor[mesh] + its rank among the same-mesh survivors of its 64-instance round (ballots, no atomics).
+ * No wait of one workgroup on another, hence no "gave up" state and no use of the scan-fault word; no global atomic, so
+ * the bytes are identical from run to run.  Once its scratch exists (first call, or more meshes) a call only enqueues
+ * kernels on the context's stream, so it can be captured into a HIP graph; the camera is baked in by value.
+ * vd_last_gpu_ms_stage (vd_cull_batch_dev): 0 = pass 1, 1 = everything after it.
+ * OUT OF SCOPE: more than VD_BATCH_MAX_MESHES meshes (needs a second sort digit); a multi-view form and a shard /
+ * vd_dist_* form; dropping empty meshes from the command array; pad_tail (nothing behind |S| is ever written).
+ * Measured times against vd_cull_compact_dev: DESIGN.md §3.1, profiles/cull_batch.md.                                  */
+#define VD_BATCH_MAX_MESHES 4096u
+int vd_batch_mask_dev(VdCtx* ctx, const uint64_t* d_mask, uint32_t n_inst,
+                      const void* d_mesh_ids, uint32_t id_bytes /* 1, 2, 4 */,
+                      const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                      VdDrawIndexedIndirect* d_out_cmds /* n_mesh */,
+                      uint32_t* d_out_instance_ids /* n_inst */,
+                      uint32_t* d_out_count);
+int vd_cull_batch_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */,
+                      const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                      const VdInstance* d_instances, uint32_t n_inst,
+                      VdDrawIndexedIndirect* d_out_cmds, uint32_t* d_out_instance_ids, uint32_t* d_out_count);
+int vd_cull_batch(VdCtx* ctx, const VdCameraUniform* camera,
+                  const VdMeshInfo* meshes, uint32_t n_mesh,
+                  const VdInstance* instances, uint32_t n_inst,
+                  VdDrawIndexedIndirect* out_cmds, uint32_t* out_instance_ids, uint32_t* out_count);
+
 /* ------------------------------------------------------------------------------------ */
 /* BLAS build                                                       */
 /* ------------------------------------------------------------------------------------ */

@@ -47,6 +47,7 @@ MAX_DIST = np.float32(1e30)
 CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run their split form from this many instances
 TLAS_MAX_INSTANCES = 32768
 MAX_VIEWS = 8             # VD_MAX_VIEWS: cameras per vd_cull_compact_views* call
+BATCH_MAX_MESHES = 4096   # VD_BATCH_MAX_MESHES: meshes per vd_cull_batch* / vd_batch_mask_dev call (one-digit counting sort)
 
 VD_OK = 0
 VD_ERR_INVALID_ARG = -1
@@ -146,6 +147,9 @@ PROTOTYPES = {
     "vd_mask_to_indices_dev": (_I, [_P, _P, _U, _U, _P, _P]),
     "vd_indices_to_draws_dev": (_I, [_P, _P, _U, _P, _U, _U, _P, _U, _P]),
     "vd_compact_draws_dev": (_I, [_P, _P, _U, _P, _P]),
+    "vd_batch_mask_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P, _P, _P]),
+    "vd_cull_batch_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _P, _P]),
+    "vd_cull_batch": (_I, [_P, _P, _P, _U, _P, _U, _P, _P, _P]),
     "vd_bvh_build": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
     "vd_bvh_build_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
     "vd_bvh_build_batch": (_I, [_P, _P, _U, _P, C.c_uint64, _U, _P]),

@@ -111,6 +111,7 @@ int vd_ctx_destroy(VdCtx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->views_scratch) (void)hipFree(ctx->views_scratch);
     if (ctx->occ_scratch) (void)hipFree(ctx->occ_scratch);
+    if (ctx->batch_scratch) (void)hipFree(ctx->batch_scratch);
     if (ctx->scan_state) (void)hipFree(ctx->scan_state);
     if (ctx->expand_state) (void)hipFree(ctx->expand_state);
     if (ctx->trace_ovf) (void)hipFree(ctx->trace_ovf);

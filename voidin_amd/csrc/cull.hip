@@ -1577,8 +1577,9 @@ int vd_cull_emit_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
 }
 
 // Pass 1 of the split forms: instances -> one bit + a compact mesh id each, and the survivors of every 1024-instance
-// tile (*out_tile_count, padded to whole 16-byte groups; the emit path ignores it), in ctx scratch.
-static int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+// tile (*out_tile_count, padded to whole 16-byte groups; the emit path ignores it), in ctx scratch.  Declared in
+// vd_common.hpp (hidden visibility): batch.hip runs the same pass.
+int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
                             const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids, unsigned* out_id_bytes,
                             unsigned** out_tile_count) {
     const unsigned n_words = (n_inst + 63u) / 64u;

@@ -32,6 +32,7 @@ struct VdCtx {
     void* scratch = nullptr;     size_t scratch_bytes = 0;     // general purpose
     void* views_scratch = nullptr; size_t views_scratch_bytes = 0;   // vd_cull_compact_views*: id table, K masks, K tile-count tables
     void* occ_scratch = nullptr; size_t occ_scratch_bytes = 0;       // vd_cull_compact_hiz* / vd_cull_early_dev / vd_cull_late_dev: id table, mask, tile counts
+    void* batch_scratch = nullptr; size_t batch_scratch_bytes = 0;   // vd_cull_batch* / vd_batch_mask_dev: mesh totals, mesh bases, the [wave][mesh] count table
     void* scan_state = nullptr;  size_t scan_state_bytes = 0;  // look-back granules + ticket word (epoch-tagged)
     void* expand_state = nullptr; size_t expand_state_bytes = 0;  // mask_scan_kernel: done counter + chunk offsets
     void* trace_ovf = nullptr;   size_t trace_ovf_bytes = 0;      // traversal: one bit per ray of the call = "its 128-entry stack overflowed"
@@ -104,6 +105,12 @@ int vd_scan_scratch(VdCtx* ctx, unsigned n_tiles, unsigned long long** ticket, u
 // that launches a look-back scan, so a renderer that only uses the *_dev forms hears about it on its next frame.
 int vd_scan_check_fault(VdCtx* ctx);
 static inline unsigned* vd_scan_fault_word(VdCtx* ctx) { return ctx->fault_dev; }
+// cull.hip: pass 1 of the split forms (cull_mask_tiled_kernel) into ctx->scratch - the visibility bitmask, the clamped
+// mesh-id table (*out_id_bytes = 1, 2 or 4 by n_mesh) and the survivors per 1024-instance tile.  Starts the call's timer
+// and records its stage boundary.  batch.hip groups by mesh from the same pass.  Not part of the C ABI.
+extern "C" __attribute__((visibility("hidden"))) int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                                                                      const VdInstance* d_instances, uint32_t n_inst, unsigned long long** out_mask, void** out_ids,
+                                                                      unsigned* out_id_bytes, unsigned** out_tile_count);
 
 static inline void vd_time_begin(VdCtx* ctx) {
     ctx->timed_mid = false;

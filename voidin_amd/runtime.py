@@ -145,6 +145,20 @@ class Context:
         self._chk(self.lib.vd_indices_to_draws_dev(self.h, abi.ptr(d_indices), n_indices, abi.ptr(d_mesh_ids), id_bytes, n_total,
                                                    abi.ptr(d_meshes), n_mesh, abi.ptr(d_out)))
 
+    # instanced draw lists: one command per mesh + the survivors' ids grouped by mesh (voidin_abi.h "Instanced draw lists")
+    def batch_mask_dev(self, d_mask, n_inst, d_mesh_ids, d_meshes, n_mesh, d_out_cmds, d_out_instance_ids, d_count, id_bytes=None):
+        """vd_batch_mask_dev: group the set bits of any visibility mask by mesh through a caller-supplied id table."""
+        if id_bytes is None:
+            id_bytes = d_mesh_ids.element_size() if hasattr(d_mesh_ids, "element_size") else 4
+        self._chk(self.lib.vd_batch_mask_dev(self.h, abi.ptr(d_mask), n_inst, abi.ptr(d_mesh_ids), id_bytes, abi.ptr(d_meshes), n_mesh,
+                                             abi.ptr(d_out_cmds), abi.ptr(d_out_instance_ids), abi.ptr(d_count)))
+
+    def cull_batch_dev(self, camera: np.ndarray, d_meshes, n_mesh, d_inst, n_inst, d_out_cmds, d_out_instance_ids, d_count):
+        """vd_cull_batch_dev: cull + group in one read of the instances; n_mesh commands, |S| ids, the count."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
+        self._chk(self.lib.vd_cull_batch_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst,
+                                             abi.ptr(d_out_cmds), abi.ptr(d_out_instance_ids), abi.ptr(d_count)))
+
     def compact_draws_dev(self, d_in, n, d_out, d_count):
         self._chk(self.lib.vd_compact_draws_dev(self.h, abi.ptr(d_in), n, abi.ptr(d_out), abi.ptr(d_count)))
 
@@ -184,6 +198,18 @@ class Context:
                                            instances.ctypes.data, len(instances), out.ctypes.data,
                                            C.addressof(cnt), int(pad_tail)))
         return out, cnt.value
+
+    def cull_batch(self, camera, meshes, instances):
+        """Host arrays in; (cmds [n_mesh], ids[:count], count) out: one command per mesh, the survivors' ids grouped by mesh."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
+        meshes = np.ascontiguousarray(meshes, dtype=abi.MESH_INFO)
+        instances = np.ascontiguousarray(instances, dtype=abi.INSTANCE)
+        cmds = np.zeros(len(meshes), dtype=abi.DRAW)
+        ids = np.full(max(len(instances), 1), 0xABABABAB, dtype=np.uint32)      # poison: only [0, count) is defined
+        cnt = C.c_uint32(0)
+        self._chk(self.lib.vd_cull_batch(self.h, cam.ctypes.data, meshes.ctypes.data, len(meshes), instances.ctypes.data,
+                                         len(instances), cmds.ctypes.data, ids.ctypes.data, C.addressof(cnt)))
+        return cmds, ids[:cnt.value], cnt.value
 
     def cull_compact_views(self, cameras, meshes, instances, pad_tail=False):
         """Host arrays in, (lists [n_views, n_inst], counts [n_views]) out; only [0, count) of a list is defined
@@ -460,6 +486,12 @@ class EmitDraws:
         command v * out_stride of draw_cmd_buffer (default: n_inst), its count is word v of draw_count_buf."""
         self.ctx.cull_compact_views_dev(cameras, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer,
                                         draw_count_buf, pad_tail, out_stride)
+
+    def record_batched(self, camera, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer, visible_ids_buf, draw_count_buf):
+        """The instanced form: draw_cmd_buffer[0..n_mesh) = one command per mesh (instance_count = its visible instances),
+        visible_ids_buf[0..count) = the survivors' instance ids grouped by mesh, which the vertex shader indexes with
+        instance_index; the consumer is multi_draw_indexed_indirect(draw_cmd_buffer, 0, n_mesh)."""
+        self.ctx.cull_batch_dev(camera, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer, visible_ids_buf, draw_count_buf)
 
     def record_hiz(self, camera, mesh_info_buf, n_mesh, instances_buf, n_inst, pyramid_buf, width, height, draw_cmd_buffer,
                    draw_count_buf, pad_tail=False):
