@@ -245,22 +245,18 @@ int launch_batch(VdCtx* ctx, const vd_u64* d_mask, unsigned n_inst, const void* 
     while ((1u << id_bits) < n_mesh) ++id_bits;
     unsigned cols = 16u;
     while (cols < 64u && cols < n_mesh) cols *= 2u;
-#define VD_BATCH(IdT)                                                                                                                  \
-    do {                                                                                                                               \
-        hipLaunchKernelGGL(batch_hist_kernel<IdT>, dim3(blocks), dim3(kBlock), lds, ctx->stream, d_mask, reinterpret_cast<const IdT*>(d_ids), \
-                           n_inst, n_words, n_mesh, p.words_per_row, p.rows, hist);                                                    \
-        hipLaunchKernelGGL(batch_scan_kernel, dim3((n_mesh + cols - 1u) / cols), dim3(kScanBlock), 0, ctx->stream, hist, p.rows, n_mesh, \
-                           cols, totals);                                                                                              \
-        hipLaunchKernelGGL(batch_cmds_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, totals, d_meshes, n_mesh, mesh_base, d_cmds,   \
-                           d_count);                                                                                                   \
-        hipLaunchKernelGGL(batch_scatter_kernel<IdT>, dim3(blocks), dim3(kBlock), lds, ctx->stream, d_mask,                             \
-                           reinterpret_cast<const IdT*>(d_ids), n_inst, n_words, n_mesh, id_bits, p.words_per_row, p.rows, hist,        \
-                           mesh_base, d_out_ids);                                                                                      \
-    } while (0)
-    if (id_bytes == 1u) VD_BATCH(unsigned char);
-    else if (id_bytes == 2u) VD_BATCH(unsigned short);
-    else VD_BATCH(unsigned);
-#undef VD_BATCH
+    vd_dispatch_id(id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        hipLaunchKernelGGL(batch_hist_kernel<IdT>, dim3(blocks), dim3(kBlock), lds, ctx->stream, d_mask, reinterpret_cast<const IdT*>(d_ids),
+                           n_inst, n_words, n_mesh, p.words_per_row, p.rows, hist);
+        hipLaunchKernelGGL(batch_scan_kernel, dim3((n_mesh + cols - 1u) / cols), dim3(kScanBlock), 0, ctx->stream, hist, p.rows, n_mesh,
+                           cols, totals);
+        hipLaunchKernelGGL(batch_cmds_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, totals, d_meshes, n_mesh, mesh_base, d_cmds,
+                           d_count);
+        hipLaunchKernelGGL(batch_scatter_kernel<IdT>, dim3(blocks), dim3(kBlock), lds, ctx->stream, d_mask,
+                           reinterpret_cast<const IdT*>(d_ids), n_inst, n_words, n_mesh, id_bits, p.words_per_row, p.rows, hist,
+                           mesh_base, d_out_ids);
+    });
     return VD_OK;
 }
 

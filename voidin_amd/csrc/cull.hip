@@ -14,7 +14,9 @@
 //     through the same slab and leave as 16-B-per-lane stores;
 //   * compact path, large inputs (split form), two launches: pass 1 `cull_mask_tiled_kernel`
 //     writes only one ballot bit + a compact mesh id per instance and the survivors of every
-//     1024-instance tile, so the read stream runs at ~6.5 TB/s; pass 2 `expand_mask_u8_kernel` /
+//     1024-instance tile, so the read stream runs at ~6.5 TB/s (it is `cull_tile`, the one tile
+//     skeleton, with `TiledPolicy`; the several-views and the occlusion pass 1 are the same
+//     skeleton with `ViewsPolicy` / `OccPolicy`); pass 2 `expand_mask_u8_kernel` /
 //     `expand_mask_kernel`: workgroup c sums the tile counts before its 8192-instance chunk and
 //     expands the chunk to out[offset[c]...): no ticket, no look-back, no wait on another
 //     workgroup, every load issued before the first store.
@@ -28,6 +30,7 @@
 //     per-round (mesh id | visible) words wait in LDS;
 //   * multi-GPU: the same pass 1 / pass 2 pair with the bitmask all-gathered in between
 //     (vd_cull_mask_dev / vd_expand_mask_dev, voidin_amd/dist.py).
+// Every float expression of the visibility test is written ONCE, below MeshRec: every kernel calls those.
 #include "vd_common.hpp"
 
 #include <math.h>
@@ -50,6 +53,9 @@ struct CullCamera {   // the slice of CameraUniform the shader reads (shared.wgs
     float frustum[4];
     float znear, zfar;
 };
+// Occlusion extension (include/voidin_abi.h, "Occlusion culling"): the projection terms and the depth pyramid (hiz.hip)
+struct OccProj { float p00, p11, p20, p21, p22, p32; };
+struct HizView { const float* base; unsigned width, height, n_levels; unsigned off[17]; };
 
 struct MeshRec { float mnx, mny, mnz; unsigned index_count; float mxx, mxy, mxz; unsigned base_index; int vertex_offset; };
 
@@ -63,16 +69,33 @@ __device__ __forceinline__ MeshRec load_mesh(const VdMeshInfo* __restrict__ mesh
     return m;
 }
 
+struct LaneInst { float4 T0, T1, T2, T3; unsigned mesh; };   // T = transform columns
+
 __device__ __forceinline__ float len3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 
-// emit_draws.wgsl:13-33 with the evaluation order of SURVEY.md §8a C2'. T = transform columns.
-__device__ __forceinline__ bool is_visible(const CullCamera& cam, const MeshRec& m, const float4 T0,
-                                           const float4 T1, const float4 T2, const float4 T3) {
-    const float* V = cam.view;
-    // center = (mesh.max + mesh.min) / 2
-    const float c0x = (m.mxx + m.mnx) / 2.0f, c0y = (m.mxy + m.mny) / 2.0f, c0z = (m.mxz + m.mnz) / 2.0f;
-    // rows 0..2 of (view * transform): column j = ((V.c0*Tj.x + V.c1*Tj.y) + V.c2*Tj.z) + V.c3*Tj.w
-    float c[3];
+// ------------------------------------------------------------------------------------------
+// The visibility test: emit_draws.wgsl:13-33 with the evaluation order of SURVEY.md §8a C2', and the occlusion
+// extension on the same view-space centre.  ONE definition of every expression: with
+// -ffp-contract=off the order written here is the contract with the oracle, for every kernel below.
+// ------------------------------------------------------------------------------------------
+struct MeshCentre { float x, y, z; };
+struct ViewCentre { float c[3]; float max_scale; };
+
+// center = (mesh.max + mesh.min) / 2
+__device__ __forceinline__ MeshCentre mesh_centre(const MeshRec& m) {
+    return MeshCentre{(m.mxx + m.mnx) / 2.0f, (m.mxy + m.mny) / 2.0f, (m.mxz + m.mnz) / 2.0f};
+}
+
+// extract_scale (math.wgsl:67-73) and max_scale
+__device__ __forceinline__ float max_scale(const float4 T0, const float4 T1, const float4 T2) {
+    const float sx = len3(T0.x, T0.y, T0.z), sy = len3(T1.x, T1.y, T1.z), sz = len3(T2.x, T2.y, T2.z);
+    return fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
+}
+
+// Rows 0..2 of (view * transform) * vec4(centre, 1): the view-space centre, c[].
+__device__ __forceinline__ void view_rows(const float* V, const MeshCentre c0, const float4 T0, const float4 T1, const float4 T2, const float4 T3,
+                                          float (&c)[3]) {
+    // column j = ((V.c0*Tj.x + V.c1*Tj.y) + V.c2*Tj.z) + V.c3*Tj.w
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const float v0 = V[r], v1 = V[4 + r], v2 = V[8 + r], v3 = V[12 + r];
@@ -81,25 +104,76 @@ __device__ __forceinline__ bool is_visible(const CullCamera& cam, const MeshRec&
         const float m2 = ((v0 * T2.x + v1 * T2.y) + v2 * T2.z) + v3 * T2.w;
         const float m3 = ((v0 * T3.x + v1 * T3.y) + v2 * T3.z) + v3 * T3.w;
         // (VT * vec4(center, 1)).r
-        c[r] = ((m0 * c0x + m1 * c0y) + m2 * c0z) + m3 * 1.0f;
+        c[r] = ((m0 * c0.x + m1 * c0.y) + m2 * c0.z) + m3 * 1.0f;
     }
-    // extract_scale (math.wgsl:67-73) and max_scale
-    const float sx = len3(T0.x, T0.y, T0.z), sy = len3(T1.x, T1.y, T1.z), sz = len3(T2.x, T2.y, T2.z);
-    const float max_scale = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
+}
+
+// What both tests start from.  mesh_centre and max_scale do not depend on the camera: a kernel with several cameras computes
+// them once per instance and calls the first form per camera; the second form is the whole of it for one camera.
+__device__ __forceinline__ ViewCentre view_centre(const float* V, const MeshCentre c0, const LaneInst& li, float max_scale) {
+    ViewCentre vc;
+    view_rows(V, c0, li.T0, li.T1, li.T2, li.T3, vc.c);
+    vc.max_scale = max_scale;
+    return vc;
+}
+__device__ __forceinline__ ViewCentre view_centre(const float* V, const MeshRec& m, const LaneInst& li) {
+    ViewCentre vc;
+    view_rows(V, mesh_centre(m), li.T0, li.T1, li.T2, li.T3, vc.c);
+    vc.max_scale = max_scale(li.T0, li.T1, li.T2);
+    return vc;
+}
+
+__device__ __forceinline__ bool frustum_visible(const CullCamera& cam, const MeshRec& m, const ViewCentre& vc) {
+    const float* c = vc.c;
     // radius: object-space min/max against the view-space centre — bug-compatible (C2)
     const float d0 = len3(m.mnx - c[0], m.mny - c[1], m.mnz - c[2]);
     const float d1 = len3(m.mxx - c[0], m.mxy - c[1], m.mxz - c[2]);
-    const float radius = fmaxf(d0, d1) * max_scale;
+    const float radius = fmaxf(d0, d1) * vc.max_scale;
     if (c[2] * cam.frustum[1] - fabsf(c[0]) * cam.frustum[0] < -radius) return false;
     if (c[2] * cam.frustum[3] - fabsf(c[1]) * cam.frustum[2] < -radius) return false;
     if (c[2] + radius > cam.znear && c[2] - radius > cam.zfar) return false;
     return true;
 }
 
+// does the bounding sphere lie behind the depth pyramid?  (no reference counterpart: definition in include/voidin_abi.h)
+__device__ __forceinline__ bool sphere_occluded(const OccProj& P, const float znear, const HizView& hz, const MeshRec& m, const ViewCentre& vc) {
+    const float* c = vc.c;
+    const float r = (len3(m.mxx - m.mnx, m.mxy - m.mny, m.mxz - m.mnz) * 0.5f) * vc.max_scale;
+    const float d = -c[2];
+    const float dn = d - r;
+    if (!(dn > znear)) return false;
+    const float rr = r * r, dd = d * d, rd = r * d;
+    const float tx = sqrtf((c[0] * c[0] + dd) - rr), ty = sqrtf((c[1] * c[1] + dd) - rr);
+    const float dxm = d * tx + c[0] * r, dxp = d * tx - c[0] * r, dym = d * ty + c[1] * r, dyp = d * ty - c[1] * r;
+    if (!(dxm > 0.0f && dxp > 0.0f && dym > 0.0f && dyp > 0.0f)) return false;
+    const float sx0 = (c[0] * tx - rd) / dxm, sx1 = (c[0] * tx + rd) / dxp;
+    const float sy0 = (c[1] * ty - rd) / dym, sy1 = (c[1] * ty + rd) / dyp;
+    const float nxa = P.p00 * sx0 - P.p20, nxb = P.p00 * sx1 - P.p20, nya = P.p11 * sy0 - P.p21, nyb = P.p11 * sy1 - P.p21;
+    const float nx_lo = fminf(nxa, nxb), nx_hi = fmaxf(nxa, nxb), ny_lo = fminf(nya, nyb), ny_hi = fmaxf(nya, nyb);
+    const float W = (float)hz.width, H = (float)hz.height;
+    const float u0 = (nx_lo * 0.5f + 0.5f) * W - 0.5f, u1 = (nx_hi * 0.5f + 0.5f) * W + 0.5f;
+    const float v0 = (0.5f - ny_hi * 0.5f) * H - 0.5f, v1 = (0.5f - ny_lo * 0.5f) * H + 0.5f;
+    if (!(u1 >= 0.0f && v1 >= 0.0f && u0 < W && v0 < H)) return false;
+    const unsigned x0 = (unsigned)floorf(fmaxf(u0, 0.0f)), x1 = (unsigned)floorf(fminf(u1, W - 1.0f));
+    const unsigned y0 = (unsigned)floorf(fmaxf(v0, 0.0f)), y1 = (unsigned)floorf(fminf(v1, H - 1.0f));
+    const unsigned span = max(x1 - x0, y1 - y0);
+    const unsigned lvl = min(span ? 32u - (unsigned)__clz((int)span) : 0u, hz.n_levels - 1u);
+    const float* t = hz.base + hz.off[lvl];
+    const unsigned lw = ((hz.width - 1u) >> lvl) + 1u;
+    const unsigned ax = x0 >> lvl, bx = x1 >> lvl, ay = y0 >> lvl, by = y1 >> lvl;
+    const float h0 = fminf(t[(size_t)ay * lw + ax], t[(size_t)ay * lw + bx]);
+    const float h1 = fminf(t[(size_t)by * lw + ax], t[(size_t)by * lw + bx]);
+    const float hmin = fminf(h0, h1);
+    const float depth = (P.p32 - P.p22 * dn) / dn;
+    return depth < hmin;
+}
+
+__device__ __forceinline__ bool is_visible(const CullCamera& cam, const MeshRec& m, const LaneInst& li) {
+    return frustum_visible(cam, m, view_centre(cam.view, m, li));
+}
+
 // Stream the 64 instances starting at `first` into this wave's LDS slab (coalesced 16 B per
 // lane), then return this lane's transform + mesh id.  `n_valid` = instances in range (<= 64).
-struct LaneInst { float4 T0, T1, T2, T3; unsigned mesh; };
-
 template <bool NT>
 __device__ __forceinline__ void slab_fill(const VdInstance* __restrict__ inst, size_t first,
                                           unsigned n_valid, unsigned lane, u32x4 (&regs)[kChunksPerLane]) {
@@ -161,7 +235,7 @@ __global__ __launch_bounds__(kBlock, 4) void emit_draws_kernel(CullCamera cam, c
 
         const unsigned mid = min(li.mesh, n_mesh - 1u);
         const MeshRec m = load_mesh(meshes, mid);
-        const bool vis = is_visible(cam, m, li.T0, li.T1, li.T2, li.T3);
+        const bool vis = is_visible(cam, m, li);
 
         // emit_draws.wgsl:55-63 — stage the wave's 64 commands (1280 B) and store 16 B per lane
         unsigned* cmd = reinterpret_cast<unsigned*>(slab) + lane * 5u;
@@ -238,7 +312,7 @@ void cull_compact_kernel(CullCamera cam, const VdMeshInfo* __restrict__ meshes, 
         vd_wave_lds_sync();
         const unsigned mid = min(li.mesh, n_mesh - 1u);
         const MeshRec m = load_mesh(meshes, mid);
-        const bool vis = lane < n_valid && is_visible(cam, m, li.T0, li.T1, li.T2, li.T3);
+        const bool vis = lane < n_valid && is_visible(cam, m, li);
         s_rec[r * kBlock + threadIdx.x] = mid | (vis ? 0x80000000u : 0u);
         wave_total += (unsigned)__popcll(__ballot(vis));
     }
@@ -285,13 +359,10 @@ constexpr int compact_lds_bytes() { return kWavesPerBlock * kSlabBytes + ROUNDS 
 // ------------------------------------------------------------------------------------------
 // Multi-GPU wire format: cull -> one bit per instance; expand bits -> ordered draw list.
 // ------------------------------------------------------------------------------------------
-// ids_out != nullptr: also write the (clamped) mesh id of every instance as IdT (vd_cull_mask_dev
-// passes none; the split single-GPU path uses cull_mask_tiled_kernel below).
-template <typename IdT>
+// (vd_cull_mask_dev: the mask alone; the split single-GPU path uses cull_mask_tiled_kernel below)
 __global__ __launch_bounds__(kBlock, 3) void cull_mask_kernel(CullCamera cam, const VdMeshInfo* __restrict__ meshes,
                                                                unsigned n_mesh, const VdInstance* __restrict__ inst,
-                                                               unsigned n_inst, vd_u64* __restrict__ mask,
-                                                               IdT* __restrict__ ids_out, unsigned n_wave_tiles) {
+                                                               unsigned n_inst, vd_u64* __restrict__ mask, unsigned n_wave_tiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     char* slab = smem + wave * kSlabBytes;
@@ -316,10 +387,9 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_kernel(CullCamera cam, co
         vd_wave_lds_sync();
         const unsigned mid = min(li.mesh, n_mesh - 1u);
         const MeshRec m = load_mesh(meshes, mid);
-        const bool vis = lane < n_valid && is_visible(cam, m, li.T0, li.T1, li.T2, li.T3);
+        const bool vis = lane < n_valid && is_visible(cam, m, li);
         const unsigned long long b = __ballot(vis);
         if (lane == 0) mask[wt] = b;
-        if (ids_out && lane < n_valid) ids_out[first + lane] = (IdT)mid;
     }
 }
 
@@ -329,56 +399,7 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_kernel(CullCamera cam, co
 // behind the depth pyramid.  Words of mask_in that are 0 cost nothing: their 9 KB of instances are not read, which
 // is the common case in the second pass of the two-pass scheme.
 // ------------------------------------------------------------------------------------------
-struct OccCamera { float view[16]; float p00, p11, p20, p21, p22, p32, znear; };
-struct HizView { const float* base; unsigned width, height, n_levels; unsigned off[17]; };
-
-__device__ __forceinline__ bool is_occluded(const OccCamera& cam, const HizView& hz, const MeshRec& m, const float4 T0, const float4 T1,
-                                            const float4 T2, const float4 T3) {
-    const float* V = cam.view;
-    const float c0x = (m.mxx + m.mnx) / 2.0f, c0y = (m.mxy + m.mny) / 2.0f, c0z = (m.mxz + m.mnz) / 2.0f;
-    float c[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float v0 = V[r], v1 = V[4 + r], v2 = V[8 + r], v3 = V[12 + r];
-        const float m0 = ((v0 * T0.x + v1 * T0.y) + v2 * T0.z) + v3 * T0.w;
-        const float m1 = ((v0 * T1.x + v1 * T1.y) + v2 * T1.z) + v3 * T1.w;
-        const float m2 = ((v0 * T2.x + v1 * T2.y) + v2 * T2.z) + v3 * T2.w;
-        const float m3 = ((v0 * T3.x + v1 * T3.y) + v2 * T3.z) + v3 * T3.w;
-        c[r] = ((m0 * c0x + m1 * c0y) + m2 * c0z) + m3 * 1.0f;
-    }
-    const float sx = len3(T0.x, T0.y, T0.z), sy = len3(T1.x, T1.y, T1.z), sz = len3(T2.x, T2.y, T2.z);
-    const float max_scale = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
-    const float r = (len3(m.mxx - m.mnx, m.mxy - m.mny, m.mxz - m.mnz) * 0.5f) * max_scale;
-    const float d = -c[2];
-    const float dn = d - r;
-    if (!(dn > cam.znear)) return false;
-    const float rr = r * r, dd = d * d, rd = r * d;
-    const float tx = sqrtf((c[0] * c[0] + dd) - rr), ty = sqrtf((c[1] * c[1] + dd) - rr);
-    const float dxm = d * tx + c[0] * r, dxp = d * tx - c[0] * r, dym = d * ty + c[1] * r, dyp = d * ty - c[1] * r;
-    if (!(dxm > 0.0f && dxp > 0.0f && dym > 0.0f && dyp > 0.0f)) return false;
-    const float sx0 = (c[0] * tx - rd) / dxm, sx1 = (c[0] * tx + rd) / dxp;
-    const float sy0 = (c[1] * ty - rd) / dym, sy1 = (c[1] * ty + rd) / dyp;
-    const float nxa = cam.p00 * sx0 - cam.p20, nxb = cam.p00 * sx1 - cam.p20, nya = cam.p11 * sy0 - cam.p21, nyb = cam.p11 * sy1 - cam.p21;
-    const float nx_lo = fminf(nxa, nxb), nx_hi = fmaxf(nxa, nxb), ny_lo = fminf(nya, nyb), ny_hi = fmaxf(nya, nyb);
-    const float W = (float)hz.width, H = (float)hz.height;
-    const float u0 = (nx_lo * 0.5f + 0.5f) * W - 0.5f, u1 = (nx_hi * 0.5f + 0.5f) * W + 0.5f;
-    const float v0 = (0.5f - ny_hi * 0.5f) * H - 0.5f, v1 = (0.5f - ny_lo * 0.5f) * H + 0.5f;
-    if (!(u1 >= 0.0f && v1 >= 0.0f && u0 < W && v0 < H)) return false;
-    const unsigned x0 = (unsigned)floorf(fmaxf(u0, 0.0f)), x1 = (unsigned)floorf(fminf(u1, W - 1.0f));
-    const unsigned y0 = (unsigned)floorf(fmaxf(v0, 0.0f)), y1 = (unsigned)floorf(fminf(v1, H - 1.0f));
-    const unsigned span = max(x1 - x0, y1 - y0);
-    const unsigned lvl = min(span ? 32u - (unsigned)__clz((int)span) : 0u, hz.n_levels - 1u);
-    const float* t = hz.base + hz.off[lvl];
-    const unsigned lw = ((hz.width - 1u) >> lvl) + 1u;
-    const unsigned ax = x0 >> lvl, bx = x1 >> lvl, ay = y0 >> lvl, by = y1 >> lvl;
-    const float h0 = fminf(t[(size_t)ay * lw + ax], t[(size_t)ay * lw + bx]);
-    const float h1 = fminf(t[(size_t)by * lw + ax], t[(size_t)by * lw + bx]);
-    const float hmin = fminf(h0, h1);
-    const float depth = (cam.p32 - cam.p22 * dn) / dn;
-    return depth < hmin;
-}
-
-__global__ __launch_bounds__(kBlock, 3) void occlusion_mask_kernel(OccCamera cam, HizView hz, const VdMeshInfo* __restrict__ meshes,
+__global__ __launch_bounds__(kBlock, 3) void occlusion_mask_kernel(CullCamera cam, OccProj proj, HizView hz, const VdMeshInfo* __restrict__ meshes,
                                                                    unsigned n_mesh, const VdInstance* __restrict__ inst, unsigned n_inst,
                                                                    const vd_u64* __restrict__ mask_in, vd_u64* __restrict__ mask_out,
                                                                    unsigned n_wave_tiles) {
@@ -403,142 +424,28 @@ __global__ __launch_bounds__(kBlock, 3) void occlusion_mask_kernel(OccCamera cam
         bool keep = false;
         if (lane < n_valid && ((in >> lane) & 1ull)) {
             const MeshRec m = load_mesh(meshes, min(li.mesh, n_mesh - 1u));
-            keep = !is_occluded(cam, hz, m, li.T0, li.T1, li.T2, li.T3);
+            keep = !sphere_occluded(proj, cam.znear, hz, m, view_centre(cam.view, m, li));
         }
         const unsigned long long b = __ballot(keep);
         if (lane == 0) mask_out[wt] = b;
     }
 }
 
-// Tiled form of pass 1: a wave owns kMaskRounds CONSECUTIVE rounds (1024 instances), keeps their
-// mesh ids and ballot words on chip and flushes them once per tile as wide stores, so the read
-// stream is interrupted by one 1-KB store per 147 KB read instead of a 64-B store per 9 KB.
-// With the flush goes the number of the tile's survivors, tile_count[t]: a plain store, ordered before pass 2 by the
-// kernel boundary.  The expansion of the single-GPU step sums these to place its chunk (expand_mask_u8_kernel<.., true>).
+// ------------------------------------------------------------------------------------------
+// Pass 1 of the two-launch forms: ONE tile skeleton (cull_tile), three kernels that differ in a policy.
+// A wave owns kMaskRounds CONSECUTIVE rounds (1024 instances), keeps their mesh ids and ballot words on chip and flushes
+// them once per tile as wide stores, so the read stream is interrupted by one 1-KB store per 147 KB read instead of a
+// 64-B store per 9 KB.  With the flush goes the number of the tile's survivors, tile_count[t]: a plain store, ordered
+// before pass 2 by the kernel boundary.  The expansion sums these to place its chunk (expand_mask_u8_kernel<.., true>).
+// No atomics, no fences, no wait on another workgroup.
+// ------------------------------------------------------------------------------------------
 constexpr int kMaskRounds = 16;
-template <typename IdT>
-__global__ __launch_bounds__(kBlock, 3) void cull_mask_tiled_kernel(CullCamera cam, const VdMeshInfo* __restrict__ meshes,
-                                                                     unsigned n_mesh, const VdInstance* __restrict__ inst,
-                                                                     unsigned n_inst, vd_u64* __restrict__ mask,
-                                                                     IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
-                                                                     unsigned n_tiles) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr int kIdBytes = kMaskRounds * kWave * (int)sizeof(IdT);
-    char* slab = smem + wave * (kSlabBytes + kIdBytes);
-    IdT* s_ids = reinterpret_cast<IdT*>(slab + kSlabBytes);
-    const unsigned waves_total = gridDim.x * kWavesPerBlock;
-    auto valid_at = [&](size_t f) -> unsigned { return f < n_inst ? (unsigned)min((size_t)64, (size_t)n_inst - f) : 0u; };
-    u32x4 regs[kChunksPerLane];
-    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < n_tiles; t += waves_total) {
-        const size_t tile_first = (size_t)t * (kWave * kMaskRounds);
-        slab_fill<true>(inst, tile_first, valid_at(tile_first), lane, regs);
-        // what the id table holds for this tile now: mesh assignment is static in practice (only transforms animate:
-        // shaders/compute_update.wgsl), and a row that already matches is not written again - a store interleaved
-        // with the read stream costs ~3x its bytes, a load does not.  Always correct: any row that
-        // differs (first frame, reallocated scratch, edited instances) is rewritten.
-        constexpr int kIdRows = kIdBytes / (kWave * 16);
-        u32x4 old_ids[kIdRows];
-        const size_t id_base0 = tile_first * sizeof(IdT);
-        const bool full_tile = tile_first + (size_t)kWave * kMaskRounds <= (size_t)n_inst;
-        if (full_tile) {
-#pragma unroll
-            for (int r = 0; r < kIdRows; ++r)
-                old_ids[r] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ids_out) + id_base0 + (size_t)r * kWave * 16 + lane * 16u);
-        }
-        vd_u64 my_word = 0;
-#pragma unroll 1
-        for (int r = 0; r < kMaskRounds; ++r) {
-            const size_t first = tile_first + (size_t)r * kWave;
-            const unsigned n_valid = valid_at(first);
-            slab_store(slab, lane, regs);
-            if (r + 1 < kMaskRounds) slab_fill<true>(inst, first + kWave, valid_at(first + kWave), lane, regs);
-            vd_wave_lds_sync();
-            const LaneInst li = slab_read(slab, lane);
-            vd_wave_lds_sync();
-            const unsigned mid = min(li.mesh, n_mesh - 1u);
-            const MeshRec m = load_mesh(meshes, mid);
-            const bool vis = lane < n_valid && is_visible(cam, m, li.T0, li.T1, li.T2, li.T3);
-            const unsigned long long b = __ballot(vis);
-            if (lane == (unsigned)r) my_word = b;
-            s_ids[r * kWave + lane] = (IdT)mid;
-        }
-        vd_wave_lds_sync();
-        // flush: ballot words (lane r holds round r) and the tile's ids as 16-B stores
-        const size_t w0 = (size_t)t * kMaskRounds;
-        const size_t n_words = ((size_t)n_inst + 63) / 64;
-        if (lane < (unsigned)kMaskRounds && w0 + lane < n_words) mask[w0 + lane] = my_word;
-        unsigned survivors = (unsigned)__popcll(my_word);                // 0 in lanes >= kMaskRounds
-#pragma unroll
-        for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
-        if (lane == 0u) tile_count[t] = survivors;
-        const size_t id_base = tile_first * sizeof(IdT);                 // bytes; tile_first % 1024 == 0 -> 16-B aligned
-        const size_t id_end = min((size_t)n_inst, tile_first + (size_t)kWave * kMaskRounds) * sizeof(IdT);
-        char* gids = reinterpret_cast<char*>(ids_out);
-        if (full_tile) {
-#pragma unroll
-            for (int r = 0; r < kIdRows; ++r) {
-                const unsigned b0 = (unsigned)r * kWave * 16u + lane * 16u;
-                const u32x4 nv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(s_ids) + b0);
-                const bool diff = nv.x != old_ids[r].x || nv.y != old_ids[r].y || nv.z != old_ids[r].z || nv.w != old_ids[r].w;
-                if (__any(diff)) *reinterpret_cast<u32x4*>(gids + id_base + b0) = nv;
-            }
-        } else {
-            for (unsigned b0 = lane * 16u; b0 < (unsigned)kIdBytes; b0 += kWave * 16u) {
-                if (id_base + b0 + 16u <= id_end) {
-                    *reinterpret_cast<u32x4*>(gids + id_base + b0) = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(s_ids) + b0);
-                } else {
-                    for (unsigned q = 0; q < 16u && id_base + b0 + q < id_end; ++q) gids[id_base + b0 + q] = reinterpret_cast<const char*>(s_ids)[b0 + q];
-                }
-            }
-        }
-        vd_wave_lds_sync();
-    }
-}
 
-// Pass 1 for several cameras in ONE read of the instances (vd_cull_compact_views*): the load path, tile ownership and id
-// table of cull_mask_tiled_kernel above, with the view-dependent part of is_visible evaluated once per camera while the
-// instance is in registers.  The test costs ~250 vector instructions per view and instance, under 15 % of the vector
-// budget at the HBM rate, so a further view is close to free until the vector unit fills up.
-//   * ONE instantiation per id width serves every view count: the view loop is a run-time loop (not unrolled), and its
-//     22 camera dwords are fetched by scalar loads from the kernel-argument segment at a wave-uniform offset (eight
-//     cameras are 176 dwords: more than the scalar registers of a wave, and nothing a lane should hold);
-//   * the 16 ballot words of view v live in the lanes 16 (v & 3) .. + 15 of one of two 64-bit registers (v >> 2): no LDS
-//     beyond the single-view kernel's, hence the same occupancy; the flush is one 8-byte store per lane and register;
-//   * per tile: n_views x 16 mask words (view v's mask = mask + v * mask_stride), n_views survivor counts
-//     (tile_count + v * count_stride) and the mesh ids ONCE, compared before they are stored, as above.
-// No atomics, no fences, no wait on another workgroup: the kernel boundary orders all of it before the expansions.
-constexpr int kMaxViews = VD_MAX_VIEWS;
-static_assert(kMaxViews * kMaskRounds == 2 * kWave, "two ballot registers per lane hold every (view, round) word of a tile");
-struct ViewCameras { CullCamera cam[kMaxViews]; };
-
-// The part of is_visible() that depends on the camera: the same expressions in the same order, from the mesh centre
-// (c0) and max_scale the caller computed once per instance exactly as is_visible() does.
-__device__ __forceinline__ bool is_visible_view(const CullCamera& cam, const MeshRec& m, const float c0x, const float c0y, const float c0z,
-                                                const float max_scale, const float4 T0, const float4 T1, const float4 T2, const float4 T3) {
-    const float* V = cam.view;
-    float c[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float v0 = V[r], v1 = V[4 + r], v2 = V[8 + r], v3 = V[12 + r];
-        const float m0 = ((v0 * T0.x + v1 * T0.y) + v2 * T0.z) + v3 * T0.w;
-        const float m1 = ((v0 * T1.x + v1 * T1.y) + v2 * T1.z) + v3 * T1.w;
-        const float m2 = ((v0 * T2.x + v1 * T2.y) + v2 * T2.z) + v3 * T2.w;
-        const float m3 = ((v0 * T3.x + v1 * T3.y) + v2 * T3.z) + v3 * T3.w;
-        c[r] = ((m0 * c0x + m1 * c0y) + m2 * c0z) + m3 * 1.0f;
-    }
-    const float d0 = len3(m.mnx - c[0], m.mny - c[1], m.mnz - c[2]);
-    const float d1 = len3(m.mxx - c[0], m.mxy - c[1], m.mxz - c[2]);
-    const float radius = fmaxf(d0, d1) * max_scale;
-    if (c[2] * cam.frustum[1] - fabsf(c[0]) * cam.frustum[0] < -radius) return false;
-    if (c[2] * cam.frustum[3] - fabsf(c[1]) * cam.frustum[2] < -radius) return false;
-    if (c[2] + radius > cam.znear && c[2] - radius > cam.zfar) return false;
-    return true;
-}
-
-// The id table's part of a pass-1 tile, as cull_mask_tiled_kernel has it inline (that kernel is left as it is; a change
-// to the flush belongs in both places): the tile's rows as the table holds them now, and - after the rounds - the store of
-// every row that differs, or of the whole ragged last tile.
+// The id table's part of a tile: the tile's rows as the table holds them now, and - after the rounds - the store of every
+// row that differs, or of the whole ragged last tile.  Mesh assignment is static in practice (only transforms animate:
+// shaders/compute_update.wgsl), and a row that already matches is not written again - a store interleaved with the read
+// stream costs ~3x its bytes, a load does not.  Always correct: any row that differs (first frame,
+// reallocated scratch, edited instances) is rewritten.
 template <typename IdT> struct TileIds {
     static constexpr int kBytes = kMaskRounds * kWave * (int)sizeof(IdT);
     static constexpr int kRows = kBytes / (kWave * 16);
@@ -576,150 +483,189 @@ template <typename IdT> struct TileIds {
     }
 };
 
-template <typename IdT>
-__global__ __launch_bounds__(kBlock, 3) void cull_mask_views_kernel(ViewCameras cams, unsigned n_views, const VdMeshInfo* __restrict__ meshes,
-                                                                     unsigned n_mesh, const VdInstance* __restrict__ inst,
-                                                                     unsigned n_inst, vd_u64* __restrict__ mask, size_t mask_stride,
-                                                                     IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
-                                                                     unsigned count_stride, unsigned n_tiles) {
+// One wave's tile t.  The policy is called once per round with this lane's instance - `live` = it exists - and keeps the
+// ballot word(s) it decides on in its own registers; flush(t), after the last round, stores them and their survivor
+// count(s).  Everything else of a tile is here: the instance stream through the wave-private slab (the next round's loads
+// in flight while this one is tested), the mesh clamp, and the id table.
+template <typename IdT, typename Policy>
+__device__ __forceinline__ void cull_tile(const VdMeshInfo* __restrict__ meshes, unsigned n_mesh, const VdInstance* __restrict__ inst,
+                                          unsigned n_inst, IdT* __restrict__ ids_out, unsigned t, Policy& policy) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr int kIdBytes = TileIds<IdT>::kBytes;
-    char* slab = smem + wave * (kSlabBytes + kIdBytes);
+    char* slab = smem + wave * (kSlabBytes + TileIds<IdT>::kBytes);
     IdT* s_ids = reinterpret_cast<IdT*>(slab + kSlabBytes);
-    const unsigned waves_total = gridDim.x * kWavesPerBlock;
     auto valid_at = [&](size_t f) -> unsigned { return f < n_inst ? (unsigned)min((size_t)64, (size_t)n_inst - f) : 0u; };
+    const size_t tile_first = (size_t)t * (kWave * kMaskRounds);
     u32x4 regs[kChunksPerLane];
-    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < n_tiles; t += waves_total) {
-        const size_t tile_first = (size_t)t * (kWave * kMaskRounds);
-        slab_fill<true>(inst, tile_first, valid_at(tile_first), lane, regs);
-        TileIds<IdT> tile_ids;                 // the id table's rows of this tile as they are now: only rows that differ are stored
-        tile_ids.load(ids_out, tile_first, n_inst, lane);
-        vd_u64 word_lo = 0, word_hi = 0;      // lane l: the ballot of view (l >> 4) [+ 4] in round l & 15
+    slab_fill<true>(inst, tile_first, valid_at(tile_first), lane, regs);
+    TileIds<IdT> tile_ids;
+    tile_ids.load(ids_out, tile_first, n_inst, lane);
 #pragma unroll 1
-        for (int r = 0; r < kMaskRounds; ++r) {
-            const size_t first = tile_first + (size_t)r * kWave;
-            const unsigned n_valid = valid_at(first);
-            slab_store(slab, lane, regs);
-            if (r + 1 < kMaskRounds) slab_fill<true>(inst, first + kWave, valid_at(first + kWave), lane, regs);
-            vd_wave_lds_sync();
-            const LaneInst li = slab_read(slab, lane);
-            vd_wave_lds_sync();
-            const unsigned mid = min(li.mesh, n_mesh - 1u);
-            const MeshRec m = load_mesh(meshes, mid);
-            // once per instance, as is_visible() has them: center = (mesh.max + mesh.min) / 2, extract_scale, max_scale
-            const float c0x = (m.mxx + m.mnx) / 2.0f, c0y = (m.mxy + m.mny) / 2.0f, c0z = (m.mxz + m.mnz) / 2.0f;
-            const float sx = len3(li.T0.x, li.T0.y, li.T0.z), sy = len3(li.T1.x, li.T1.y, li.T1.z), sz = len3(li.T2.x, li.T2.y, li.T2.z);
-            const float max_scale = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
-            const bool live = lane < n_valid;
-#pragma unroll 1
-            for (unsigned v = 0; v < n_views; ++v) {
-                const bool vis = live && is_visible_view(cams.cam[v], m, c0x, c0y, c0z, max_scale, li.T0, li.T1, li.T2, li.T3);
-                const unsigned long long b = __ballot(vis);
-                const unsigned slot = (v & 3u) * (unsigned)kMaskRounds + (unsigned)r;
-                if (lane == slot) { if (v < 4u) word_lo = b; else word_hi = b; }
-            }
-            s_ids[r * kWave + lane] = (IdT)mid;
-        }
+    for (int r = 0; r < kMaskRounds; ++r) {
+        const size_t first = tile_first + (size_t)r * kWave;
+        const unsigned n_valid = valid_at(first);
+        slab_store(slab, lane, regs);
+        if (r + 1 < kMaskRounds) slab_fill<true>(inst, first + kWave, valid_at(first + kWave), lane, regs);
         vd_wave_lds_sync();
-        // flush: every lane stores its word of each register into its view's mask; the survivors of a view are the
-        // bits of its 16 lanes
-        const size_t w0 = (size_t)t * kMaskRounds;
-        const size_t n_words = ((size_t)n_inst + 63) / 64;
+        const LaneInst li = slab_read(slab, lane);
+        vd_wave_lds_sync();
+        const unsigned mid = min(li.mesh, n_mesh - 1u);
+        const MeshRec m = load_mesh(meshes, mid);
+        policy.round(r, lane < n_valid, m, li);
+        s_ids[r * kWave + lane] = (IdT)mid;
+    }
+    vd_wave_lds_sync();
+    policy.flush(t);
+    tile_ids.flush(ids_out, s_ids, tile_first, n_inst, lane);
+    vd_wave_lds_sync();
+}
+
+// The survivors of a tile from its 16 ballot words, one per lane of a 16-lane group (lanes that hold none pass 0): summed
+// over the group, stored by the lane `leader` names.
+__device__ __forceinline__ void store_tile_count(unsigned* __restrict__ dst, vd_u64 my_word, bool leader) {
+    unsigned survivors = (unsigned)__popcll(my_word);
+#pragma unroll
+    for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
+    if (leader) *dst = survivors;
+}
+
+// One camera: one ballot word per round, round r's in lane r.
+struct TiledPolicy {
+    const CullCamera& cam;
+    vd_u64* __restrict__ mask; unsigned* __restrict__ tile_count; unsigned n_inst;
+    const unsigned lane = threadIdx.x & 63u;
+    vd_u64 my_word = 0;
+    __device__ __forceinline__ void round(int r, bool live, const MeshRec& m, const LaneInst& li) {
+        const vd_u64 b = __ballot(live && is_visible(cam, m, li));
+        if (lane == (unsigned)r) my_word = b;
+    }
+    __device__ __forceinline__ void flush(unsigned t) {
+        const size_t w0 = (size_t)t * kMaskRounds, n_words = ((size_t)n_inst + 63) / 64;
+        if (lane < (unsigned)kMaskRounds && w0 + lane < n_words) mask[w0 + lane] = my_word;
+        store_tile_count(tile_count + t, my_word, lane == 0u);           // my_word is 0 in lanes >= kMaskRounds
+    }
+};
+
+template <typename IdT>
+__global__ __launch_bounds__(kBlock, 3) void cull_mask_tiled_kernel(CullCamera cam, const VdMeshInfo* __restrict__ meshes,
+                                                                     unsigned n_mesh, const VdInstance* __restrict__ inst,
+                                                                     unsigned n_inst, vd_u64* __restrict__ mask,
+                                                                     IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
+                                                                     unsigned n_tiles) {
+    for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
+        TiledPolicy policy{cam, mask, tile_count, n_inst};
+        cull_tile(meshes, n_mesh, inst, n_inst, ids_out, t, policy);
+    }
+}
+
+// Several cameras in ONE read of the instances (vd_cull_compact_views*): the camera-independent part of the test
+// (mesh_centre, max_scale) once per instance, the rest once per camera while the instance is in registers.  The test costs ~250 vector
+// instructions per view and instance, under 15 % of the vector budget at the HBM rate, so a further view is
+// close to free until the vector unit fills up.
+//   * ONE instantiation per id width serves every view count: the view loop is a run-time loop (not unrolled), and its
+//     22 camera dwords are fetched by scalar loads from the kernel-argument segment at a wave-uniform offset (eight
+//     cameras are 176 dwords: more than the scalar registers of a wave, and nothing a lane should hold);
+//   * the 16 ballot words of view v live in the lanes 16 (v & 3) .. + 15 of one of two 64-bit registers (v >> 2): no LDS
+//     beyond the single-view kernel's, hence the same occupancy; the flush is one 8-byte store per lane and register;
+//   * per tile: n_views x 16 mask words (view v's mask = mask + v * mask_stride), n_views survivor counts
+//     (tile_count + v * count_stride) and the mesh ids ONCE.
+constexpr int kMaxViews = VD_MAX_VIEWS;
+static_assert(kMaxViews * kMaskRounds == 2 * kWave, "two ballot registers per lane hold every (view, round) word of a tile");
+struct ViewCameras { CullCamera cam[kMaxViews]; };
+
+struct ViewsPolicy {
+    const ViewCameras& cams; unsigned n_views;
+    vd_u64* __restrict__ mask; size_t mask_stride; unsigned* __restrict__ tile_count; unsigned count_stride; unsigned n_inst;
+    const unsigned lane = threadIdx.x & 63u;
+    vd_u64 word_lo = 0, word_hi = 0;      // lane l: the ballot of view (l >> 4) [+ 4] in round l & 15
+    __device__ __forceinline__ void round(int r, bool live, const MeshRec& m, const LaneInst& li) {
+        const MeshCentre c0 = mesh_centre(m);
+        const float ms = max_scale(li.T0, li.T1, li.T2);
+#pragma unroll 1
+        for (unsigned v = 0; v < n_views; ++v) {
+            const CullCamera& cam = cams.cam[v];
+            const vd_u64 b = __ballot(live && frustum_visible(cam, m, view_centre(cam.view, c0, li, ms)));
+            const unsigned slot = (v & 3u) * (unsigned)kMaskRounds + (unsigned)r;
+            if (lane == slot) { if (v < 4u) word_lo = b; else word_hi = b; }
+        }
+    }
+    // every lane stores its word of each register into its view's mask; the survivors of a view are the bits of its 16 lanes
+    __device__ __forceinline__ void flush(unsigned t) {
+        const size_t w0 = (size_t)t * kMaskRounds, n_words = ((size_t)n_inst + 63) / 64;
         const unsigned slot_view = lane >> 4, slot_round = lane & 15u;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const unsigned v = (unsigned)h * 4u + slot_view;
             const vd_u64 my_word = h ? word_hi : word_lo;                // 0 where no view wrote it
             if (v < n_views && w0 + slot_round < n_words) mask[(size_t)v * mask_stride + w0 + slot_round] = my_word;
-            unsigned survivors = (unsigned)__popcll(my_word);
-#pragma unroll
-            for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
-            if (slot_round == 0u && v < n_views) tile_count[(size_t)v * count_stride + t] = survivors;
+            store_tile_count(tile_count + (size_t)v * count_stride + t, my_word, slot_round == 0u && v < n_views);
         }
-        tile_ids.flush(ids_out, s_ids, tile_first, n_inst, lane);
-        vd_wave_lds_sync();
+    }
+};
+
+template <typename IdT>
+__global__ __launch_bounds__(kBlock, 3) void cull_mask_views_kernel(ViewCameras cams, unsigned n_views, const VdMeshInfo* __restrict__ meshes,
+                                                                     unsigned n_mesh, const VdInstance* __restrict__ inst,
+                                                                     unsigned n_inst, vd_u64* __restrict__ mask, size_t mask_stride,
+                                                                     IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
+                                                                     unsigned count_stride, unsigned n_tiles) {
+    for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
+        ViewsPolicy policy{cams, n_views, mask, mask_stride, tile_count, count_stride, n_inst};
+        cull_tile(meshes, n_mesh, inst, n_inst, ids_out, t, policy);
     }
 }
 
-// Pass 1 of the occlusion-culled draw lists (vd_cull_compact_hiz*, vd_cull_early_dev, vd_cull_late_dev; extension, no
-// reference counterpart): the load path, tile ownership, id table and flush of cull_mask_tiled_kernel, with the frustum test
-// AND - where a pyramid is bound - the occlusion test evaluated while the instance is in registers, so the list of
-// unoccluded instances costs one read of the instances instead of two (vd_cull_mask_dev, then vd_occlusion_mask_dev).
-// With F = is_visible, V = F and not is_occluded, P = the caller's visible-last-frame bits:
+// The occlusion-culled draw lists (vd_cull_compact_hiz*, vd_cull_early_dev, vd_cull_late_dev; extension, no reference
+// counterpart): the frustum test AND - where a pyramid is bound - the occlusion test evaluated while the instance is in
+// registers, so the list of unoccluded instances costs one read of the instances instead of two (vd_cull_mask_dev, then
+// vd_occlusion_mask_dev).  With F = frustum_visible, V = F and not sphere_occluded, P = the caller's visible-last-frame bits:
 //   HIZ,  no PREV (hiz):    list = V
 //   PREV, no HIZ  (early):  list = F & P
 //   HIZ and PREV  (late):   list = V & ~P, and V itself goes to visible_out (which may be the buffer P came from: a wave
 //                           reads its tile's 16 words of P before it stores anything, and no other wave touches them)
-// The view-space centre and max_scale are computed once and feed both tests: the expressions, in the order is_visible()
-// and is_occluded() have them (-ffp-contract=off keeps them bit-identical).  Instances that fail the frustum test do not
-// fetch pyramid texels, and a round none of whose instances passes skips the occlusion test altogether.  The pyramid is
-// read through the ordinary cached path: only the instance stream is nontemporal.
-struct OccProj { float p00, p11, p20, p21, p22, p32; };
-struct ViewCentre { float c[3]; float max_scale; };
-
-__device__ __forceinline__ ViewCentre view_centre(const float* V, const MeshRec& m, const float4 T0, const float4 T1, const float4 T2,
-                                                  const float4 T3) {
-    const float c0x = (m.mxx + m.mnx) / 2.0f, c0y = (m.mxy + m.mny) / 2.0f, c0z = (m.mxz + m.mnz) / 2.0f;
-    ViewCentre vc;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float v0 = V[r], v1 = V[4 + r], v2 = V[8 + r], v3 = V[12 + r];
-        const float m0 = ((v0 * T0.x + v1 * T0.y) + v2 * T0.z) + v3 * T0.w;
-        const float m1 = ((v0 * T1.x + v1 * T1.y) + v2 * T1.z) + v3 * T1.w;
-        const float m2 = ((v0 * T2.x + v1 * T2.y) + v2 * T2.z) + v3 * T2.w;
-        const float m3 = ((v0 * T3.x + v1 * T3.y) + v2 * T3.z) + v3 * T3.w;
-        vc.c[r] = ((m0 * c0x + m1 * c0y) + m2 * c0z) + m3 * 1.0f;
+// One view_centre feeds both tests.  Instances that fail the frustum test do not fetch pyramid texels, and a round none of
+// whose instances passes skips the occlusion test altogether.  The pyramid is read through the ordinary cached path: only
+// the instance stream is nontemporal.
+template <bool HIZ, bool PREV>
+struct OccPolicy {
+    const CullCamera& cam; const OccProj& proj; const HizView& hz;
+    vd_u64* __restrict__ mask; vd_u64* visible_out; unsigned* __restrict__ tile_count;
+    const unsigned lane = threadIdx.x & 63u;
+    bool my_slot;                         // lane r holds the words of round r
+    unsigned p_lo = 0u, p_hi = 0u;
+    vd_u64 list_word = 0, vis_word = 0;
+    // this tile's 16 words of P, before anything of the tile is written (visible_out may be the same buffer)
+    __device__ __forceinline__ void begin(unsigned t, unsigned n_inst, const vd_u64* prev) {
+        const size_t w0 = (size_t)t * kMaskRounds, n_words = ((size_t)n_inst + 63) / 64;
+        my_slot = lane < (unsigned)kMaskRounds && w0 + lane < n_words;
+        if (PREV && my_slot) { const vd_u64 p = prev[w0 + lane]; p_lo = (unsigned)p; p_hi = (unsigned)(p >> 32); }
     }
-    const float sx = len3(T0.x, T0.y, T0.z), sy = len3(T1.x, T1.y, T1.z), sz = len3(T2.x, T2.y, T2.z);
-    vc.max_scale = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sz));
-    return vc;
-}
-
-// is_visible() from its view-space centre on
-__device__ __forceinline__ bool frustum_visible(const CullCamera& cam, const MeshRec& m, const ViewCentre& vc) {
-    const float* c = vc.c;
-    const float d0 = len3(m.mnx - c[0], m.mny - c[1], m.mnz - c[2]);
-    const float d1 = len3(m.mxx - c[0], m.mxy - c[1], m.mxz - c[2]);
-    const float radius = fmaxf(d0, d1) * vc.max_scale;
-    if (c[2] * cam.frustum[1] - fabsf(c[0]) * cam.frustum[0] < -radius) return false;
-    if (c[2] * cam.frustum[3] - fabsf(c[1]) * cam.frustum[2] < -radius) return false;
-    if (c[2] + radius > cam.znear && c[2] - radius > cam.zfar) return false;
-    return true;
-}
-
-// is_occluded() from its view-space centre on
-__device__ __forceinline__ bool sphere_occluded(const OccProj& P, const float znear, const HizView& hz, const MeshRec& m, const ViewCentre& vc) {
-    const float* c = vc.c;
-    const float r = (len3(m.mxx - m.mnx, m.mxy - m.mny, m.mxz - m.mnz) * 0.5f) * vc.max_scale;
-    const float d = -c[2];
-    const float dn = d - r;
-    if (!(dn > znear)) return false;
-    const float rr = r * r, dd = d * d, rd = r * d;
-    const float tx = sqrtf((c[0] * c[0] + dd) - rr), ty = sqrtf((c[1] * c[1] + dd) - rr);
-    const float dxm = d * tx + c[0] * r, dxp = d * tx - c[0] * r, dym = d * ty + c[1] * r, dyp = d * ty - c[1] * r;
-    if (!(dxm > 0.0f && dxp > 0.0f && dym > 0.0f && dyp > 0.0f)) return false;
-    const float sx0 = (c[0] * tx - rd) / dxm, sx1 = (c[0] * tx + rd) / dxp;
-    const float sy0 = (c[1] * ty - rd) / dym, sy1 = (c[1] * ty + rd) / dyp;
-    const float nxa = P.p00 * sx0 - P.p20, nxb = P.p00 * sx1 - P.p20, nya = P.p11 * sy0 - P.p21, nyb = P.p11 * sy1 - P.p21;
-    const float nx_lo = fminf(nxa, nxb), nx_hi = fmaxf(nxa, nxb), ny_lo = fminf(nya, nyb), ny_hi = fmaxf(nya, nyb);
-    const float W = (float)hz.width, H = (float)hz.height;
-    const float u0 = (nx_lo * 0.5f + 0.5f) * W - 0.5f, u1 = (nx_hi * 0.5f + 0.5f) * W + 0.5f;
-    const float v0 = (0.5f - ny_hi * 0.5f) * H - 0.5f, v1 = (0.5f - ny_lo * 0.5f) * H + 0.5f;
-    if (!(u1 >= 0.0f && v1 >= 0.0f && u0 < W && v0 < H)) return false;
-    const unsigned x0 = (unsigned)floorf(fmaxf(u0, 0.0f)), x1 = (unsigned)floorf(fminf(u1, W - 1.0f));
-    const unsigned y0 = (unsigned)floorf(fmaxf(v0, 0.0f)), y1 = (unsigned)floorf(fminf(v1, H - 1.0f));
-    const unsigned span = max(x1 - x0, y1 - y0);
-    const unsigned lvl = min(span ? 32u - (unsigned)__clz((int)span) : 0u, hz.n_levels - 1u);
-    const float* t = hz.base + hz.off[lvl];
-    const unsigned lw = ((hz.width - 1u) >> lvl) + 1u;
-    const unsigned ax = x0 >> lvl, bx = x1 >> lvl, ay = y0 >> lvl, by = y1 >> lvl;
-    const float h0 = fminf(t[(size_t)ay * lw + ax], t[(size_t)ay * lw + bx]);
-    const float h1 = fminf(t[(size_t)by * lw + ax], t[(size_t)by * lw + bx]);
-    const float hmin = fminf(h0, h1);
-    const float depth = (P.p32 - P.p22 * dn) / dn;
-    return depth < hmin;
-}
+    __device__ __forceinline__ void round(int r, bool live, const MeshRec& m, const LaneInst& li) {
+        const ViewCentre vc = view_centre(cam.view, m, li);
+        bool keep = live && frustum_visible(cam, m, vc);
+        if (HIZ) {
+            if (__ballot(keep) != 0ull) {                              // wave-uniform: a round wholly outside the frustum fetches no texel
+                if (keep) keep = !sphere_occluded(proj, cam.znear, hz, m, vc);
+            }
+        }
+        vd_u64 b = __ballot(keep);
+        if (PREV) {
+            const vd_u64 p = (vd_u64)(unsigned)__builtin_amdgcn_readlane((int)p_lo, r) |
+                             ((vd_u64)(unsigned)__builtin_amdgcn_readlane((int)p_hi, r) << 32);
+            if (HIZ) { if (lane == (unsigned)r) vis_word = b; b &= ~p; }
+            else b &= p;
+        }
+        if (lane == (unsigned)r) list_word = b;
+    }
+    __device__ __forceinline__ void flush(unsigned t) {
+        const size_t w0 = (size_t)t * kMaskRounds;
+        if (my_slot) {
+            mask[w0 + lane] = list_word;
+            if (HIZ && PREV) visible_out[w0 + lane] = vis_word;
+        }
+        store_tile_count(tile_count + t, list_word, lane == 0u);         // list_word is 0 in lanes >= kMaskRounds
+    }
+};
 
 template <typename IdT, bool HIZ, bool PREV>
 __global__ __launch_bounds__(kBlock, 3) void cull_mask_occ_kernel(CullCamera cam, OccProj proj, HizView hz, const VdMeshInfo* __restrict__ meshes,
@@ -727,66 +673,13 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_occ_kernel(CullCamera cam
                                                                    vd_u64* __restrict__ mask, const vd_u64* prev, vd_u64* visible_out,
                                                                    IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
                                                                    unsigned n_tiles) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr int kIdBytes = TileIds<IdT>::kBytes;
-    char* slab = smem + wave * (kSlabBytes + kIdBytes);
-    IdT* s_ids = reinterpret_cast<IdT*>(slab + kSlabBytes);
-    const unsigned waves_total = gridDim.x * kWavesPerBlock;
-    const size_t n_words = ((size_t)n_inst + 63) / 64;
-    auto valid_at = [&](size_t f) -> unsigned { return f < n_inst ? (unsigned)min((size_t)64, (size_t)n_inst - f) : 0u; };
-    u32x4 regs[kChunksPerLane];
-    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < n_tiles; t += waves_total) {
-        const size_t tile_first = (size_t)t * (kWave * kMaskRounds);
-        const size_t w0 = (size_t)t * kMaskRounds;
-        const bool my_slot = lane < (unsigned)kMaskRounds && w0 + lane < n_words;      // lane r holds the words of round r
-        slab_fill<true>(inst, tile_first, valid_at(tile_first), lane, regs);
-        // this tile's 16 words of P, before anything of the tile is written (visible_out may be the same buffer)
-        unsigned p_lo = 0u, p_hi = 0u;
-        if (PREV && my_slot) { const vd_u64 p = prev[w0 + lane]; p_lo = (unsigned)p; p_hi = (unsigned)(p >> 32); }
-        TileIds<IdT> tile_ids;                 // the id table's rows of this tile as they are now: only rows that differ are stored
-        tile_ids.load(ids_out, tile_first, n_inst, lane);
-        vd_u64 list_word = 0, vis_word = 0;
-#pragma unroll 1
-        for (int r = 0; r < kMaskRounds; ++r) {
-            const size_t first = tile_first + (size_t)r * kWave;
-            const unsigned n_valid = valid_at(first);
-            slab_store(slab, lane, regs);
-            if (r + 1 < kMaskRounds) slab_fill<true>(inst, first + kWave, valid_at(first + kWave), lane, regs);
-            vd_wave_lds_sync();
-            const LaneInst li = slab_read(slab, lane);
-            vd_wave_lds_sync();
-            const unsigned mid = min(li.mesh, n_mesh - 1u);
-            const MeshRec m = load_mesh(meshes, mid);
-            const ViewCentre vc = view_centre(cam.view, m, li.T0, li.T1, li.T2, li.T3);
-            bool keep = lane < n_valid && frustum_visible(cam, m, vc);
-            if (HIZ) {
-                if (__ballot(keep) != 0ull) {                              // wave-uniform: a round wholly outside the frustum fetches no texel
-                    if (keep) keep = !sphere_occluded(proj, cam.znear, hz, m, vc);
-                }
-            }
-            vd_u64 b = __ballot(keep);
-            if (PREV) {
-                const vd_u64 p = (vd_u64)(unsigned)__builtin_amdgcn_readlane((int)p_lo, r) |
-                                 ((vd_u64)(unsigned)__builtin_amdgcn_readlane((int)p_hi, r) << 32);
-                if (HIZ) { if (lane == (unsigned)r) vis_word = b; b &= ~p; }
-                else b &= p;
-            }
-            if (lane == (unsigned)r) list_word = b;
-            s_ids[r * kWave + lane] = (IdT)mid;
-        }
-        vd_wave_lds_sync();
-        // flush: the list's ballot words (and V's), the tile's survivor count, the id rows that changed
-        if (my_slot) {
-            mask[w0 + lane] = list_word;
-            if (HIZ && PREV) visible_out[w0 + lane] = vis_word;
-        }
-        unsigned survivors = (unsigned)__popcll(list_word);               // 0 in lanes >= kMaskRounds
-#pragma unroll
-        for (int off = kMaskRounds / 2; off > 0; off >>= 1) survivors += __shfl_xor(survivors, off);
-        if (lane == 0u) tile_count[t] = survivors;
-        tile_ids.flush(ids_out, s_ids, tile_first, n_inst, lane);
-        vd_wave_lds_sync();
+    for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
+        OccPolicy<HIZ, PREV> policy{cam, proj, hz, mask, visible_out, tile_count};
+        policy.begin(t, n_inst, prev);
+        // (t is the same in every lane of the wave.  The early forms say so: the tile's addresses then live in scalar registers,
+        // which the 4-byte-id one, at the 168-register ceiling of three waves per SIMD, needs to stay free of spills.  The forms
+        // that read the pyramid measured 0.2-0.6 % slower with it: profiles/cull_pass1_refactor.md, section 3)
+        cull_tile(meshes, n_mesh, inst, n_inst, ids_out, HIZ ? t : (unsigned)__builtin_amdgcn_readfirstlane((int)t), policy);
     }
 }
 
@@ -1402,26 +1295,24 @@ static int launch_expand(VdCtx* ctx, const vd_u64* d_mask, unsigned n_words, uns
     if (fast) {
         // up to ~250 MB of commands (the Infinity Cache absorbs them) the direct form is at the write ceiling; past
         // that the L2 merges fewer of its 4-byte pieces in time and the LDS-staged 16-byte runs win
-#define VD_EXPAND_U8(D, T)                                                                                                  \
-        hipLaunchKernelGGL((expand_mask_u8_kernel<D, T>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps, \
-                           shard_size, n_total, first_instance, reinterpret_cast<const unsigned char*>(d_ids), d_meshes,      \
-                           n_mesh, d_out, offsets, d_tile_count, d_out_count)
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps, shard_size, n_total, first_instance,
+                               reinterpret_cast<const unsigned char*>(d_ids), d_meshes, n_mesh, d_out, offsets, d_tile_count, d_out_count);
+        };
         const bool direct = n_total <= (12u << 20);
-        if (d_tile_count) { if (direct) VD_EXPAND_U8(true, true); else VD_EXPAND_U8(false, true); }
-        else { if (direct) VD_EXPAND_U8(true, false); else VD_EXPAND_U8(false, false); }
-#undef VD_EXPAND_U8
+        if (d_tile_count) { if (direct) launch(expand_mask_u8_kernel<true, true>); else launch(expand_mask_u8_kernel<false, true>); }
+        else { if (direct) launch(expand_mask_u8_kernel<true, false>); else launch(expand_mask_u8_kernel<false, false>); }
         return VD_OK;
     }
-#define VD_EXPAND_T(IdT, T, S)                                                                                             \
-    hipLaunchKernelGGL((expand_mask_kernel<IdT, T, S>), dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps, \
-                       shard_size, n_total, first_instance, reinterpret_cast<const IdT*>(d_ids), d_meshes, n_mesh, d_out,    \
-                       offsets, d_tile_count, d_out_count)
-#define VD_EXPAND(IdT, T) do { if (d_tile_count) VD_EXPAND_T(IdT, T, true); else VD_EXPAND_T(IdT, T, false); } while (0)
-    if (id_bytes == 1u) { if (tab) VD_EXPAND(unsigned char, true); else VD_EXPAND(unsigned char, false); }
-    else if (id_bytes == 2u) { if (tab) VD_EXPAND(unsigned short, true); else VD_EXPAND(unsigned short, false); }
-    else { if (tab) VD_EXPAND(unsigned, true); else VD_EXPAND(unsigned, false); }
-#undef VD_EXPAND
-#undef VD_EXPAND_T
+    vd_dispatch_id(id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(kBlock), 0, ctx->stream, d_mask, n_words, wps, shard_size, n_total, first_instance,
+                               reinterpret_cast<const IdT*>(d_ids), d_meshes, n_mesh, d_out, offsets, d_tile_count, d_out_count);
+        };
+        if (d_tile_count) { if (tab) launch(expand_mask_kernel<IdT, true, true>); else launch(expand_mask_kernel<IdT, false, true>); }
+        else { if (tab) launch(expand_mask_kernel<IdT, true, false>); else launch(expand_mask_kernel<IdT, false, false>); }
+    });
     return VD_OK;
 }
 
@@ -1566,6 +1457,62 @@ CullCamera make_cam(const VdCameraUniform* c) {
     return k;
 }
 
+OccProj make_proj(const VdCameraUniform* c) {
+    const float* P = c->projection;
+    return OccProj{P[0], P[5], P[8], P[9], P[10], P[14]};
+}
+
+HizView make_hiz(const float* d_pyramid, unsigned width, unsigned height, const VdHizLayout& L) {
+    HizView hz;
+    hz.base = d_pyramid; hz.width = width; hz.height = height; hz.n_levels = L.n_levels;
+    for (int k = 0; k < 17; ++k) hz.off[k] = L.level_offset[k];
+    return hz;
+}
+
+// Pass 1 for n_views cameras over n_inst instances: the id width, the tile and launch geometry, and where its outputs lie
+// in the arena - [id table | n_views masks | n_views count tables], the id table at offset 0 whatever n_views is.
+// ctx->scratch keeps its older order, [mask | id table | counts] (mask_first): the common one would round the id table up
+// to 256 bytes and so need up to 240 bytes more than it has today.  What the expansion relies on holds in both: the id
+// table dword-aligned (16 bytes for full tiles: tiles are 1024 ids), every mask 256-byte aligned, every count table
+// 16-byte aligned and padded to whole groups of 4 entries (tile_prefix_partial).
+struct Pass1Plan {
+    unsigned id_bytes, n_words, n_mt;     // id width by n_mesh; mask words; 1024-instance tiles
+    unsigned mb, lds_bytes;               // workgroups (a wave per tile, grid-stride beyond 3 per CU) and their dynamic LDS
+    size_t ids_off, mask_off, counts_off, need;     // bytes
+    size_t mask_stride, count_stride;               // words between two views' masks / entries between their count tables
+    void* ids(void* arena) const { return reinterpret_cast<char*>(arena) + ids_off; }
+    vd_u64* mask(void* arena) const { return reinterpret_cast<vd_u64*>(reinterpret_cast<char*>(arena) + mask_off); }
+    unsigned* counts(void* arena) const { return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(arena) + counts_off); }
+};
+
+Pass1Plan pass1_plan(const VdCtx* ctx, unsigned n_inst, unsigned n_mesh, unsigned n_views, bool mask_first = false) {
+    Pass1Plan p;
+    p.id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
+    p.n_words = (n_inst + 63u) / 64u;
+    p.n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
+    p.mb = (p.n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (p.mb > (unsigned)ctx->num_cus * 3u) p.mb = (unsigned)ctx->num_cus * 3u;
+    p.lds_bytes = kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * p.id_bytes);
+    const size_t ids_bytes = (size_t)n_inst * p.id_bytes, mask_bytes = ((size_t)p.n_words * 8 + 255) & ~(size_t)255;
+    p.mask_stride = mask_bytes / 8;
+    p.count_stride = ((size_t)p.n_mt + 3) & ~(size_t)3;
+    if (mask_first) {
+        p.mask_off = 0;
+        p.ids_off = n_views * mask_bytes;
+        p.counts_off = (p.ids_off + ids_bytes + 15) & ~(size_t)15;
+    } else {
+        p.ids_off = 0;
+        p.mask_off = (ids_bytes + 255) & ~(size_t)255;
+        p.counts_off = p.mask_off + n_views * mask_bytes;
+    }
+    p.need = p.counts_off + n_views * p.count_stride * 4 + 512;
+    return p;
+}
+
+void launch_pad_tail(VdCtx* ctx, VdDrawIndexedIndirect* d_out, const unsigned* d_count, unsigned n_inst) {
+    hipLaunchKernelGGL(pad_tail_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(kBlock), 0, ctx->stream, d_out, d_count, n_inst);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1582,31 +1529,20 @@ int vd_cull_emit_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
 int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
                             const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids, unsigned* out_id_bytes,
                             unsigned** out_tile_count) {
-    const unsigned n_words = (n_inst + 63u) / 64u;
-    const unsigned id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
-    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
-    const size_t ids_off = ((size_t)n_words * 8 + 255) & ~(size_t)255;
-    const size_t counts_off = (ids_off + (size_t)n_inst * id_bytes + 15) & ~(size_t)15;
-    const size_t need = counts_off + (((size_t)n_mt + 3) & ~(size_t)3) * 4 + 512;
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, need);
+    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u, /*mask_first=*/true);
+    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, p.need);
     if (rc) return rc;
-    vd_u64* d_mask = reinterpret_cast<vd_u64*>(ctx->scratch);
-    void* d_ids = reinterpret_cast<char*>(ctx->scratch) + ids_off;
-    unsigned* d_counts = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctx->scratch) + counts_off);
+    vd_u64* d_mask = p.mask(ctx->scratch);
+    void* d_ids = p.ids(ctx->scratch);
+    unsigned* d_counts = p.counts(ctx->scratch);
     vd_time_begin(ctx);
-    unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
-#define VD_SPLIT(IdT)                                                                                              \
-    hipLaunchKernelGGL(cull_mask_tiled_kernel<IdT>, dim3(mb), dim3(kBlock),                                        \
-                       kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
-                       ctx->stream, make_cam(camera), d_meshes, n_mesh, d_instances, n_inst, d_mask,               \
-                       reinterpret_cast<IdT*>(d_ids), d_counts, n_mt)
-    if (id_bytes == 1u) VD_SPLIT(unsigned char);
-    else if (id_bytes == 2u) VD_SPLIT(unsigned short);
-    else VD_SPLIT(unsigned);
-#undef VD_SPLIT
+    vd_dispatch_id(p.id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        hipLaunchKernelGGL(cull_mask_tiled_kernel<IdT>, dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, make_cam(camera), d_meshes, n_mesh,
+                           d_instances, n_inst, d_mask, reinterpret_cast<IdT*>(d_ids), d_counts, p.n_mt);
+    });
     vd_time_mid(ctx);
-    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = id_bytes; *out_tile_count = d_counts;
+    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = p.id_bytes; *out_tile_count = d_counts;
     return VD_OK;
 }
 
@@ -1626,14 +1562,17 @@ int vd_cull_emit_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMe
         const unsigned quads = (n_inst + 3u) / 4u;
         unsigned eb = (quads + kBlock - 1) / kBlock;
         if (eb > (unsigned)ctx->num_cus * 16u) eb = (unsigned)ctx->num_cus * 16u;
-#define VD_EMIT(IdT) hipLaunchKernelGGL(emit_from_mask_kernel<IdT>, dim3(eb), dim3(kBlock), 0, ctx->stream, d_mask,               \
-                                        reinterpret_cast<const IdT*>(d_ids), d_meshes, n_mesh, n_inst, first_instance, d_out)
         if (id_bytes == 1u) {
             const unsigned n_words = (n_inst + 63u) / 64u;
             hipLaunchKernelGGL(emit_all_u8_kernel, dim3((n_words + kChunkWords - 1) / kChunkWords), dim3(kBlock), 0, ctx->stream, d_mask,
                                n_words, n_inst, first_instance, reinterpret_cast<const unsigned char*>(d_ids), d_meshes, n_mesh, d_out);
-        } else if (id_bytes == 2u) VD_EMIT(unsigned short); else VD_EMIT(unsigned);
-#undef VD_EMIT
+        } else {
+            auto launch = [&](auto kernel, auto ids) {
+                hipLaunchKernelGGL(kernel, dim3(eb), dim3(kBlock), 0, ctx->stream, d_mask, ids, d_meshes, n_mesh, n_inst, first_instance, d_out);
+            };
+            if (id_bytes == 2u) launch(emit_from_mask_kernel<unsigned short>, reinterpret_cast<const unsigned short*>(d_ids));
+            else launch(emit_from_mask_kernel<unsigned>, reinterpret_cast<const unsigned*>(d_ids));
+        }
         vd_time_end(ctx);
         VD_HIP_CHECK(ctx, hipGetLastError());
         return VD_OK;
@@ -1688,10 +1627,7 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
                            d_out, d_out_count, d_tile_count);
         if (rc) return rc;
         vd_time_end(ctx);
-        if (pad_tail) {
-            unsigned pblocks = (unsigned)ctx->num_cus * 4u;
-            hipLaunchKernelGGL(pad_tail_kernel, dim3(pblocks), dim3(kBlock), 0, ctx->stream, d_out, d_out_count, n_inst);
-        }
+        if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
         VD_HIP_CHECK(ctx, hipGetLastError());
         return VD_OK;
     }
@@ -1719,10 +1655,7 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
     }
 #undef VD_LAUNCH_COMPACT
     vd_time_end(ctx);
-    if (pad_tail) {
-        unsigned blocks = (unsigned)ctx->num_cus * 4u;
-        hipLaunchKernelGGL(pad_tail_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, d_out, d_out_count, n_inst);
-    }
+    if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
@@ -1748,47 +1681,30 @@ int vd_cull_compact_views_dev(VdCtx* ctx, const VdCameraUniform* cameras, uint32
     }
     if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null instances/out");
     if (n_views == 1) return vd_cull_compact_dev(ctx, cameras, d_meshes, n_mesh, d_instances, n_inst, d_out, d_out_counts, pad_tail);
-    const unsigned n_words = (n_inst + 63u) / 64u;
-    const unsigned id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
-    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
-    const size_t mask_off = ((size_t)n_inst * id_bytes + 255) & ~(size_t)255;        // (the expansion reads ids as aligned dwords)
-    const size_t mask_stride = (((size_t)n_words * 8 + 255) & ~(size_t)255) / 8;      // words between two views' masks
-    const size_t count_stride = ((size_t)n_mt + 3) & ~(size_t)3;                      // entries: whole 16-byte groups (tile_prefix_partial)
-    const size_t counts_off = mask_off + (size_t)n_views * mask_stride * 8;
-    const size_t need = counts_off + (size_t)n_views * count_stride * 4 + 512;
-    int rc = vd_ensure(ctx, &ctx->views_scratch, &ctx->views_scratch_bytes, need);
+    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, n_views);
+    int rc = vd_ensure(ctx, &ctx->views_scratch, &ctx->views_scratch_bytes, p.need);
     if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->views_scratch);
-    void* d_ids = base;
-    vd_u64* d_mask = reinterpret_cast<vd_u64*>(base + mask_off);
-    unsigned* d_counts = reinterpret_cast<unsigned*>(base + counts_off);
+    void* d_ids = p.ids(ctx->views_scratch);
+    vd_u64* d_mask = p.mask(ctx->views_scratch);
+    unsigned* d_counts = p.counts(ctx->views_scratch);
     ViewCameras cams;
     memset(&cams, 0, sizeof(cams));
     for (uint32_t v = 0; v < n_views; ++v) cams.cam[v] = make_cam(cameras + v);
     vd_time_begin(ctx);
-    unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
-#define VD_VIEWS(IdT)                                                                                              \
-    hipLaunchKernelGGL(cull_mask_views_kernel<IdT>, dim3(mb), dim3(kBlock),                                        \
-                       kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
-                       ctx->stream, cams, n_views, d_meshes, n_mesh, d_instances, n_inst, d_mask, mask_stride,     \
-                       reinterpret_cast<IdT*>(d_ids), d_counts, (unsigned)count_stride, n_mt)
-    if (id_bytes == 1u) VD_VIEWS(unsigned char);
-    else if (id_bytes == 2u) VD_VIEWS(unsigned short);
-    else VD_VIEWS(unsigned);
-#undef VD_VIEWS
+    vd_dispatch_id(p.id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        hipLaunchKernelGGL(cull_mask_views_kernel<IdT>, dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, cams, n_views, d_meshes, n_mesh,
+                           d_instances, n_inst, d_mask, p.mask_stride, reinterpret_cast<IdT*>(d_ids), d_counts, (unsigned)p.count_stride, p.n_mt);
+    });
     vd_time_mid(ctx);
     for (uint32_t v = 0; v < n_views; ++v) {
-        rc = launch_expand(ctx, d_mask + (size_t)v * mask_stride, n_words, n_words, n_inst, n_inst, 0u, d_ids, id_bytes, d_meshes, n_mesh,
-                           d_out + (size_t)v * out_stride, d_out_counts + v, d_counts + (size_t)v * count_stride);
+        rc = launch_expand(ctx, d_mask + (size_t)v * p.mask_stride, p.n_words, p.n_words, n_inst, n_inst, 0u, d_ids, p.id_bytes, d_meshes, n_mesh,
+                           d_out + (size_t)v * out_stride, d_out_counts + v, d_counts + (size_t)v * p.count_stride);
         if (rc) return rc;
     }
     vd_time_end(ctx);
-    if (pad_tail) {
-        const unsigned pblocks = (unsigned)ctx->num_cus * 4u;
-        for (uint32_t v = 0; v < n_views; ++v)
-            hipLaunchKernelGGL(pad_tail_kernel, dim3(pblocks), dim3(kBlock), 0, ctx->stream, d_out + (size_t)v * out_stride, d_out_counts + v, n_inst);
-    }
+    if (pad_tail)
+        for (uint32_t v = 0; v < n_views; ++v) launch_pad_tail(ctx, d_out + (size_t)v * out_stride, d_out_counts + v, n_inst);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
@@ -1823,54 +1739,32 @@ static int cull_occ_list(VdCtx* ctx, OccMode mode, const char* name, const VdCam
     if (prev && !d_prev) VD_OCC_FAIL("null visibility mask");
     if (mode == kOccLate && !d_visible_out) VD_OCC_FAIL("null visibility mask (out)");
 #undef VD_OCC_FAIL
-    const unsigned n_words = (n_inst + 63u) / 64u;
-    const unsigned id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
-    const unsigned n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
-    const size_t mask_off = ((size_t)n_inst * id_bytes + 255) & ~(size_t)255;        // (the expansion reads ids as aligned dwords)
-    const size_t counts_off = mask_off + (((size_t)n_words * 8 + 255) & ~(size_t)255);
-    const size_t need = counts_off + (((size_t)n_mt + 3) & ~(size_t)3) * 4 + 512;    // whole 16-byte groups of counts (tile_prefix_partial)
-    int rc = vd_ensure(ctx, &ctx->occ_scratch, &ctx->occ_scratch_bytes, need);
+    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u);
+    int rc = vd_ensure(ctx, &ctx->occ_scratch, &ctx->occ_scratch_bytes, p.need);
     if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->occ_scratch);
-    void* d_ids = base;
-    vd_u64* d_mask = reinterpret_cast<vd_u64*>(base + mask_off);
-    unsigned* d_counts = reinterpret_cast<unsigned*>(base + counts_off);
+    void* d_ids = p.ids(ctx->occ_scratch);
+    vd_u64* d_mask = p.mask(ctx->occ_scratch);
+    unsigned* d_counts = p.counts(ctx->occ_scratch);
     OccProj proj = {};
     HizView hz = {};
-    if (hiz) {
-        const float* P = camera->projection;
-        proj.p00 = P[0]; proj.p11 = P[5]; proj.p20 = P[8]; proj.p21 = P[9]; proj.p22 = P[10]; proj.p32 = P[14];
-        hz.base = d_pyramid; hz.width = width; hz.height = height; hz.n_levels = L.n_levels;
-        for (int k = 0; k < 17; ++k) hz.off[k] = L.level_offset[k];
-    }
+    if (hiz) { proj = make_proj(camera); hz = make_hiz(d_pyramid, width, height, L); }
     vd_time_begin(ctx);
-    unsigned mb = (n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (mb > (unsigned)ctx->num_cus * 3u) mb = (unsigned)ctx->num_cus * 3u;
-#define VD_OCC(IdT, H, P)                                                                                          \
-    hipLaunchKernelGGL((cull_mask_occ_kernel<IdT, H, P>), dim3(mb), dim3(kBlock),                                  \
-                       kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * (int)sizeof(IdT)),                     \
-                       ctx->stream, make_cam(camera), proj, hz, d_meshes, n_mesh, d_instances, n_inst, d_mask,     \
-                       reinterpret_cast<const vd_u64*>(d_prev), reinterpret_cast<vd_u64*>(d_visible_out),          \
-                       reinterpret_cast<IdT*>(d_ids), d_counts, n_mt)
-#define VD_OCC_MODE(IdT)                                                                                           \
-    do {                                                                                                           \
-        if (mode == kOccHiz) VD_OCC(IdT, true, false);                                                             \
-        else if (mode == kOccEarly) VD_OCC(IdT, false, true);                                                      \
-        else VD_OCC(IdT, true, true);                                                                              \
-    } while (0)
-    if (id_bytes == 1u) VD_OCC_MODE(unsigned char);
-    else if (id_bytes == 2u) VD_OCC_MODE(unsigned short);
-    else VD_OCC_MODE(unsigned);
-#undef VD_OCC_MODE
-#undef VD_OCC
+    vd_dispatch_id(p.id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, make_cam(camera), proj, hz, d_meshes, n_mesh, d_instances,
+                               n_inst, d_mask, reinterpret_cast<const vd_u64*>(d_prev), reinterpret_cast<vd_u64*>(d_visible_out),
+                               reinterpret_cast<IdT*>(d_ids), d_counts, p.n_mt);
+        };
+        if (mode == kOccHiz) launch(cull_mask_occ_kernel<IdT, true, false>);
+        else if (mode == kOccEarly) launch(cull_mask_occ_kernel<IdT, false, true>);
+        else launch(cull_mask_occ_kernel<IdT, true, true>);
+    });
     vd_time_mid(ctx);
-    rc = launch_expand(ctx, d_mask, n_words, n_words, n_inst, n_inst, 0u, d_ids, id_bytes, d_meshes, n_mesh, d_out, d_out_count, d_counts);
+    rc = launch_expand(ctx, d_mask, p.n_words, p.n_words, n_inst, n_inst, 0u, d_ids, p.id_bytes, d_meshes, n_mesh, d_out, d_out_count, d_counts);
     if (rc) return rc;
     vd_time_end(ctx);
-    if (pad_tail) {
-        const unsigned pblocks = (unsigned)ctx->num_cus * 4u;
-        hipLaunchKernelGGL(pad_tail_kernel, dim3(pblocks), dim3(kBlock), 0, ctx->stream, d_out, d_out_count, n_inst);
-    }
+    if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
@@ -1912,8 +1806,8 @@ int vd_cull_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
     const unsigned cap = (unsigned)ctx->num_cus * 4u;
     if (blocks > cap) blocks = cap;
     vd_time_begin(ctx);
-    hipLaunchKernelGGL(cull_mask_kernel<unsigned>, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream, make_cam(camera),
-                       d_meshes, n_mesh, d_instances, n_inst, reinterpret_cast<vd_u64*>(d_mask), (unsigned*)nullptr, n_wave_tiles);
+    hipLaunchKernelGGL(cull_mask_kernel, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream, make_cam(camera),
+                       d_meshes, n_mesh, d_instances, n_inst, reinterpret_cast<vd_u64*>(d_mask), n_wave_tiles);
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
@@ -1931,19 +1825,13 @@ int vd_occlusion_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMes
         VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_occlusion_mask: projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)");
     if (n_inst == 0) return VD_OK;
     if (!d_instances || !d_mask_in || !d_mask_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_occlusion_mask: null instances/masks");
-    OccCamera oc;
-    for (int k = 0; k < 16; ++k) oc.view[k] = camera->view[k];
-    const float* P = camera->projection;
-    oc.p00 = P[0]; oc.p11 = P[5]; oc.p20 = P[8]; oc.p21 = P[9]; oc.p22 = P[10]; oc.p32 = P[14]; oc.znear = camera->znear;
-    HizView hz;
-    hz.base = d_pyramid; hz.width = width; hz.height = height; hz.n_levels = L.n_levels;
-    for (int k = 0; k < 17; ++k) hz.off[k] = L.level_offset[k];
     const unsigned n_wave_tiles = (n_inst + kWave - 1) / kWave;
     unsigned blocks = (n_wave_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned cap = (unsigned)ctx->num_cus * 8u;
     if (blocks > cap) blocks = cap;
     vd_time_begin(ctx);
-    hipLaunchKernelGGL(occlusion_mask_kernel, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream, oc, hz, d_meshes, n_mesh,
+    hipLaunchKernelGGL(occlusion_mask_kernel, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream, make_cam(camera),
+                       make_proj(camera), make_hiz(d_pyramid, width, height, L), d_meshes, n_mesh,
                        d_instances, n_inst, reinterpret_cast<const vd_u64*>(d_mask_in), reinterpret_cast<vd_u64*>(d_mask_out), n_wave_tiles);
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
@@ -2007,10 +1895,11 @@ int vd_indices_to_draws_dev(VdCtx* ctx, const uint32_t* d_indices, uint32_t n_in
     unsigned blocks = (n_indices + kBlock - 1) / kBlock;
     if (blocks > (unsigned)ctx->num_cus * 16u) blocks = (unsigned)ctx->num_cus * 16u;
     vd_time_begin(ctx);
-#define VD_I2D(IdT) hipLaunchKernelGGL(indices_to_draws_kernel<IdT>, dim3(blocks), dim3(kBlock), 0, ctx->stream, d_indices, n_indices,   \
-                                       reinterpret_cast<const IdT*>(d_mesh_ids), n_total, d_meshes, n_mesh, d_out)
-    if (id_bytes == 1u) VD_I2D(unsigned char); else if (id_bytes == 2u) VD_I2D(unsigned short); else VD_I2D(unsigned);
-#undef VD_I2D
+    vd_dispatch_id(id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        hipLaunchKernelGGL(indices_to_draws_kernel<IdT>, dim3(blocks), dim3(kBlock), 0, ctx->stream, d_indices, n_indices,
+                           reinterpret_cast<const IdT*>(d_mesh_ids), n_total, d_meshes, n_mesh, d_out);
+    });
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;

@@ -112,6 +112,15 @@ extern "C" __attribute__((visibility("hidden"))) int launch_mask_pass(VdCtx* ctx
                                                                       const VdInstance* d_instances, uint32_t n_inst, unsigned long long** out_mask, void** out_ids,
                                                                       unsigned* out_id_bytes, unsigned** out_tile_count);
 
+// Calls f with a value of the mesh-id type of that width - unsigned char, unsigned short or unsigned: the one place
+// where an id width (1, 2 or 4 bytes; checked by the caller) picks a kernel instantiation.
+//   vd_dispatch_id(id_bytes, [&](auto id) { using IdT = decltype(id); hipLaunchKernelGGL(some_kernel<IdT>, ...); });
+template <typename F> static inline void vd_dispatch_id(unsigned id_bytes, F&& f) {
+    if (id_bytes == 1u) f((unsigned char)0);
+    else if (id_bytes == 2u) f((unsigned short)0);
+    else f(0u);
+}
+
 static inline void vd_time_begin(VdCtx* ctx) {
     ctx->timed_mid = false;
     if (ctx->timing_enabled) (void)hipEventRecord(ctx->ev_start, ctx->stream);
