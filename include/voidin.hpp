@@ -14,6 +14,7 @@
 // vd_last_error text — nothing aborts.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -126,6 +127,12 @@ struct Dist {
 
 struct Bvh {
     std::vector<BvhNode> nodes;   // `pub nodes: Vec<BvhNode>` (blas.rs:206-208)
+    // NEW (voidin_abi.h "BLAS refit"): same topology, boxes recomputed for moved vertices; `indices` as build() permuted them.
+    // refit(build(x), x) == build(x) bit for bit; left_first / count are not touched.
+    void refit(const Gpu& gpu, const Vec3* vertices, size_t n_vertices, const UVec3* indices, size_t n_triangles) {
+        gpu.check(vd_bvh_refit(gpu.ctx(), &vertices->x, (uint32_t)n_vertices, &indices->x, (uint32_t)n_triangles, nodes.data(),
+                               (uint32_t)nodes.size()));
+    }
     // `Bvh::traverse_iter(&self, &[Vec3], &[UVec3], Ray) -> Dist` (blas.rs:247-295), for a batch of rays
     std::vector<Dist> traverse_iter(const Gpu& gpu, const Vec3* vertices, size_t n_vertices, const UVec3* indices, size_t n_triangles,
                                     const std::vector<VdRay>& rays) const {
@@ -226,13 +233,7 @@ class MeshPool {
         const uint32_t base_index = (uint32_t)indices.size();
         indices.insert(indices.end(), mesh.indices, mesh.indices + mesh.n_indices);
         MeshInfo info{};
-        // calculate_bounds (mesh/mod.rs:22-27): fold from (+inf, -inf)
-        float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-        for (size_t i = 0; i < mesh.n_vertices; ++i) {
-            const float p[3] = {mesh.vertices[i].x, mesh.vertices[i].y, mesh.vertices[i].z};
-            for (int k = 0; k < 3; ++k) { mn[k] = p[k] < mn[k] ? p[k] : mn[k]; mx[k] = p[k] > mx[k] ? p[k] : mx[k]; }
-        }
-        std::memcpy(info.min, mn, 12); std::memcpy(info.max, mx, 12);
+        calculate_bounds(mesh.vertices, mesh.n_vertices, info);
         info.index_count = (uint32_t)mesh.n_indices;
         info.base_index = base_index;
         info.vertex_offset = (int32_t)vertex_offset;
@@ -265,12 +266,7 @@ class MeshPool {
         for (size_t m = 0; m < n_meshes; ++m) {
             const MeshRef& mesh = meshes[m];
             MeshInfo info{};
-            float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-            for (size_t i = 0; i < mesh.n_vertices; ++i) {
-                const float p[3] = {mesh.vertices[i].x, mesh.vertices[i].y, mesh.vertices[i].z};
-                for (int k = 0; k < 3; ++k) { mn[k] = p[k] < mn[k] ? p[k] : mn[k]; mx[k] = p[k] > mx[k] ? p[k] : mx[k]; }
-            }
-            std::memcpy(info.min, mn, 12); std::memcpy(info.max, mx, 12);
+            calculate_bounds(mesh.vertices, mesh.n_vertices, info);
             info.index_count = (uint32_t)mesh.n_indices;
             info.base_index = (uint32_t)indices.size();
             info.vertex_offset = (int32_t)vertices.size();
@@ -280,6 +276,22 @@ class MeshPool {
             mesh_info_cpu.push_back(info);
         }
         return first_id;
+    }
+
+    // NEW (voidin_abi.h "BLAS refit"): a mesh deformed - same vertex count, same indices.  The pool's copy of the positions
+    // is replaced, the mesh's BLAS is refitted in place (topology and permuted indices kept) and MeshInfo.min / max become
+    // calculate_bounds(positions) again (mesh/mod.rs:22-27), which generate_tlas / Tlas::refit and the cull read.
+    void update_vertices(uint32_t mesh_id, const Vec3* positions, size_t n_positions) {
+        if (mesh_id >= mesh_info_cpu.size()) throw Error(VD_ERR_INVALID_ARG, "MeshPool::update_vertices: no such mesh");
+        MeshInfo& info = mesh_info_cpu[mesh_id];
+        const bool last = mesh_id + 1 == mesh_info_cpu.size();                 // meshes lie in the pool in MeshId order
+        const size_t v0 = (size_t)info.vertex_offset, v1 = last ? vertices.size() : (size_t)mesh_info_cpu[mesh_id + 1].vertex_offset;
+        const size_t b0 = info.bvh_index, b1 = last ? bvh_nodes.size() : (size_t)mesh_info_cpu[mesh_id + 1].bvh_index;
+        if (n_positions != v1 - v0) throw Error(VD_ERR_INVALID_ARG, "MeshPool::update_vertices: vertex count differs from the mesh's");
+        gpu_.check(vd_bvh_refit(gpu_.ctx(), &positions->x, (uint32_t)n_positions, indices.data() + info.base_index, info.index_count / 3,
+                                bvh_nodes.data() + b0, (uint32_t)(b1 - b0)));
+        std::copy(positions, positions + n_positions, vertices.begin() + (std::ptrdiff_t)v0);
+        calculate_bounds(positions, n_positions, info);
     }
 
     // MeshPool::generate_tlas (mesh/mod.rs:279-286)
@@ -300,6 +312,16 @@ class MeshPool {
     }
 
    private:
+    // calculate_bounds (mesh/mod.rs:22-27): fold from (+inf, -inf), into info.min / info.max
+    static void calculate_bounds(const Vec3* positions, size_t n, MeshInfo& info) {
+        float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        for (size_t i = 0; i < n; ++i) {
+            const float p[3] = {positions[i].x, positions[i].y, positions[i].z};
+            for (int k = 0; k < 3; ++k) { mn[k] = p[k] < mn[k] ? p[k] : mn[k]; mx[k] = p[k] > mx[k] ? p[k] : mx[k]; }
+        }
+        std::memcpy(info.min, mn, 12); std::memcpy(info.max, mx, 12);
+    }
+
     const Gpu& gpu_;
 };
 
@@ -548,6 +570,8 @@ class TraceScene {
     // from the instance buffer after the instances moved (compute_update.wgsl:10-28) - 2 = LBVH is the builder for that.
     VdTraceAccelInfo info() const { VdTraceAccelInfo i{}; gpu_.check(vd_trace_accel_info(accel_, &i)); return i; }
     void update() { gpu_.check(vd_trace_accel_update_dev(gpu_.ctx(), accel_)); }
+    // the vertices moved (and the BLAS was refitted): de-index the leaf triangles again; enqueues only
+    void update_geometry() { gpu_.check(vd_trace_accel_update_geometry_dev(gpu_.ctx(), accel_)); }
 
    private:
     const Gpu& gpu_;

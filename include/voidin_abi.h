@@ -207,6 +207,9 @@ typedef enum VdOption {
                                      they would fit LDS (<= 5600 instances); default 1 (A/B)               */
     VD_OPT_BLAS_WIDE_PAYLOAD = 30,/* 1: vd_bvh_build moves the 8-byte payload (what meshes above 2^25 triangles use) at
                                      any size (tests); default 0                                                  */
+    VD_OPT_BLAS_REFIT_FENCES = 31,/* 1: vd_bvh_refit_planned_dev adds an agent-scope release / acquire fence pair around every arrival-counter
+                                     add of its climb, on top of the write-through stores and L1-bypassing loads that carry the boxes
+                                     (same bytes; A/B: profiles/blas_refit.md); default 0                                     */
     VD_OPT_TRACE_SORT = 21,       /* 1: vd_trace* bin the rays first (sorted by origin cell + direction) and hand them
                                      out in that order; results are per ray, so only the order changes.  Default 0:
                                      measured slower on this part                                */
@@ -542,6 +545,56 @@ int vd_bvh_build_batch(VdCtx* ctx, VdBvhBatchItem* items, uint32_t n_items, VdBv
 int vd_bvh_build_batch_dev(VdCtx* ctx, VdBvhBatchItem* items, uint32_t n_items, VdBvhNode* d_packed_nodes,
                            uint64_t packed_cap, uint32_t packed_first, uint32_t* out_packed_end);
 
+/* BLAS refit (NEW, not in the reference): new boxes for a mesh whose VERTICES moved - skinning, morph targets, cloth -
+ * without a rebuild.  The topology (left_first, count) and the index buffer as the build permuted it are kept; every
+ * node's min / max is recomputed.  Every box BvhBuilder writes is `calculate_bounds` over the vertices of the node's
+ * triangles (blas.rs:184-204): a fold from (+1e30, -1e30) with f32::min / max, which ignore a NaN operand (tie rule
+ * -0 < +0).  That min / max is associative and commutative, so an interior box is the union of its children's boxes and
+ *     refit(build(x), x) == build(x)  bit for bit;
+ * after a deformation the tree is the one build(x_old) chose with exact boxes for x_new (valid for every walk here; its
+ * SAH quality is the old split's - rebuild when it has degraded; no heuristic for that is offered).
+ * REWRITTEN: min / max of node 0 and of every node reachable from it; min / max of *mesh_info when an item carries one.
+ * NOT rewritten: left_first, count, the reserved all-zero node 1 (unless a tree refers to it), every byte past n_nodes,
+ * the indices, every other field of the VdMeshInfo.
+ *   mesh_info   optional.  Its min / max become what MeshPool::calculate_bounds gives (crates/pools/src/mesh/mod.rs:22-27):
+ *               the fold over ALL n_vert vertices from (+inf, -inf), NaN ignored - NOT the root box, which starts from
+ *               +-1e30 and sees referenced vertices only.  vd_tlas_refit_dev and the cull read these bounds.
+ *   packed      a mesh packed into a shared node buffer (vd_bvh_build_batch*) is an item whose `nodes` points at its
+ *               out_first_node; node ids stay mesh-local.
+ * vd_bvh_refit_plan_dev      once per topology.  BLOCKS (it copies nodes and indices to the host and validates them, as
+ *                            vd_trace_prepare_dev validates) and derives a parent id and an arrival counter per node and
+ *                            the list of leaves.  The plan keeps the items' POINTERS, not their data: vertices may change
+ *                            freely, nodes' topology and indices may not.  VD_ERR_INVALID_ARG with items[m].status set
+ *                            (no plan is returned) for: an interior node whose children left_first, left_first + 1 are not
+ *                            both in (own id, n_nodes); a node with two parents, or a node other than 0 and the reserved
+ *                            slot 1 with none; a leaf whose range [left_first, left_first + count) leaves [0, n_tri); an
+ *                            index >= n_vert; n_nodes < 1; a null pointer.  Leaves may hold any number of triangles.
+ *                            n_items == 0 is VD_OK: a plan that does nothing.
+ * vd_bvh_refit_planned_dev   ENQUEUES ONE kernel for all items on the context's stream and nothing else - no host read,
+ *                            allocation or memset - so it can be captured into a HIP graph and replayed.  A lane takes a
+ *                            leaf, folds its box and climbs; at each parent the first arriver leaves, the second stores
+ *                            the union and goes on.  No lane waits on another (no spin, no look-back); the counters are
+ *                            back at 0 when the kernel ends, so nothing is cleared between refits.  One refit of a plan at
+ *                            a time (calls on one stream are ordered).
+ * vd_bvh_refit_plan_release  synchronises the stream first (a queued refit reads the plan).
+ * vd_bvh_refit               host pointers, one mesh, synchronous: stage, plan, refit, copy the nodes back.
+ * Per-frame order for a deforming mesh: INTEGRATION.md.  Measured against the rebuild: profiles/blas_refit.md.          */
+typedef struct VdBvhRefitItem {
+    const float*    verts_xyz;   /* n_vert * 3, read at every refit                      */
+    const uint32_t* indices;     /* n_tri * 3, as the build permuted them; never written */
+    VdBvhNode*      nodes;       /* n_nodes; only min / max are rewritten                */
+    VdMeshInfo*     mesh_info;   /* optional: min / max rewritten (mesh/mod.rs:22-27)    */
+    uint32_t        n_vert, n_tri, n_nodes;
+    int32_t         status;      /* written by the plan call                             */
+} VdBvhRefitItem;
+typedef struct VdBvhRefitPlan VdBvhRefitPlan;
+int vd_bvh_refit_plan_dev(VdCtx* ctx, VdBvhRefitItem* items /* host array, device pointers inside */, uint32_t n_items,
+                          VdBvhRefitPlan** out);
+int vd_bvh_refit_planned_dev(VdCtx* ctx, const VdBvhRefitPlan* plan);
+int vd_bvh_refit_plan_release(VdCtx* ctx, VdBvhRefitPlan* plan);
+int vd_bvh_refit(VdCtx* ctx, const float* verts_xyz, uint32_t n_vert, const uint32_t* indices, uint32_t n_tri,
+                 VdBvhNode* nodes_inout, uint32_t n_nodes);
+
 /* ------------------------------------------------------------------------------------ */
 /* TLAS build / refit                                               */
 /* ------------------------------------------------------------------------------------ */
@@ -611,9 +664,10 @@ int vd_trace_dev(VdCtx* ctx, const VdTraceScene* d_scene /* struct on host, poin
  * per triangle in index-buffer (= leaf) order, so that a BLAS leaf is ONE contiguous fetch instead
  * of indices[] -> vertices[] (bvh.wgsl:30-33, 49-53).  Same vertices, same arithmetic: results are
  * bit-identical to vd_trace_dev / vd_trace_any_dev.  The accel holds a copy of the scene struct
- * (the pointers, not the data): rebuild it when vertices / indices / meshes change; instances
- * and TLAS nodes may change freely (they are read through the scene's pointers).  vd_trace_prepare_dev
- * blocks (it validates the index ranges); release with vd_trace_release.                      */
+ * (the pointers, not the data): rebuild it when indices / meshes change; after the VERTICES changed
+ * (and the BLAS was refitted: vd_bvh_refit_planned_dev) vd_trace_accel_update_geometry_dev refreshes the
+ * triangle copy; instances and TLAS nodes may change freely (they are read through the scene's pointers).
+ * vd_trace_prepare_dev blocks (it validates the index ranges); release with vd_trace_release.  */
 typedef struct VdTraceAccel VdTraceAccel;
 int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel** out);
 int vd_trace_release(VdCtx* ctx, VdTraceAccel* accel);
@@ -632,6 +686,10 @@ int vd_trace_accel_info(const VdTraceAccel* accel, VdTraceAccelInfo* out);
  * qualifies; if one does not, the walk goes back to the scene's own top level until an update finds all qualifying again).
  * A no-op for a scene prepared without VD_OPT_TRACE_TIGHT_TLAS: that one walks the host's top level, which the host refits.  */
 int vd_trace_accel_update_dev(VdCtx* ctx, VdTraceAccel* accel);
+/* Re-runs the de-indexing of vd_trace_prepare_dev into the accel's existing triangle array, from the scene's vertex buffer
+ * as it is NOW (a mesh deformed).  Enqueues only: no validation and no read-back - indices and meshes have not changed and
+ * prepare validated them - so it can be captured into a HIP graph.  The BLAS boxes are the caller's: refit them first.    */
+int vd_trace_accel_update_geometry_dev(VdCtx* ctx, VdTraceAccel* accel);
 int vd_trace_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out);
 int vd_trace_any_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays,
                               uint32_t* d_out_hit);

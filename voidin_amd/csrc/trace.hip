@@ -15,7 +15,9 @@
 #include <algorithm>
 #include <new>
 
-// vd_trace_prepare_dev: per-scene data derived once from the six trace buffers
+// vd_trace_prepare_dev: per-scene data derived once from the six trace buffers.  The triangle copy follows the scene's
+// vertex buffer through vd_trace_accel_update_geometry_dev (a mesh deformed: same indices and meshes, new positions), which
+// re-runs the de-indexing into the same array without validating or reading anything back.
 struct VdTraceAccel {
     VdTraceScene scene; float* tris = nullptr;
     // private top level (VD_OPT_TRACE_TIGHT_TLAS): its nodes, which builder made it (1 agglomerative, 2 LBVH), the scene's own top
@@ -1555,6 +1557,18 @@ int vd_trace_accel_update_dev(VdCtx* ctx, VdTraceAccel* accel) {
     if (!accel->tight) return VD_OK;          // the scene's own top level is walked: the host refits that one (vd_tlas_refit_dev)
     ctx->fan_forget(accel->tight);
     return build_tight_tlas(ctx, accel);
+}
+
+int vd_trace_accel_update_geometry_dev(VdCtx* ctx, VdTraceAccel* accel) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx || !accel) return VD_ERR_INVALID_ARG;
+    const VdTraceScene& s = accel->scene;
+    unsigned* d_ignored = reinterpret_cast<unsigned*>(accel->tris + 9 * (size_t)(s.n_indices / 3u));      // the array's slack: prepare validated, nobody reads this word
+    for (unsigned m0 = 0; m0 < s.n_meshes; m0 += 65535u)
+        hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, std::min(s.n_meshes - m0, 65535u)), dim3(256), 0, ctx->stream, s.meshes + m0,
+                           s.vertices, s.indices, s.n_indices, s.n_vertices, accel->tris, d_ignored);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
 }
 
 int vd_trace_release(VdCtx* ctx, VdTraceAccel* accel) {

@@ -273,6 +273,53 @@ class Context:
                                                   packed_cap, packed_first, C.addressof(end)))
         return end.value
 
+    # BLAS refit: new boxes for deformed vertices, same topology (voidin_abi.h "BLAS refit")
+    def bvh_refit(self, verts, indices, nodes) -> np.ndarray:
+        """vd_bvh_refit, host arrays, one mesh: `indices` as the build permuted them; returns the nodes with min / max
+        recomputed for `verts` (refit(build(x), x) == build(x) bit for bit)."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        nodes = np.array(nodes, dtype=abi.BVH_NODE, copy=True)
+        self._chk(self.lib.vd_bvh_refit(self.h, verts.ctypes.data, len(verts), idx.ctypes.data, len(idx) // 3,
+                                        nodes.ctypes.data, len(nodes)))
+        return nodes
+
+    class BvhRefitPlan:
+        """vd_bvh_refit_plan_dev: what a refit needs from the topology of K meshes, derived and validated once.  `items` is an
+        (abi.BvhRefitItem * K) with device pointers (a failed plan leaves the offending item's status set); the plan keeps
+        those pointers, so the caller keeps the tensors alive."""
+
+        def __init__(self, ctx: "Context", items, n_items=None):
+            self.ctx, self.items = ctx, items
+            self.n_items = len(items) if n_items is None else int(n_items)
+            h = C.c_void_p()
+            ctx._chk(ctx.lib.vd_bvh_refit_plan_dev(ctx.h, C.addressof(items) if self.n_items else None, self.n_items, C.byref(h)))
+            self.h = h
+
+        def refit(self):
+            self.ctx.bvh_refit_planned(self)
+
+        def close(self):
+            if getattr(self, "h", None):
+                self.ctx.lib.vd_bvh_refit_plan_release(self.ctx.h, self.h)
+                self.h = None
+
+        def __del__(self):
+            try:
+                self.close()
+            except Exception:
+                pass
+
+    def bvh_refit_plan(self, items, n_items=None) -> "Context.BvhRefitPlan":
+        return Context.BvhRefitPlan(self, items, n_items)
+
+    def bvh_refit_planned(self, plan: "Context.BvhRefitPlan"):
+        """vd_bvh_refit_planned_dev: one kernel for all meshes of the plan, enqueued on the context's stream."""
+        self._chk(self.lib.vd_bvh_refit_planned_dev(self.h, plan.h))
+
+    def bvh_refit_plan_release(self, plan: "Context.BvhRefitPlan"):
+        plan.close()
+
     def bvh_last_build_stats(self) -> dict:
         st = abi.BvhBuildStats()
         self._chk(self.lib.vd_bvh_last_build_stats(self.h, C.byref(st)))
@@ -366,6 +413,11 @@ class Context:
         def update(self):
             """vd_trace_accel_update_dev: rebuild the private top level from the instance buffer as it is now."""
             self.ctx._chk(self.ctx.lib.vd_trace_accel_update_dev(self.ctx.h, self.h))
+
+        def update_geometry(self):
+            """vd_trace_accel_update_geometry_dev: de-index the leaf triangles again from the vertex buffer as it is now
+            (enqueues only; refit the BLAS first)."""
+            self.ctx._chk(self.ctx.lib.vd_trace_accel_update_geometry_dev(self.ctx.h, self.h))
 
         def close(self):
             if getattr(self, "h", None):
@@ -530,6 +582,10 @@ class OcclusionState:
 class Bvh:
     def __init__(self, nodes: np.ndarray):
         self.nodes = nodes
+
+    def refit(self, ctx: Context, vertices: np.ndarray, indices: np.ndarray):
+        """NEW (not in the reference): same topology, boxes recomputed for `vertices`; `indices` as build() left them."""
+        self.nodes = ctx.bvh_refit(vertices, indices, self.nodes)
 
 
 class BvhBuilder:
