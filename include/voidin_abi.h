@@ -210,15 +210,11 @@ typedef enum VdOption {
     VD_OPT_BLAS_REFIT_FENCES = 31,/* 1: vd_bvh_refit_planned_dev adds an agent-scope release / acquire fence pair around every arrival-counter
                                      add of its climb, on top of the write-through stores and L1-bypassing loads that carry the boxes
                                      (same bytes; A/B: profiles/blas_refit.md); default 0                                     */
-    VD_OPT_TRACE_SORT = 21,       /* 1: vd_trace* bin the rays first (sorted by origin cell + direction) and hand them
-                                     out in that order; results are per ray, so only the order changes.  Default 0:
-                                     measured slower on this part                                */
-    VD_OPT_TRACE_SORT_MIN = 22,   /* fewest rays a call bins when VD_OPT_TRACE_SORT is on; default 65536          */
-    VD_OPT_TRACE_CHUNK = 23,      /* 1 (default): idle lanes draw single rays from one counter; >= 64: consecutive
-                                     rays per workgroup in chunks of this size (measured slower: imbalance)      */
+    /* 21, 22, 23 are unassigned: they switched on ray binning and the chunked ray supply, both measured slower and
+       removed.  Like every id below VD_OPT_COUNT_ they are still accepted, and change nothing.     */
     VD_OPT_TRACE_YIELD = 24,      /* lanes of a wave that wait (at a BLAS leaf, or with a finished ray) before the wave
                                      leaves its stepping loop to serve them; default 16                          */
-    VD_OPT_TRACE_WAVES = 25,      /* persistent waves per CU of the single-ray supply (1..24); default 24          */
+    VD_OPT_TRACE_WAVES = 25,      /* persistent waves per CU (1..24); default 24                                  */
     VD_OPT_TRACE_AUTO_PREPARE = 27,/* 1 (default): a vd_trace_dev / vd_trace_any_dev call de-indexes the leaf triangles
                                      itself (what vd_trace_prepare_dev does once per scene) when that is cheap next to
                                      the walk: n_rays * 8 >= triangles <= 2 Mi, at most 65 535 meshes.  The 36 B per

@@ -360,12 +360,13 @@ def test_trace_seeded_scene_vs_oracle(ctx, oracle):
 
 
 @pytest.mark.parametrize("side", [96, 320])
-def test_trace_supply_binning_and_prepared_triangles_are_order_only(ctx, oracle, ctx_options, side):
-    """Round 3: rays are binned (sorted by origin cell and direction), handed to workgroups in chunks of the sorted
-    order, and leaf triangles may come de-indexed from vd_trace_prepare_dev.  All of that changes the ORDER in which rays
-    are walked and where a triangle's vertices are fetched from - never a result: every variant must reproduce the
-    oracle's hit flags / distances, and all variants the same bytes, on a multi-mesh scene
-    (vertex_offset / base_index / bvh_index all non-zero) with degenerate rays mixed in."""
+def test_trace_yield_waves_and_prepared_triangles_are_order_only(ctx, oracle, ctx_options, side):
+    """When a wave leaves its stepping loop to serve waiting lanes (VD_OPT_TRACE_YIELD), how many waves a CU runs
+    (VD_OPT_TRACE_WAVES), and whether leaf triangles come de-indexed - from vd_trace_prepare_dev, or from the call itself
+    (VD_OPT_TRACE_AUTO_PREPARE) - change the ORDER in which rays are walked and where a triangle's vertices are fetched
+    from - never a result: every variant must reproduce the oracle's hit flags / distances, and all variants the same
+    bytes, on a multi-mesh scene (vertex_offset / base_index / bvh_index all non-zero) with duplicate and degenerate
+    rays mixed in."""
     import torch
     meshes_src = [synth.uv_sphere(1.0, 4), synth.knot_mesh(96, 24), synth.triangle_soup(64)]
     V, I, B = [], [], []
@@ -382,7 +383,7 @@ def test_trace_supply_binning_and_prepared_triangles_are_order_only(ctx, oracle,
     inst = synth.instances(300, n_mesh=3, seed=synth.SEED_BASE + 18, extent=50.0, scale_range=(0.5, 3.0))
     tl = ctx.tlas_build(inst, infos)
     rays = synth.primary_rays(synth.camera_uniform(eye=(0, 2.5, 40), pitch_deg=0), side, side)
-    rays = np.concatenate([rays, rays[::7]])                    # duplicates: equal keys in the sort
+    rays = np.concatenate([rays, rays[::7]])                    # duplicates
     rays["dir"][5] = (0, 0, 0); rays["dir"][6] = (np.nan, 1, 0); rays["eye"][7] = (np.inf, 0, 0); rays["dir"][8] = (0, 0, -1)
     rays["eye"][9] = (1e30, -1e30, 0)
     scene = (tl, inst, infos, B, V, I)
@@ -392,14 +393,13 @@ def test_trace_supply_binning_and_prepared_triangles_are_order_only(ctx, oracle,
     d_rays, d_hits = ctx.upload(rays), ctx.empty(len(rays) * 16)
     d_any = torch.zeros(len(rays), dtype=torch.int32, device="cuda")
     first = None
-    variants = [dict(), dict(chunk=64), dict(sort=1, sort_min=1), dict(sort=1, sort_min=1, chunk=64), dict(sort=1, sort_min=1, chunk=4096),
-                dict(sort=1, sort_min=1, chunk=100), dict(chunk=1000),     # default: single rays from one counter, no binning
+    variants = [dict(),                                         # the defaults
                 # when a wave leaves its stepping loop to serve waiting lanes, and how many waves a CU runs
-                {"yield": 4}, {"yield": 64}, {"yield": 64, "chunk": 64}, dict(waves=3),
+                {"yield": 4}, {"yield": 64}, dict(waves=3),
                 # the plain calls de-index the leaves themselves by default; without that they walk the indexed leaves
                 dict(auto_prepare=0), {"auto_prepare": 0, "yield": 4}]
     for opts in variants:
-        for k in ("sort", "sort_min", "chunk", "yield", "waves", "auto_prepare"):
+        for k in ("yield", "waves", "auto_prepare"):
             ctx_options("trace." + k, opts.get(k))
         for prep in (False, True):
             d_hits.zero_(); d_any.fill_(9)

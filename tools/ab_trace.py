@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the traversal on the bench scenes: supply (round-2 single-ray counter / chunks per workgroup), ray binning,
-chunk size, de-indexed leaf triangles.  Every variant's output is compared byte for byte with the first one's.
+"""A/B of the traversal on the stress scene: indexed against de-indexed leaf triangles, the scene's top level against the
+private tight ones; AB_YIELD / AB_FAN / AB_WAVES (comma-separated values) sweep VD_OPT_TRACE_YIELD / _FAN / _WAVES instead.
+Every variant's output is compared byte for byte with the first one's.
     python tools/ab_trace.py [--rays 1024] [--harness]"""
 import argparse, os, sys, time
 import numpy as np, torch
@@ -40,25 +41,21 @@ for _acc, _nm in ((acc_tight, "agglomerative"), (acc_lbvh, "LBVH")):
     print(f"private top level, {_nm}: vd_trace_accel_update_dev (rebuild from the instance buffer, blocking) {min(_t) * 1e3:.3f} ms")
 d_rays, d_hits = ctx.upload(rays), ctx.empty(len(rays) * 16)
 d_any = torch.zeros(len(rays), dtype=torch.int32, device="cuda")
-variants = [("single rays (default)", dict(sort=0, chunk=1), False), ("single rays prep", dict(sort=0, chunk=1), True),
-            ("single rays prep TIGHT TLAS", dict(sort=0, chunk=1), "tight"), ("single rays prep TIGHT TLAS (LBVH)", dict(sort=0, chunk=1), "lbvh"),
-            ("chunk64 nosort", dict(sort=0, chunk=64), False), ("chunk64 nosort prep", dict(sort=0, chunk=64), True),
-             ("chunk64 sort", dict(sort=1, chunk=64), False),
-            ("chunk64 sort prep", dict(sort=1, chunk=64), True), ("chunk256 sort prep", dict(sort=1, chunk=256), True),
-            ("chunk128 sort prep", dict(sort=1, chunk=128), True)]
-if os.environ.get("AB_YIELD"):        # sweep of VD_OPT_TRACE_YIELD on the default supply
-    variants = [("yield %2d%s" % (y, " prep" if pr else ""), dict(sort=0, chunk=1, **{"yield": y}), pr)
+variants = [("single rays (default)", dict(), False), ("single rays prep", dict(), True),
+            ("single rays prep TIGHT TLAS", dict(), "tight"), ("single rays prep TIGHT TLAS (LBVH)", dict(), "lbvh")]
+if os.environ.get("AB_YIELD"):        # sweep of VD_OPT_TRACE_YIELD
+    variants = [("yield %2d%s" % (y, " prep" if pr else ""), {"yield": y}, pr)
                 for y in [int(v) for v in os.environ["AB_YIELD"].split(",")] for pr in (False, True)]
-if os.environ.get("AB_FAN"):          # sweep of VD_OPT_TRACE_FAN (launches per call) on the default supply
-    variants = [("fan %d%s" % (r, " prep" if pr else ""), dict(sort=0, chunk=1, fan=r), pr)
+if os.environ.get("AB_FAN"):          # sweep of VD_OPT_TRACE_FAN (launches per call)
+    variants = [("fan %d%s" % (r, " prep" if pr else ""), dict(fan=r), pr)
                 for r in [int(v) for v in os.environ["AB_FAN"].split(",")] for pr in (False, True)]
-if os.environ.get("AB_WAVES"):        # sweep of VD_OPT_TRACE_WAVES on the default supply
-    variants = [("waves/CU %2d%s" % (w, " prep" if pr else ""), dict(sort=0, chunk=1, waves=w), pr)
+if os.environ.get("AB_WAVES"):        # sweep of VD_OPT_TRACE_WAVES
+    variants = [("waves/CU %2d%s" % (w, " prep" if pr else ""), dict(waves=w), pr)
                 for w in [int(v) for v in os.environ["AB_WAVES"].split(",")] for pr in (False, True)]
 ref_bytes = ref_any = None
 ctx.set_timing(True)
 for name, opts, prep in variants:
-    for k in ("sort", "chunk", "yield", "waves", "fan"):
+    for k in ("yield", "waves", "fan"):
         ctx.set_option("trace." + k, opts.get(k, -1))
     t_cl, t_any = [], []
     acc_v = acc_tight if prep == "tight" else (acc_lbvh if prep == "lbvh" else acc)

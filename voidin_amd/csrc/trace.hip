@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <new>
+#include <type_traits>
 
 // vd_trace_prepare_dev: per-scene data derived once from the six trace buffers.  The triangle copy follows the scene's
 // vertex buffer through vd_trace_accel_update_geometry_dev (a mesh deformed: same indices and meshes, new positions), which
@@ -88,13 +89,10 @@ struct Scene {
     unsigned deep_cap = 0;          // ... and how many there are per lane
 };
 
-// Where a wave's rays come from.  `order` (nullptr = identity) lists the ray ids in the order they are handed out (the
-// optional binning pre-pass sorts them by origin cell and direction).  chunk == 1 (default): idle lanes draw single
-// rays from one global counter.  chunk >= 64: rays are handed out in CHUNKS of consecutive positions, a workgroup (several
-// waves = one CU's L1) working one chunk off before it takes the next, so that the lanes of a wave and the waves of a CU
-// sit in a small window of the order.  Both were built to test whether locality pays on this part; it does not
-// (launch_trace), and the defaults are the round-2 supply.
-// Fan-out (single-ray supply, see kFan*): one job = one TLAS subtree of one ray.  48 bytes: as a pending job {ray, the distance
+// Where a wave's rays come from: idle lanes draw single positions 0 .. n_rays - 1 from the global counter `next`, and
+// position p is ray order[p] (nullptr = identity: the first pass; the deep second pass hands out its overflow list).
+// Handing the rays out in a sorted order or in per-workgroup chunks was tried and lost: DESIGN.md 3.5.
+// Fan-out (see kFan*): one job = one TLAS subtree of one ray.  48 bytes: as a pending job {ray, the distance
 // found so far, ray id, order key, the subtree as a stack-entry word}; when finished the same slot holds the job's result.
 struct FanJob { float ex, ey, ez, dx, dy, dz; float lim; unsigned ray_id, key, node, state, tri; };
 static_assert(sizeof(FanJob) == 48, "FanJob is three uint4");
@@ -105,7 +103,7 @@ struct Fan {                       // one launch's place in the fan-out (all nul
     unsigned long long* best;                                      // per ray: min over finished jobs of {distance bits, key}
     unsigned below, level;                                         // fan out when fewer than `below` rays are alive in a draining wave (0: never); key digit position
 };
-struct RaySource { const unsigned* order; unsigned n_rays, chunk, n_chunks; unsigned* next_chunk; Fan fan = {}; };
+struct RaySource { const unsigned* order; unsigned n_rays; unsigned* next; Fan fan = {}; };
 
 // Fan-out.  The stress scene's call is as long as its longest rays - 8 500 dependent steps of ~1.4 us against a mean of 517 -
 // and for most of it a few waves each nurse a handful of such rays while the rest of the machine is idle (the "relay" that
@@ -124,23 +122,11 @@ struct RaySource { const unsigned* order; unsigned n_rays, chunk, n_chunks; unsi
 // records {distance bits, key} with an atomic min per ray; vd_fan_resolve_kernel lets the job that holds the minimum write the
 // ray's record.  (The reference's root is visited twice - tlas.rs:59 merges the true root with itself - and the second
 // visit can only tie: its job is not created.)
-#ifndef VD_FAN_PHASES
-#define VD_FAN_PHASES 3
-#endif
-#ifndef VD_FAN_BELOW
-#define VD_FAN_BELOW 32
-#endif
-#ifndef VD_FAN_GRACE
-#define VD_FAN_GRACE 128
-#endif
-#ifndef VD_FAN_AGE
-#define VD_FAN_AGE 512
-#endif
-constexpr unsigned kFanPhases = VD_FAN_PHASES;   // launches per call (VD_OPT_TRACE_FAN; 1 = one launch, no fan-out)
-constexpr unsigned kFanBelow = VD_FAN_BELOW;     // live rays below which a draining wave fans its rays out at once
-constexpr unsigned kFanGrace = VD_FAN_GRACE;     // stepping iterations after the last draw before a wave fans out whatever is still alive
+constexpr unsigned kFanPhases = 3;            // launches per call (VD_OPT_TRACE_FAN; 1 = one launch, no fan-out)
+constexpr unsigned kFanBelow = 32;            // live rays below which a draining wave fans its rays out at once
+constexpr unsigned kFanGrace = 128;           // stepping iterations after the last draw before a wave fans out whatever is still alive
 constexpr unsigned kFanAgain = 8;             // ... and between two looks at the rays that were inside an instance at the time
-constexpr unsigned kFanAge = VD_FAN_AGE;      // only rays that have been stepping for at least this many of the wave's iterations fan out (0: all)
+constexpr unsigned kFanAge = 512;             // only rays that have been stepping for at least this many of the wave's iterations fan out (0: all)
 
 // A fixed grid of waves; a lane whose ray is finished draws the next ray from a counter, so a wave stays full while
 // rays of very different cost (a few node visits to thousands) pass through it.  To let a lane restart at any point the
@@ -155,13 +141,11 @@ constexpr unsigned kFanAge = VD_FAN_AGE;      // only rays that have been steppi
 constexpr long long kYieldDefault = 1;   // see the stepping loop (sweep in profiles/r03_ab_trace.log: 1 is best)
 constexpr unsigned kRefillBelow = 56;   // draw new rays when fewer than this many lanes are busy
 constexpr unsigned kWavesPerCu = 24;    // persistent grid = what is resident (6 waves per SIMD at <= 84 VGPRs: the walk holds ~76, and with 72 it spilled): no wave starts late
-constexpr int kWgWaves = 6;             // waves per workgroup of the chunked form: 4 workgroups per CU
 // PREP: leaf triangles come de-indexed from Scene::tris (one contiguous fetch instead of indices[] -> verts[]).
-// CHUNKS = false (default): idle lanes draw single rays from one global counter, one wave per workgroup - the round-2
-// form, kept apart so that it carries none of the chunk machinery (inside multi-wave workgroups with the chunk state live
-// the closest-hit walk spilled registers and lost 10 %: 38.5 -> 34.5 Mrays/s, same-session A/B against the round-2 library).
+// FAN: the fan-out's code is compiled in (src.fan says what this launch hands out and whether it may append jobs).
 // DEEP: the second pass over the rays whose stack overflowed (launch_trace) - same walk, entries 128.. in s.deep.
-template <bool ANY, bool PREP, bool CHUNKS, bool FAN = false, bool DEEP = false>
+// Every kernel that calls this runs one wave per workgroup.
+template <bool ANY, bool PREP, bool FAN = false, bool DEEP = false>
 __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restrict__ rays, const RaySource& src, VdHit* __restrict__ out,
                                            unsigned* __restrict__ out_any, unsigned* __restrict__ overflow) {
     const unsigned lane = threadIdx.x & 63u;
@@ -172,17 +156,10 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
     unsigned drain_iters = 0;              // wave-uniform: stepping iterations since this wave found the supply empty
     unsigned wave_iters = 0;               // wave-uniform: stepping iterations of this wave (FAN: a ray's age = now - s_born[lane])
     __shared__ unsigned s_born[(FAN && kFanAge) ? 64 : 1];
-    __shared__ vd_u64 s_word;              // chunked supply: {next, end} positions of the workgroup's current chunk
-    unsigned p_next = 0, p_end = 0;        // a chunk this wave could not publish (another wave's was installed first)
-    if (CHUNKS) {
-        if (threadIdx.x == 0) s_word = 0ull;
-        __syncthreads();
-    }
     // The first kLdsStack entries of a ray's stack live in LDS ([slot][lane]: a lane always hits its own bank), the rest in
     // the private array.  A private array indexed by a per-lane depth is scratch memory, and 64 lanes at 64 depths are 64
     // lines per push and per pop - as many as the node fetch itself, out of the same L1 miss bandwidth that bounds the walk.
-    __shared__ unsigned s_stack[CHUNKS ? kWgWaves : 1][kLdsStack][64];
-    const unsigned wv = CHUNKS ? (threadIdx.x >> 6) : 0u;     // (indexed, not through a pointer: a 64-bit pointer was spilled and reloaded at every push)
+    __shared__ unsigned s_stack[kLdsStack][64];       // (indexed, not through a pointer: a 64-bit pointer was spilled and reloaded at every push)
     unsigned stack[2 * kStack - kLdsStack];  // BLAS entries sit above the TLAS entries of the same ray
     const size_t deep_base = DEEP ? (size_t)blockIdx.x * s.deep_cap * 64u + lane : 0u;       // one wave per workgroup in the DEEP kernel
     Ray world, ray;                        // `ray` is the active one (object space inside an instance)
@@ -210,7 +187,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
         --head;
         unsigned w;
         if (DEEP && head >= 2u * (unsigned)kStack) w = s.deep[deep_base + (size_t)(head - 2u * (unsigned)kStack) * 64u];
-        else w = head < (unsigned)kLdsStack ? s_stack[wv][head][lane] : stack[head - (unsigned)kLdsStack];
+        else w = head < (unsigned)kLdsStack ? s_stack[head][lane] : stack[head - (unsigned)kLdsStack];
         if (((st & kInBlas) != 0u)) cn = make_uint2(w & 0x3fffffffu, w >> 30);
         else cn = (w & 0xffffu) ? make_uint2(w, 0xffffffffu) : make_uint2(0u, w >> 16);
     };
@@ -240,42 +217,16 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
         if (!exhausted && (unsigned)__popcll(busy_mask) < kRefillBelow) {
             const unsigned long long idle = ~busy_mask;
             const unsigned want = (unsigned)__popcll(idle);
-            unsigned base = 0, got = 0, done = 0;
-            if (!CHUNKS) {                                          // single rays from one global counter: the finest balance
-                if (lane == 0) base = atomicAdd(src.next_chunk, want);
-                base = __shfl(base, 0);
-                got = want;                                         // ids are checked against n_rays below (limit)
-                done = base + want >= n_rays ? 1u : 0u;
-            } else {
-                if (lane == 0) {
-                    if (p_next < p_end) { got = min(want, p_end - p_next); base = p_next; p_next += got; }
-                    else for (;;) {
-                        const vd_u64 old = __hip_atomic_load(&s_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        const unsigned nx = (unsigned)old, en = (unsigned)(old >> 32);
-                        if (nx < en) {                                  // the workgroup's chunk still has rays
-                            const unsigned take = min(want, en - nx);
-                            vd_u64 expect = old;
-                            if (__hip_atomic_compare_exchange_strong(&s_word, &expect, ((vd_u64)en << 32) | (nx + take), __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                                     __HIP_MEMORY_SCOPE_WORKGROUP)) { base = nx; got = take; break; }
-                            continue;
-                        }
-                        const unsigned c = atomicAdd(src.next_chunk, 1u);
-                        if (c >= src.n_chunks) { done = 1u; break; }
-                        const unsigned b = c * src.chunk, e = min(b + src.chunk, n_rays);
-                        base = b; got = min(want, e - b);
-                        vd_u64 expect = old;                            // the rest is for the whole workgroup - unless another wave installed a chunk meanwhile
-                        if (!__hip_atomic_compare_exchange_strong(&s_word, &expect, ((vd_u64)e << 32) | (b + got), __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                                  __HIP_MEMORY_SCOPE_WORKGROUP)) { p_next = b + got; p_end = e; }
-                        break;
-                    }
-                }
-                base = __shfl(base, 0); got = __shfl(got, 0); done = __shfl(done, 0);
-            }
+            unsigned base = 0, end = 0, done = 0;                   // single positions from one global counter: the finest balance
+            if (lane == 0) base = atomicAdd(src.next, want);
+            base = __shfl(base, 0);
+            end = base + want;                                      // positions are checked against n_rays below (limit)
+            done = end >= n_rays ? 1u : 0u;
             // the position drawn is checked against an explicit upper limit (`pos < limit`), never through a difference: written as
             // `got = base < n_rays ? min(want, n_rays - base) : 0; if (k < got)` the one-wave kernel was compiled WITHOUT the
             // `base < n_rays` guard (v_sub_u32 + v_min_u32, no clamp, no select: profiles/r03_trace_guard_isa.txt) and every
             // draw past the end took `want` rays from beyond the array
-            const unsigned limit = CHUNKS ? base + got : n_rays;
+            const unsigned limit = n_rays;
             if (!((st & kBusy) != 0u)) {
                 const unsigned pos = base + vd_mbcnt(idle);
                 if (from_jobs && pos < limit && pos >= base) {
@@ -331,7 +282,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                     const unsigned lr = s.tlas[0].left_right, l = lr & 0xffffu;
                     if (lr != 0u && l == (lr >> 16)) { const unsigned w2 = s.tlas[l].left_right; dup_word = w2 != 0u ? w2 : (l << 16); }
                 }
-                const bool dup = can && head != 0u && dup_word != 0u && (ray_id & 0x80000000u) == 0u && s_stack[wv][0][lane] == dup_word;
+                const bool dup = can && head != 0u && dup_word != 0u && (ray_id & 0x80000000u) == 0u && s_stack[0][lane] == dup_word;
                 const unsigned n_ent = can ? head - (dup ? 1u : 0u) : 0u;
                 const unsigned m = can ? n_ent + 2u : 0u;           // the result so far, the node it is at, the stack entries
                 unsigned incl = m;
@@ -372,7 +323,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                         O[5] = make_uint4(pkey | (1u << shift), cn.x != 0u ? cn.x : (cn.y << 16), FAN_PENDING, 0u);
                         for (unsigned e = 0; e < n_ent; ++e) {
                             const unsigned at = head - 1u - e;
-                            const unsigned w = at < (unsigned)kLdsStack ? s_stack[wv][at][lane] : stack[at - (unsigned)kLdsStack];
+                            const unsigned w = at < (unsigned)kLdsStack ? s_stack[at][lane] : stack[at - (unsigned)kLdsStack];
                             O[6u + 3u * e] = r0; O[7u + 3u * e] = make_uint4(dyb, dzb, limb, rid);
                             O[8u + 3u * e] = make_uint4(pkey | ((2u + e) << shift), w, FAN_PENDING, 0u);
                         }
@@ -513,7 +464,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                 const unsigned w_blas = far.x | (far.y << 30), w_tlas = far.x != 0u ? far.x : (far.y << 16);
                 const unsigned w = blas_now ? w_blas : w_tlas;
                 if (DEEP && head >= 2u * (unsigned)kStack) s.deep[deep_base + (size_t)(head - 2u * (unsigned)kStack) * 64u] = w;
-                else if (head < (unsigned)kLdsStack) s_stack[wv][head][lane] = w; else stack[head - (unsigned)kLdsStack] = w;
+                else if (head < (unsigned)kLdsStack) s_stack[head][lane] = w; else stack[head - (unsigned)kLdsStack] = w;
                 ++head;
             }
             cn = near;
@@ -568,33 +519,31 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
     if (st & kBadEntry) atomicOr(overflow, 4u);
 }
 
-// Entry points.  The single-ray form takes the scene's buffers as plain kernel arguments (one wave per workgroup, the
-// persistent grid = 24 waves per CU); the chunked form takes the scene / supply structs.
+// Entry points: one wave per workgroup, the persistent grid = 24 waves per CU.  The first pass takes the scene's buffers
+// as plain kernel arguments (SceneArgs) and the ray count by value; the deep second pass takes the Scene struct and its list.
 struct SceneArgs { const VdTlasNode* tlas; const VdInstance* inst; const VdMeshInfo* meshes; const VdBvhNode* bvh;
                    const float* verts; const unsigned* indices; unsigned n_meshes, yield; const float4* irec; const float4* tpair; const float4* mrec;
                    unsigned* ovf_bits; };
-#ifndef VD_FAN_WPS
-#define VD_FAN_WPS 5
-#endif
+constexpr int kFanWps = 5;
 template <bool ANY, bool FAN>      // FAN: the fan-out's code is compiled in (calls that run as one launch use the kernel without it)
-__global__ __launch_bounds__(64, FAN ? VD_FAN_WPS : 6)   // second argument (HIP): waves per SIMD = 24 per CU; the fan-out's kernels take 96 registers at 5 per SIMD
+__global__ __launch_bounds__(64, FAN ? kFanWps : 6)      // second argument (HIP): waves per SIMD = 24 per CU; the fan-out's kernels take 96 registers at 5 per SIMD
                                                          // instead of spilling 9-12 at 6 (124 -> 129 / 192 -> 202 Mrays/s, profiles/r04_ab_trace_fan_wps.log)
 void trace_single_kernel(SceneArgs a, const VdRay* __restrict__ rays, unsigned n_rays, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
                          unsigned* __restrict__ overflow, unsigned* next_ray, const unsigned* __restrict__ gate, Fan fan) {
     if (gate && *gate == 0u) return;          // the call de-indexed the leaves itself and that went well: the other kernel runs
     const Scene s{a.tlas, a.inst, a.meshes, a.bvh, a.verts, a.indices, a.n_meshes, nullptr, a.irec, a.tpair, a.mrec, a.yield, a.ovf_bits};
-    const RaySource src{nullptr, n_rays, 1u, n_rays, next_ray, fan};
-    trace_body<ANY, false, false, FAN>(s, rays, src, out, out_any, overflow);
+    const RaySource src{nullptr, n_rays, next_ray, fan};
+    trace_body<ANY, false, FAN>(s, rays, src, out, out_any, overflow);
 }
 template <bool ANY, bool FAN>
-__global__ __launch_bounds__(64, FAN ? VD_FAN_WPS : 6)
+__global__ __launch_bounds__(64, FAN ? kFanWps : 6)
 void trace_single_prep_kernel(SceneArgs a, const VdRay* __restrict__ rays, unsigned n_rays, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
                               unsigned* __restrict__ overflow, unsigned* next_ray, const float* __restrict__ tris,
                               const unsigned* __restrict__ gate, Fan fan) {
     if (gate && *gate != 0u) return;          // the call's own de-indexing met an index range it cannot use: the indexed kernel runs
     const Scene s{a.tlas, a.inst, a.meshes, a.bvh, a.verts, a.indices, a.n_meshes, tris, a.irec, a.tpair, a.mrec, a.yield, a.ovf_bits};
-    const RaySource src{nullptr, n_rays, 1u, n_rays, next_ray, fan};
-    trace_body<ANY, true, false, FAN>(s, rays, src, out, out_any, overflow);
+    const RaySource src{nullptr, n_rays, next_ray, fan};
+    trace_body<ANY, true, FAN>(s, rays, src, out, out_any, overflow);
 }
 // The second pass: the rays listed in `list` (their ids, *n_list of them), one wave per workgroup, the stack beyond 128
 // entries in s.deep.  Rare by construction - a handful of rays of a deep scene - so it is one plain launch.
@@ -603,8 +552,8 @@ __global__ __launch_bounds__(64, 4)
 void trace_deep_kernel(Scene s, const VdRay* __restrict__ rays, const unsigned* __restrict__ list, const unsigned* __restrict__ n_list,
                        VdHit* __restrict__ out, unsigned* __restrict__ out_any, unsigned* __restrict__ overflow, unsigned* next_ray) {
     const unsigned n = *n_list;
-    const RaySource src{list, n, 1u, n, next_ray};
-    trace_body<ANY, PREP, false, false, true>(s, rays, src, out, out_any, overflow);
+    const RaySource src{list, n, next_ray};
+    trace_body<ANY, PREP, false, true>(s, rays, src, out, out_any, overflow);
 }
 // bitmap of the first pass -> list of ray ids (any order: a ray's record depends on the ray alone).  n_words = ceil(n_rays / 32);
 // bits of the last word that name no ray of this call are dropped: the list holds n_rays ids, rays[] and out[] n_rays records.
@@ -617,12 +566,6 @@ __global__ __launch_bounds__(256) void ovf_list_kernel(const unsigned* __restric
     if (w == 0u) return;
     unsigned at = atomicAdd(count, (unsigned)__popc(w));
     while (w) { const unsigned b = (unsigned)__builtin_ctz(w); list[at++] = i * 32u + b; w &= w - 1u; }
-}
-template <bool ANY, bool PREP>
-__global__ __launch_bounds__(64 * kWgWaves, 6)
-void trace_chunk_kernel(Scene s, const VdRay* __restrict__ rays, RaySource src, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
-                        unsigned* __restrict__ overflow) {
-    trace_body<ANY, PREP, true>(s, rays, src, out, out_any, overflow);
 }
 
 // fan-out, between two launches: the jobs appended so far are the next launch's supply
@@ -808,42 +751,8 @@ __global__ __launch_bounds__(64) void traverse_rec_kernel(const VdBvhNode* __res
     if (ovf) atomicOr(overflow, 1u);
 }
 
-// ---- ray binning (order only: results are per ray, so any permutation gives the same output) ----------------------------
-// key = origin cell (4 bits per axis over a box three times the scene's, Morton) in the high 12 bits, direction cell
-// (octahedral map of the normalised direction, 10 + 10 bits, Morton) in the low 20: rays that start close together and
-// point the same way - the pixels of a screen tile, the shadow rays of a surface patch - become neighbours.
-__device__ __forceinline__ unsigned spread3(unsigned v) {    // 4 bits -> every third bit
-    v &= 0xfu; v = (v | (v << 4)) & 0xc3u; v = (v | (v << 2)) & 0x249u; return v;
-}
-__device__ __forceinline__ unsigned spread2(unsigned v) {    // 10 bits -> every other bit
-    v &= 0x3ffu; v = (v | (v << 8)) & 0x00ff00ffu; v = (v | (v << 4)) & 0x0f0f0f0fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u; return v;
-}
-__global__ __launch_bounds__(256) void ray_keys_kernel(const VdRay* __restrict__ rays, unsigned n, const VdTlasNode* __restrict__ tlas,
-                                                       unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float4 a = reinterpret_cast<const float4*>(rays + i)[0], b = reinterpret_cast<const float4*>(rays + i)[1];
-    const VdTlasNode root = tlas[0];
-    float q[3];
-    const float o[3] = {a.x, a.y, a.z};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float lo = root.min[k], hi = root.max[k], w = hi - lo;
-        const float t = (o[k] - (lo - w)) / (3.0f * w);                  // [lo - w, hi + w] -> [0, 1]
-        q[k] = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;                  // NaN -> 0
-    }
-    const unsigned oc = spread3((unsigned)(q[0] * 15.99f)) | (spread3((unsigned)(q[1] * 15.99f)) << 1) | (spread3((unsigned)(q[2] * 15.99f)) << 2);
-    const float l1 = (fabsf(b.x) + fabsf(b.y)) + fabsf(b.z);
-    float u = b.x / l1, v = b.y / l1;
-    if (b.z < 0.0f) { const float uu = (1.0f - fabsf(v)) * (u >= 0.0f ? 1.0f : -1.0f), vv = (1.0f - fabsf(u)) * (v >= 0.0f ? 1.0f : -1.0f); u = uu; v = vv; }
-    u = u * 0.5f + 0.5f; v = v * 0.5f + 0.5f;
-    u = u > 0.0f ? (u < 1.0f ? u : 1.0f) : 0.0f; v = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    const unsigned dc = spread2((unsigned)(u * 1023.99f)) | (spread2((unsigned)(v * 1023.99f)) << 1);
-    keys[i] = (oc << 20) | dc;
-    vals[i] = i;
-}
-
-// Stable LSD radix sort of (key, value) pairs, 8 bits per pass.  A UNIT is one wave's 1024 consecutive pairs; units are
+// Stable LSD radix sort of (key, value) pairs, 8 bits per pass, for the Morton codes of the LBVH top level
+// (build_tight_tlas, VD_OPT_TRACE_TIGHT_TLAS = 2).  A UNIT is one wave's 1024 consecutive pairs; units are
 // independent: pass 1 counts a unit's digits, a single-workgroup scan turns the [digit][unit] table into start offsets,
 // pass 2 re-reads the unit in order - 16 groups of 64 - and ranks every pair among the equal digits before it (8 ballots
 // give the lanes with the same digit; the unit's running offsets sit in LDS).
@@ -1091,7 +1000,7 @@ __global__ void tight_root_kernel(VdTlasNode* nodes, unsigned n) {
 // ---- the private top level as an LBVH (VD_OPT_TRACE_TIGHT_TLAS = 2): built on all CUs in ~0.1 ms, so it can follow moving
 // instances every frame (vd_trace_accel_update_dev); the agglomerative builder (= 1) makes the better tree and takes the
 // reference's sequential chain to do it.  Morton codes of the box centres (10 bits per axis of the scene's extent), the
-// radix sort the ray binning uses, Karras' binary radix tree (one thread per interior node; equal codes are told apart by
+// radix sort above (rs_*_kernel), Karras' binary radix tree (one thread per interior node; equal codes are told apart by
 // their position), boxes bottom-up (the second child to arrive at a node goes on).  Nodes: 0 = the root, 1 + j = the
 // leaf of the j-th code in sorted order, n + i = interior node i (i >= 1): indices stay below 2n <= 65 536.
 __device__ __forceinline__ unsigned ord_of(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -1190,56 +1099,32 @@ __global__ __launch_bounds__(256) void lbvh_fit_kernel(unsigned n, VdTlasNode* n
     }
 }
 
-// order = the ray ids sorted by ray key (scratch of the context from byte `at`: past the flags and the entry records)
-int sort_rays(VdCtx* ctx, const VdTraceScene* sc, const VdRay* d_rays, uint32_t n, const unsigned** out_order, size_t at) {
-    const unsigned n_units = (n + kSortUnit - 1u) / kSortUnit;
-    const size_t arr = ((size_t)n * 4 + 255) & ~(size_t)255, tab = ((size_t)256 * n_units * 4 + 255) & ~(size_t)255;
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, at + 4 * arr + tab);
-    if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->scratch) + at;
-    unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
-    unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
-    unsigned* table = reinterpret_cast<unsigned*>(base + 4 * arr);
-    hipLaunchKernelGGL(ray_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_rays, n, sc->tlas_nodes, k[0], v[0]);
-    const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int a = pass & 1, b = a ^ 1;
-        hipLaunchKernelGGL(rs_count_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, ctx->stream, k[a], n, 8u * pass, n_units, table);
-        hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, table, 256u * n_units);
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, ctx->stream, k[a], v[a], n, 8u * pass, n_units, table, k[b], v[b]);
-    }
-    *out_order = v[0];            // four passes: back in buffer 0
-    return VD_OK;
-}
-
 int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out,
                  uint32_t* d_any = nullptr) {
     // idle waves keep drawing from the ray counter after the last ray: leave it room below 2^32
     if (n_rays > 0xf0000000u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: more than 0xf0000000 rays in one call");
-    // scratch: [256 B flags and counters][TLAS child pairs, 64 B x 65 536][entry records, 64 B x 65 536][mesh records][de-indexed triangles][ray binning arrays]
+    // scratch: [256 B flags and counters][TLAS child pairs, 64 B x 65 536][entry records, 64 B x 65 536][mesh records][de-indexed triangles][fan-out]
     // (pairs and entry records for all 65 536 indices a 16-bit child field can name: a stray index reads a poisoned slot, not beyond)
     const size_t pair_bytes = (size_t)64 * kTlasSlots, irec_bytes = (size_t)64 * kTlasSlots, owner_bytes = (size_t)4 * kTlasSlots;
     const size_t mrec_bytes = (size_t)128 * sc->n_meshes;
     const size_t tris_at = 256 + pair_bytes + irec_bytes + owner_bytes + ((mrec_bytes + 255) & ~(size_t)255);
     // A call that was not given prepared leaves de-indexes them itself when that is cheap next to the walk (one pass over the
     // index buffer, 36 B per triangle into the scratch: 5 us for the stress scene's 131 k triangles, 20 us for the harness
-    // scene's 1.2 M) - the plain vd_trace_dev then walks at the prepared rate.  Not for few rays over a big scene, not
-    // with the binned / chunked supplies, not with more meshes than one launch's gridDim.y, and only up to 2 Mi triangles
+    // scene's 1.2 M) - the plain vd_trace_dev then walks at the prepared rate.  Not for few rays over a big scene,
+    // not with more meshes than one launch's gridDim.y, and only up to 2 Mi triangles
     // (72 MB of the context's grow-only scratch, kept for its lifetime); VD_OPT_TRACE_AUTO_PREPARE = 2 raises that to
     // 16 Mi (576 MB), 0 turns it off.  vd_trace_prepare_dev is the explicit form without a limit.
     const size_t n_tri = sc->n_indices / 3u;
-    const bool single = ctx->option(VD_OPT_TRACE_CHUNK, 1) <= 1 &&
-                        !(ctx->option(VD_OPT_TRACE_SORT, 0) != 0 && n_rays >= (unsigned)ctx->option(VD_OPT_TRACE_SORT_MIN, 65536));
     const long long auto_opt = ctx->option(VD_OPT_TRACE_AUTO_PREPARE, 1);
-    const bool auto_prep = !d_tris && single && auto_opt != 0 && n_tri > 0 && sc->n_vertices > 0 && sc->n_meshes <= 65535u &&
+    const bool auto_prep = !d_tris && auto_opt != 0 && n_tri > 0 && sc->n_vertices > 0 && sc->n_meshes <= 65535u &&
                            n_tri <= ((size_t)1 << (auto_opt >= 2 ? 24 : 21)) && (size_t)n_rays * 8u >= n_tri;
     const size_t tris_bytes = auto_prep ? (((size_t)36 * n_tri + 64 + 255) & ~(size_t)255) : 0;
-    const size_t sort_at = tris_at + tris_bytes;
-    // fan-out (kFan*): single-ray supply, calls with at least one ray per lane of the grid, scenes with enough instances for
+    const size_t fan_at = tris_at + tris_bytes;
+    // fan-out (kFan*): calls with at least one ray per lane of the grid, scenes with enough instances for
     // a ray to be long.  [256 B control words][best: 8 B per ray][jobs: 48 B x cap]
     const unsigned waves = (unsigned)ctx->num_cus * (unsigned)std::min<long long>(kWavesPerCu, std::max<long long>(1, ctx->option(VD_OPT_TRACE_WAVES, kWavesPerCu)));
     unsigned phases = (unsigned)std::min<long long>(4, std::max<long long>(1, ctx->option(VD_OPT_TRACE_FAN, kFanPhases)));
-    if (!single || (size_t)n_rays < (size_t)waves * 64u || sc->n_instances < 64u) phases = 1u;
+    if ((size_t)n_rays < (size_t)waves * 64u || sc->n_instances < 64u) phases = 1u;
     // The fan-out's kernels cost ~15 % where no ray lives long enough to fan out (more code, spilled registers, launches that find
     // nothing to do): a call remembers how many jobs it made, and while the last call over the same top level made fewer than one
     // per 64 rays the next 15 calls over it run as one launch with the plain kernels; then the fan-out is tried again.
@@ -1250,7 +1135,7 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
     if (ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1) >= 0) fan_cap = (unsigned)std::min<long long>(fan_cap, ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1));      // tests: a list that fills up
     const size_t best_bytes = ((size_t)n_rays * 8u + 255) & ~(size_t)255;
     const size_t fan_bytes = phases > 1u ? 256 + best_bytes + (size_t)fan_cap * sizeof(FanJob) : 0;
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, sort_at + fan_bytes);
+    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, fan_at + fan_bytes);
     if (rc) return rc;
     // one bit per ray: "ran out of its 128 stack entries" (second pass below).  All zero between calls: zeroed when (re)allocated
     // and again after a call that set any, so a call that overflows nowhere pays nothing for it.
@@ -1263,21 +1148,15 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
         ctx->trace_ovf_dirty = true;       // until this call has ended cleanly
     }
     unsigned* d_ovf = reinterpret_cast<unsigned*>(ctx->trace_ovf);
-    // Binning is OFF by default: measured on the stress scene (tools/ab_trace.py, profiles/r03_ab_trace.log) rays handed
-    // out in sorted order are SLOWER (32.0 against 35.7 Mrays/s): the walk is bound by the slowest of a wave's 64 fetches,
-    // not by the L1 hit rate, and sorting puts the expensive rays of the dense screen centre side by side in time.
-    const bool sorted = ctx->option(VD_OPT_TRACE_SORT, 0) != 0 && n_rays >= (unsigned)ctx->option(VD_OPT_TRACE_SORT_MIN, 65536);
     vd_time_begin(ctx);
-    const unsigned* order = nullptr;
-    if (sorted) { rc = sort_rays(ctx, sc, d_rays, n_rays, &order, sort_at); if (rc) return rc; }
-    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);      // after sort_rays: the scratch may have grown
+    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
 #ifdef VD_TUNING
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 256, ctx->stream));
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag + 16, 0xff, 8, ctx->stream));
 #else
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 64, ctx->stream));
 #endif
-    unsigned* fan_ctl = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctx->scratch) + sort_at);      // [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
+    unsigned* fan_ctl = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctx->scratch) + fan_at);      // [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
     unsigned long long* fan_best = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(fan_ctl) + 256);
     FanJob* fan_jobs = reinterpret_cast<FanJob*>(reinterpret_cast<char*>(fan_best) + best_bytes);
     if (phases > 1u) {
@@ -1302,42 +1181,34 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
         d_tris = t; gate = d_flag + 2;        // non-zero: some mesh's index range cannot be de-indexed - the indexed kernel takes the call
     }
     Scene s{sc->tlas_nodes, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, d_tris, d_rec, d_pair, d_mrec, yield, d_ovf};
-    {
-        // Default: single rays from one global counter (chunk = 1), one wave per workgroup - the finest balance.  Chunks of
-        // consecutive rays per workgroup (a CU-local window of the ray order) lose more to imbalance than they gain in
-        // locality: 64 rays per chunk 32.6, 256 rays 16.9 Mrays/s against 35.2 in the same kernel (same log).
-        unsigned chunk = (unsigned)ctx->option(VD_OPT_TRACE_CHUNK, 1);
-        if (chunk <= 1u && !order) {
-            const SceneArgs a{sc->tlas_nodes, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, yield, d_rec, d_pair, d_mrec, d_ovf};
-            // fan-out: launch 0 hands out the rays; launch p >= 1 the jobs appended before it started (fan_snapshot_kernel);
-            // every launch but the last may append; fan_resolve_kernel writes the records of the rays that were fanned out
-            for (unsigned ph = 0; ph < phases; ++ph) {
-                Fan fan = {};
-                if (phases > 1u) {
-                    fan.jobs = fan_jobs; fan.append = fan_ctl; fan.cap = fan_cap; fan.best = fan_best; fan.level = ph;
-                    fan.below = ph + 1u < phases ? kFanBelow : 0u;
-                    if (ph) { fan.begin = fan_ctl + 8 + (ph - 1); fan.end = fan_ctl + 8 + ph; }
-                }
-                if (ph) hipLaunchKernelGGL(fan_snapshot_kernel, dim3(1), dim3(64), 0, ctx->stream, fan_ctl, fan_cap, fan_ctl + 8 + ph);
-                unsigned* next = ph == 0 ? d_flag + 1 : fan_ctl + ph;
-#define VD_TRACE_S(K, ...) do { if (phases > 1u) { if (d_any) hipLaunchKernelGGL((K<true, true>), dim3(waves), dim3(64), 0, ctx->stream, __VA_ARGS__); else hipLaunchKernelGGL((K<false, true>), dim3(waves), dim3(64), 0, ctx->stream, __VA_ARGS__); } \
-                                else { if (d_any) hipLaunchKernelGGL((K<true, false>), dim3(waves), dim3(64), 0, ctx->stream, __VA_ARGS__); else hipLaunchKernelGGL((K<false, false>), dim3(waves), dim3(64), 0, ctx->stream, __VA_ARGS__); } } while (0)
-                if (d_tris) VD_TRACE_S(trace_single_prep_kernel, a, d_rays, n_rays, d_out, d_any, d_flag, next, d_tris, gate, fan);
-                if (!d_tris || gate) VD_TRACE_S(trace_single_kernel, a, d_rays, n_rays, d_out, d_any, d_flag, next, gate, fan);
-#undef VD_TRACE_S
-            }
-            if (phases > 1u && !d_any)
-                hipLaunchKernelGGL(fan_resolve_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(256), 0, ctx->stream, fan_jobs, fan_ctl, fan_cap, fan_best, d_out);
-        } else {
-            const unsigned groups = (unsigned)ctx->num_cus * (kWavesPerCu / kWgWaves);
-            chunk = chunk <= 1u ? 64u : ((chunk + 63u) & ~63u);      // binned rays are handed out in chunks (of 64 at least)
-            const RaySource src{order, n_rays, chunk, (n_rays + chunk - 1u) / chunk, d_flag + 1};
-#define VD_TRACE_C(A, P) hipLaunchKernelGGL((trace_chunk_kernel<A, P>), dim3(groups), dim3(64 * kWgWaves), 0, ctx->stream, s, d_rays, src, d_out, d_any, d_flag)
-            if (d_any) { if (d_tris) VD_TRACE_C(true, true); else VD_TRACE_C(true, false); }
-            else { if (d_tris) VD_TRACE_C(false, true); else VD_TRACE_C(false, false); }
-#undef VD_TRACE_C
+    // two run-time booleans -> the template arguments of a launch: f(std::integral_constant<bool, a>{}, std::integral_constant<bool, b>{})
+    auto with_bools = [](bool x, bool y, auto&& f) {
+        using T = std::integral_constant<bool, true>; using F = std::integral_constant<bool, false>;
+        if (x) { if (y) f(T{}, T{}); else f(T{}, F{}); }
+        else { if (y) f(F{}, T{}); else f(F{}, F{}); }
+    };
+    const SceneArgs a{sc->tlas_nodes, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, yield, d_rec, d_pair, d_mrec, d_ovf};
+    // fan-out: launch 0 hands out the rays; launch p >= 1 the jobs appended before it started (fan_snapshot_kernel);
+    // every launch but the last may append; fan_resolve_kernel writes the records of the rays that were fanned out
+    for (unsigned ph = 0; ph < phases; ++ph) {
+        Fan fan = {};
+        if (phases > 1u) {
+            fan.jobs = fan_jobs; fan.append = fan_ctl; fan.cap = fan_cap; fan.best = fan_best; fan.level = ph;
+            fan.below = ph + 1u < phases ? kFanBelow : 0u;
+            if (ph) { fan.begin = fan_ctl + 8 + (ph - 1); fan.end = fan_ctl + 8 + ph; }
         }
+        if (ph) hipLaunchKernelGGL(fan_snapshot_kernel, dim3(1), dim3(64), 0, ctx->stream, fan_ctl, fan_cap, fan_ctl + 8 + ph);
+        unsigned* next = ph == 0 ? d_flag + 1 : fan_ctl + ph;
+        with_bools(d_any != nullptr, phases > 1u, [&](auto any, auto fanned) {
+            constexpr bool A = decltype(any)::value, F = decltype(fanned)::value;
+            if (d_tris) hipLaunchKernelGGL((trace_single_prep_kernel<A, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any, d_flag,
+                                           next, d_tris, gate, fan);
+            if (!d_tris || gate) hipLaunchKernelGGL((trace_single_kernel<A, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any,
+                                                    d_flag, next, gate, fan);
+        });
     }
+    if (phases > 1u && !d_any)
+        hipLaunchKernelGGL(fan_resolve_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(256), 0, ctx->stream, fan_jobs, fan_ctl, fan_cap, fan_best, d_out);
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
     VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1376,10 +1247,10 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
             sd.ovf_bits = nullptr;
             sd.deep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(list) + list_bytes);
             sd.deep_cap = (unsigned)cap;
-#define VD_TRACE_D(A, P) hipLaunchKernelGGL((trace_deep_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays, list, ctl, d_out, d_any, d_flag, ctl + 1)
-            if (d_any) { if (prep_walked) VD_TRACE_D(true, true); else VD_TRACE_D(true, false); }
-            else { if (prep_walked) VD_TRACE_D(false, true); else VD_TRACE_D(false, false); }
-#undef VD_TRACE_D
+            with_bools(d_any != nullptr, prep_walked, [&](auto any, auto prep) {
+                hipLaunchKernelGGL((trace_deep_kernel<decltype(any)::value, decltype(prep)::value>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays,
+                                   list, ctl, d_out, d_any, d_flag, ctl + 1);
+            });
             vd_time_end(ctx);                                                              // vd_last_gpu_ms covers the second pass too
             VD_HIP_CHECK(ctx, hipGetLastError());
             VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
