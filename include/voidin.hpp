@@ -44,6 +44,8 @@ using DrawIndexedIndirect = VdDrawIndexedIndirect;
 using CameraUniform = VdCameraUniform;
 using BvhNode = VdBvhNode;
 using TlasNode = VdTlasNode;
+using LodGroup = VdLodGroup;            // EXTENSION (voidin_abi.h "Level of detail"): Instance.mesh -> a run of MeshInfo rows
+using LodParams = VdLodParams;
 
 // Owns the VdCtx (the reference's wgpu device/queue pair inside `World`: app.rs:108-118).
 class Gpu {
@@ -278,6 +280,22 @@ class MeshPool {
         return first_id;
     }
 
+    // EXTENSION (voidin_abi.h "Level of detail"): the levels of ONE mesh, finest first, as consecutive MeshInfo rows (one
+    // batched BLAS build, like add_many), and the group that names them: the box of level 0, the first row, the number of
+    // levels, and switch_size[k] = the projected size below which level k + 1 (or a coarser one) is drawn - n_lods - 1
+    // values; the rest of the group's thresholds are 0 and play no part.  Returns the group; the caller appends it to the
+    // table that Instance.mesh indexes and uploads mesh_info_cpu as before.
+    LodGroup add_lods(const MeshRef* lods, size_t n_lods, const float* switch_size) {
+        if (n_lods < 1 || n_lods > VD_LOD_MAX) throw Error(VD_ERR_INVALID_ARG, "MeshPool::add_lods: 1..VD_LOD_MAX levels");
+        LodGroup g{};
+        g.first_row = add_many(lods, n_lods);
+        g.n_lods = (uint32_t)n_lods;
+        std::memcpy(g.min, mesh_info_cpu[g.first_row].min, 12);
+        std::memcpy(g.max, mesh_info_cpu[g.first_row].max, 12);
+        for (size_t k = 0; k + 1 < n_lods; ++k) g.switch_size[k] = switch_size[k];
+        return g;
+    }
+
     // NEW (voidin_abi.h "BLAS refit"): a mesh deformed - same vertex count, same indices.  The pool's copy of the positions
     // is replaced, the mesh's BLAS is refitted in place (topology and permuted indices kept) and MeshInfo.min / max become
     // calculate_bounds(positions) again (mesh/mod.rs:22-27), which generate_tlas / Tlas::refit and the cull read.
@@ -476,6 +494,11 @@ struct EmitDrawsBatchedResource {                     // the instanced form (no 
     uint32_t* draw_count;                             // device u32: the number of survivors
 };
 
+struct EmitDrawsLodResource {                         // level-of-detail selection (no reference counterpart): what the pass needs besides the World
+    const LodGroup* d_groups; uint32_t n_groups;      // device buffer indexed by Instance.mesh; world.d_mesh_info holds the ROWS
+    LodParams params;
+};
+
 class EmitDraws {
    public:
     explicit EmitDraws(Gpu& gpu) : gpu_(gpu) {}       // EmitDraws::new(&World) -> Result<Self> (visibility.rs:200-222)
@@ -508,6 +531,23 @@ class EmitDraws {
         gpu_.set_stream(encoder.hip_stream);
         gpu_.check(vd_cull_batch_dev(gpu_.ctx(), world.camera, world.d_mesh_info, world.n_meshes, world.d_instances,
                                      world.n_instances, resources.draw_cmd_buffer, resources.visible_ids, resources.draw_count));
+    }
+
+    // EXTENSION (voidin_abi.h "Level of detail"): record() with draw_count set, where every instance names a GROUP of
+    // world.d_mesh_info rows and is drawn with the row its projected size picks (or not at all below params.min_size);
+    // record_batched_lod is record_batched over those rows: one command per (mesh, level).  The consumers are unchanged.
+    void record_lod(const World& world, ProfilerCommandEncoder& encoder, const EmitDrawsLodResource& lod, EmitDrawsResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_compact_lod_dev(gpu_.ctx(), world.camera, lod.params, lod.d_groups, lod.n_groups, world.d_mesh_info, world.n_meshes,
+                                           world.d_instances, world.n_instances, resources.draw_cmd_buffer, resources.draw_count,
+                                           resources.pad_tail ? 1 : 0));
+    }
+    void record_batched_lod(const World& world, ProfilerCommandEncoder& encoder, const EmitDrawsLodResource& lod,
+                            EmitDrawsBatchedResource resources) const {
+        gpu_.set_stream(encoder.hip_stream);
+        gpu_.check(vd_cull_batch_lod_dev(gpu_.ctx(), world.camera, lod.params, lod.d_groups, lod.n_groups, world.d_mesh_info, world.n_meshes,
+                                         world.d_instances, world.n_instances, resources.draw_cmd_buffer, resources.visible_ids,
+                                         resources.draw_count));
     }
 
     // EXTENSION (occlusion culling; voidin_abi.h "Occlusion culling"): record() with draw_count set, with the occlusion test

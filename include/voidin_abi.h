@@ -905,6 +905,99 @@ int vd_cull_compact_hiz(VdCtx* ctx, const VdCameraUniform* camera,
                         VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail);
 
 /* ------------------------------------------------------------------------------------ */
+/* Level of detail  (EXTENSION, no reference counterpart)                                   */
+/* ------------------------------------------------------------------------------------ */
+/* The reference draws every instance with the one index range of instances[i].mesh.  These entry points choose a level of
+ * detail per instance while the cull pass has it in registers, and write the choice where the draw lists already take
+ * their index ranges from: the per-instance id that the expansion (vd_expand_mask_dev) and the grouping
+ * (vd_batch_mask_dev) look up in d_meshes.  They are defined here and nowhere else and are OFF in every parity run: no
+ * entry point of the sections above reaches them.
+ *
+ * Instance.mesh indexes a table of GROUPS; a group names a run of consecutive ROWS of d_meshes, one per level, finest
+ * first.  Each level is an ordinary VdMeshInfo row (what MeshPool::add produces), so the consumer is unchanged:
+ * multi_draw_indexed_indirect reads index ranges as before.  Only index_count / base_index / vertex_offset of a row are
+ * used; the box that is tested and measured is the group's.
+ *
+ * For instance i, in fp32, in this order, no FMA (n_group groups, n_mesh rows, P = the VdLodParams):
+ *   g       = min(instances[i].mesh, n_group - 1),  G = groups[g]
+ *   c       = ((view * transform) * vec4((G.min + G.max) / 2, 1)).xyz               (as emit_draws.wgsl:14-15)
+ *   visible = the frustum test of vd_cull_emit with G.min / G.max as the mesh box    (bug-compatible radius included)
+ *   r       = (length(G.max - G.min) * 0.5) * max_scale(transform)                   (the r of "Occlusion culling")
+ *   d       = -c.z
+ *   dist    = fmaxf(d, P.min_distance)                                               (a NaN d gives min_distance)
+ *   size    = (r * P.scale) / dist
+ *   nl      = clamp(G.n_lods, 1, VD_LOD_MAX)
+ *   lod     = the NUMBER of k < nl - 1 with size < G.switch_size[k]    (a count, not a first failure: defined for
+ *             unsorted thresholds; a NaN size gives 0, the finest level)
+ *   row     = min(min(G.first_row, n_mesh - 1) + lod, n_mesh - 1)
+ *   drawn   = visible && !(size < P.min_size)                                        (contribution culling; 0 = off)
+ * With scale = projection[5] * viewport_height / 2, size is the projected radius of the bounding sphere in pixels.
+ *
+ *   vd_lod_ids_dev            d_out_ids[i] = row(i) for EVERY instance (visibility and min_size play no part), as ids of
+ *                             id_bytes = 1, 2 or 4 bytes, which must be able to hold n_mesh - 1.  The table must be
+ *                             16-byte aligned.  With it any mask the library produces (vd_cull_mask_dev on the groups'
+ *                             boxes, vd_occlusion_mask_dev, the all-gathered masks of vd_dist_*) is expanded or grouped by
+ *                             LOD row through vd_expand_mask_dev / vd_batch_mask_dev.
+ *   vd_cull_compact_lod_dev   the ordered list of the instances with `drawn`: { d_meshes[row(i)].index_count, 1,
+ *                             d_meshes[row(i)].base_index, d_meshes[row(i)].vertex_offset, i }, ascending i, and the
+ *                             count.  pad_tail as in vd_cull_compact_dev; without it nothing behind the count is written.
+ *   vd_cull_batch_lod_dev     the instanced form ("Instanced draw lists") over rows: one command per ROW of d_meshes -
+ *                             one per (mesh, level) - and the drawn instances' ids grouped by row.  n_mesh <=
+ *                             VD_BATCH_MAX_MESHES applies to rows.
+ *   vd_cull_compact_lod       host pointers, staged through the context and synchronous, like vd_cull_compact.  It sees the
+ *                             group table and refuses (VD_ERR_INVALID_ARG) one that breaks 1 <= n_lods <= VD_LOD_MAX or
+ *                             first_row + n_lods <= n_mesh in any group.
+ * The *_dev forms do not read the group table back: the clamps above make every table defined.
+ * Always the split form, at every size: one pass over the instances (cull to bitmask + the row of every instance in the
+ * id table + survivors per tile), then the unchanged expansion or grouping: two launches for the list, three with
+ * pad_tail.  No atomics, no wait between workgroups, hence no "gave up" state.  The pass shares the context's id table
+ * with vd_cull_compact_dev: calls of both kinds, also with different id widths, may alternate on one context - every
+ * row of the table that differs from the call's is rewritten.  Once its scratch exists (first call, or a larger scene)
+ * a call only enqueues kernels on the context's stream, so it can be captured into a HIP graph; the camera and the
+ * parameters are baked in by value.  vd_last_gpu_ms_stage: 0 = the pass over the instances, 1 = everything after it.
+ * VD_ERR_INVALID_ARG: null ctx / camera / groups / meshes / count (cmds); n_group == 0 or n_mesh == 0; scale not finite
+ * or < 0; min_distance not finite or <= 0; min_size not finite or < 0; id_bytes not 1, 2 or 4 or too narrow for
+ * n_mesh - 1; a misaligned id table; with n_inst > 0: null instances / out / ids.  A refused call writes nothing.
+ * n_inst == 0: as in the sibling calls (the count is set to 0; vd_cull_batch_lod_dev writes its n_mesh empty commands;
+ * vd_lod_ids_dev does nothing).
+ * OUT OF SCOPE: hysteresis or any per-instance LOD state; cross-fade; a multi-view form; a fused occlusion + LOD form
+ * and a vd_dist_* form (both are compositions of vd_lod_ids_dev with the existing mask consumers).
+ * Measured times against vd_cull_compact_dev / vd_cull_batch_dev: profiles/cull_lod.md.                                 */
+#define VD_LOD_MAX 8u
+typedef struct VdLodGroup {          /* 64 B, 16-byte aligned rows; indexed by Instance.mesh */
+    float    min[3];  uint32_t first_row;   /* box used by the visibility test and the size metric; row of LOD 0 in d_meshes */
+    float    max[3];  uint32_t n_lods;      /* 1 .. VD_LOD_MAX, LOD k is row first_row + k     */
+    float    switch_size[VD_LOD_MAX - 1];   /* LOD k+1.. is taken while size < switch_size[k]  */
+    uint32_t _pad;
+} VdLodGroup;
+typedef struct VdLodParams {         /* host, by value */
+    float scale;         /* e.g. projection[5] * viewport_height / 2: size = projected radius in pixels */
+    float min_distance;  /* > 0, finite */
+    float min_size;      /* >= 0; 0 = off; an instance with size < min_size is not drawn (contribution culling) */
+    uint32_t _pad;
+} VdLodParams;
+int vd_lod_ids_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */, VdLodParams params,
+                   const VdLodGroup* d_groups, uint32_t n_group, uint32_t n_mesh,
+                   const VdInstance* d_instances, uint32_t n_inst,
+                   void* d_out_ids /* n_inst ids */, uint32_t id_bytes /* 1, 2, 4 */);
+int vd_cull_compact_lod_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */, VdLodParams params,
+                            const VdLodGroup* d_groups, uint32_t n_group,
+                            const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                            const VdInstance* d_instances, uint32_t n_inst,
+                            VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail);
+int vd_cull_batch_lod_dev(VdCtx* ctx, const VdCameraUniform* camera /* host */, VdLodParams params,
+                          const VdLodGroup* d_groups, uint32_t n_group,
+                          const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                          const VdInstance* d_instances, uint32_t n_inst,
+                          VdDrawIndexedIndirect* d_out_cmds /* n_mesh */, uint32_t* d_out_instance_ids /* n_inst */,
+                          uint32_t* d_out_count);
+int vd_cull_compact_lod(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params,
+                        const VdLodGroup* groups, uint32_t n_group,
+                        const VdMeshInfo* meshes, uint32_t n_mesh,
+                        const VdInstance* instances, uint32_t n_inst,
+                        VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail);
+
+/* ------------------------------------------------------------------------------------ */
 /* Instance animation  (SURVEY.md §8f N2 — the upstream mutator of the cull / TLAS input)  */
 /* ------------------------------------------------------------------------------------ */
 /* Replaces the `update` compute pass (shaders/compute_update.wgsl:10-28, recorded by

@@ -38,10 +38,16 @@ TLAS_NODE_WIDE = np.dtype([("min", "<f4", (3,)), ("left", "<u4"), ("max", "<f4",
                            ("right", "<u4"), ("instance_idx", "<u4"), ("_pad", "<u4", (3,))])
 RAY = np.dtype([("eye", "<f4", (3,)), ("_pad0", "<f4"), ("dir", "<f4", (3,)), ("_pad1", "<f4")])
 HIT = np.dtype([("dist", "<f4"), ("hit", "<u4"), ("instance", "<u4"), ("triangle", "<u4")])
+# level-of-detail extension (include/voidin_abi.h "Level of detail"): VdLodGroup rows, VdLodParams
+LOD_MAX = 8
+LOD_GROUP = np.dtype([("min", "<f4", (3,)), ("first_row", "<u4"), ("max", "<f4", (3,)), ("n_lods", "<u4"),
+                      ("switch_size", "<f4", (LOD_MAX - 1,)), ("_pad", "<u4")])
+LOD_PARAMS = np.dtype([("scale", "<f4"), ("min_distance", "<f4"), ("min_size", "<f4"), ("_pad", "<u4")])
 
 assert INSTANCE.itemsize == 144 and MESH_INFO.itemsize == 48 and DRAW.itemsize == 20
 assert CAMERA.itemsize == 320 and BVH_NODE.itemsize == 32 and TLAS_NODE.itemsize == 32
 assert TLAS_NODE_WIDE.itemsize == 48 and RAY.itemsize == 32 and HIT.itemsize == 16
+assert LOD_GROUP.itemsize == 64 and LOD_PARAMS.itemsize == 16
 
 MAX_DIST = np.float32(1e30)
 CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run their split form from this many instances
@@ -84,6 +90,24 @@ class TraceScene(C.Structure):
                 ("bvh_nodes", C.c_void_p), ("n_bvh_nodes", C.c_uint32),
                 ("vertices", C.c_void_p), ("n_vertices", C.c_uint32),
                 ("indices", C.c_void_p), ("n_indices", C.c_uint32)]
+
+
+class LodParams(C.Structure):
+    """VdLodParams (include/voidin_abi.h, level-of-detail extension): passed BY VALUE."""
+    _fields_ = [("scale", C.c_float), ("min_distance", C.c_float), ("min_size", C.c_float), ("_pad", C.c_uint32)]
+
+
+def lod_params(p) -> "LodParams":
+    """LodParams from a LodParams, a LOD_PARAMS record / array of one, a mapping, or (scale, min_distance[, min_size])."""
+    if isinstance(p, LodParams):
+        return p
+    if isinstance(p, (np.ndarray, np.void)):
+        r = np.asarray(p, dtype=LOD_PARAMS).reshape(-1)[0]
+        return LodParams(float(r["scale"]), float(r["min_distance"]), float(r["min_size"]), 0)
+    if isinstance(p, dict):
+        return LodParams(float(p["scale"]), float(p["min_distance"]), float(p.get("min_size", 0.0)), 0)
+    p = tuple(p)
+    return LodParams(float(p[0]), float(p[1]), float(p[2]) if len(p) > 2 else 0.0, 0)
 
 
 class HizLayout(C.Structure):
@@ -204,6 +228,10 @@ PROTOTYPES = {
     "vd_cull_compact_hiz": (_I, [_P, _P, _P, _U, _P, _U, _P, _U, _U, _P, _P, _I]),
     "vd_cull_early_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _P, _P, _I]),
     "vd_cull_late_dev": (_I, [_P, _P, _P, _U, _P, _U, _P, _U, _U, _P, _P, _P, _P, _I]),
+    "vd_lod_ids_dev": (_I, [_P, _P, LodParams, _P, _U, _U, _P, _U, _P, _U]),
+    "vd_cull_compact_lod_dev": (_I, [_P, _P, LodParams, _P, _U, _P, _U, _P, _U, _P, _P, _I]),
+    "vd_cull_batch_lod_dev": (_I, [_P, _P, LodParams, _P, _U, _P, _U, _P, _U, _P, _P, _P]),
+    "vd_cull_compact_lod": (_I, [_P, _P, LodParams, _P, _U, _P, _U, _P, _U, _P, _P, _I]),
     "vd_compute_update_dev": (_I, [_P, _P, _U, _P, _U, C.c_float, C.c_float, _I]),
     "vd_ctx_set_timing": (_I, [_P, _I]),
     "vd_last_gpu_ms": (C.c_float, [_P]),

@@ -338,6 +338,38 @@ int vd_cull_batch_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInf
     return VD_OK;
 }
 
+// The instanced form over ROWS of the mesh table (include/voidin_abi.h, "Level of detail"): pass 1 of the LOD forms, whose
+// id table holds the row every instance is drawn with, then the grouping above unchanged - one command per (mesh, LOD).
+int vd_cull_batch_lod_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params, const VdLodGroup* d_groups, uint32_t n_group,
+                          const VdMeshInfo* d_meshes, uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst,
+                          VdDrawIndexedIndirect* d_out_cmds, uint32_t* d_out_instance_ids, uint32_t* d_out_count) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    int rc = vd_lod_check(ctx, "vd_cull_batch_lod", camera, &params, d_groups, n_group, n_mesh);
+    if (rc) return rc;
+    if (!d_meshes || !d_out_cmds || !d_out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_batch_lod: null meshes/cmds/count");
+    if (n_mesh > VD_BATCH_MAX_MESHES) {
+        snprintf(ctx->err, sizeof(ctx->err), "vd_cull_batch_lod%s", kMeshLimitMsg);
+        return VD_ERR_INVALID_ARG;
+    }
+    if (n_inst > 0 && (!d_instances || !d_out_instance_ids)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_batch_lod: null instances/instance-ids");
+    if (n_inst == 0) {
+        launch_empty(ctx, d_meshes, n_mesh, d_out_cmds, d_out_count);
+        VD_HIP_CHECK(ctx, hipGetLastError());
+        return VD_OK;
+    }
+    rc = ensure_batch_scratch(ctx, n_mesh);
+    if (rc) return rc;
+    vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
+    rc = launch_lod_pass(ctx, camera, &params, d_groups, n_group, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
+    if (rc) return rc;
+    rc = launch_batch(ctx, d_mask, n_inst, d_ids, id_bytes, d_meshes, n_mesh, d_out_cmds, d_out_instance_ids, d_out_count);
+    if (rc) return rc;
+    vd_time_end(ctx);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
+}
+
 // host pointers: staged like vd_cull_compact - instances; meshes behind a 16-byte header that takes the count; the n_mesh
 // commands followed by n_inst id words
 int vd_cull_batch(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* meshes, uint32_t n_mesh, const VdInstance* instances,

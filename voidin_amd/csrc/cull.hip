@@ -16,7 +16,8 @@
 //     writes only one ballot bit + a compact mesh id per instance and the survivors of every
 //     1024-instance tile, so the read stream runs at ~6.5 TB/s (it is `cull_tile`, the one tile
 //     skeleton, with `TiledPolicy`; the several-views and the occlusion pass 1 are the same
-//     skeleton with `ViewsPolicy` / `OccPolicy`); pass 2 `expand_mask_u8_kernel` /
+//     skeleton with `ViewsPolicy` / `OccPolicy`, and the LOD pass 1, `cull_mask_lod_kernel`, with `LodPolicy`, which
+//     takes its box from a group table and stores the mesh-table ROW it picks as the instance's id); pass 2 `expand_mask_u8_kernel` /
 //     `expand_mask_kernel`: workgroup c sums the tile counts before its 8192-instance chunk and
 //     expands the chunk to out[offset[c]...): no ticket, no look-back, no wait on another
 //     workgroup, every load issued before the first store.
@@ -135,10 +136,15 @@ __device__ __forceinline__ bool frustum_visible(const CullCamera& cam, const Mes
     return true;
 }
 
+// a TRUE bounding radius (the frustum test's is bug-compatible): the occlusion test's and the LOD metric's r
+__device__ __forceinline__ float sphere_radius(const MeshRec& m, const ViewCentre& vc) {
+    return (len3(m.mxx - m.mnx, m.mxy - m.mny, m.mxz - m.mnz) * 0.5f) * vc.max_scale;
+}
+
 // does the bounding sphere lie behind the depth pyramid?  (no reference counterpart: definition in include/voidin_abi.h)
 __device__ __forceinline__ bool sphere_occluded(const OccProj& P, const float znear, const HizView& hz, const MeshRec& m, const ViewCentre& vc) {
     const float* c = vc.c;
-    const float r = (len3(m.mxx - m.mnx, m.mxy - m.mny, m.mxz - m.mnz) * 0.5f) * vc.max_scale;
+    const float r = sphere_radius(m, vc);
     const float d = -c[2];
     const float dn = d - r;
     if (!(dn > znear)) return false;
@@ -170,6 +176,43 @@ __device__ __forceinline__ bool sphere_occluded(const OccProj& P, const float zn
 
 __device__ __forceinline__ bool is_visible(const CullCamera& cam, const MeshRec& m, const LaneInst& li) {
     return frustum_visible(cam, m, view_centre(cam.view, m, li));
+}
+
+// LOD selection (no reference counterpart: definition in include/voidin_abi.h, "Level of detail").  One row of the group
+// table is 64 bytes: the box the tests above use, the first row of the group in the mesh table, and the thresholds.
+struct LodParams { float scale, min_distance, min_size; };
+struct LodRec { MeshRec box; unsigned first_row, n_lods; float switch_size[VD_LOD_MAX - 1]; };
+
+__device__ __forceinline__ LodRec load_group(const VdLodGroup* __restrict__ groups, unsigned g) {
+    const uint4* p = reinterpret_cast<const uint4*>(groups + g);
+    const uint4 a = p[0], b = p[1], c = p[2], d = p[3];     // four independent 16-byte loads
+    LodRec G;
+    G.box.mnx = __uint_as_float(a.x); G.box.mny = __uint_as_float(a.y); G.box.mnz = __uint_as_float(a.z); G.first_row = a.w;
+    G.box.mxx = __uint_as_float(b.x); G.box.mxy = __uint_as_float(b.y); G.box.mxz = __uint_as_float(b.z); G.n_lods = b.w;
+    G.box.index_count = 0u; G.box.base_index = 0u; G.box.vertex_offset = 0;
+    G.switch_size[0] = __uint_as_float(c.x); G.switch_size[1] = __uint_as_float(c.y); G.switch_size[2] = __uint_as_float(c.z);
+    G.switch_size[3] = __uint_as_float(c.w); G.switch_size[4] = __uint_as_float(d.x); G.switch_size[5] = __uint_as_float(d.y);
+    G.switch_size[6] = __uint_as_float(d.z);
+    return G;
+}
+
+// size = the projected radius (pixels for scale = projection[5] * viewport_height / 2); a NaN distance gives min_distance
+__device__ __forceinline__ float lod_size(const LodParams& P, const MeshRec& m, const ViewCentre& vc) {
+    const float r = sphere_radius(m, vc);
+    const float d = -vc.c[2];
+    const float dist = fmaxf(d, P.min_distance);
+    return (r * P.scale) / dist;
+}
+
+// the row of the mesh table: a COUNT of the thresholds above `size` (defined for unsorted ones; NaN counts none), every
+// index clamped so that any table is defined
+__device__ __forceinline__ unsigned lod_row(const LodRec& G, float size, unsigned n_mesh) {
+    const unsigned nl = min(max(G.n_lods, 1u), (unsigned)VD_LOD_MAX);
+    unsigned lod = 0u;
+#pragma unroll
+    for (unsigned k = 0; k + 1u < (unsigned)VD_LOD_MAX; ++k) lod += (k + 1u < nl && size < G.switch_size[k]) ? 1u : 0u;
+    const unsigned first = min(G.first_row, n_mesh - 1u);
+    return first + min(lod, n_mesh - 1u - first);           // == min(first + lod, n_mesh - 1) without the overflow
 }
 
 // Stream the 64 instances starting at `first` into this wave's LDS slab (coalesced 16 B per
@@ -483,13 +526,24 @@ template <typename IdT> struct TileIds {
     }
 };
 
-// One wave's tile t.  The policy is called once per round with this lane's instance - `live` = it exists - and keeps the
-// ballot word(s) it decides on in its own registers; flush(t), after the last round, stores them and their survivor
-// count(s).  Everything else of a tile is here: the instance stream through the wave-private slab (the next round's loads
-// in flight while this one is tested), the mesh clamp, and the id table.
+// Where a policy's box comes from.  Every form but the LOD one takes it from the mesh table: the clamped mesh id - which
+// is also the id the table stores - and that mesh's record.  (LodSource, further down, reads a row of the group table.)
+struct MeshBox { unsigned mid; MeshRec m; };
+struct MeshSource {
+    const VdMeshInfo* __restrict__ meshes; unsigned n_mesh;
+    __device__ __forceinline__ MeshBox fetch(const LaneInst& li) const {
+        const unsigned mid = min(li.mesh, n_mesh - 1u);
+        return MeshBox{mid, load_mesh(meshes, mid)};
+    }
+};
+
+// One wave's tile t.  The policy supplies the box and the id to store: its `src` fetches the record this lane's instance
+// is tested with, and round - called once per round, `live` = the instance exists - keeps the ballot word(s) it decides
+// on in its own registers and returns the id the table stores for the instance; flush(t), after the last round, stores
+// the words and their survivor count(s).  Everything else of a tile is here: the instance stream through the
+// wave-private slab (the next round's loads in flight while this one is tested) and the id table.
 template <typename IdT, typename Policy>
-__device__ __forceinline__ void cull_tile(const VdMeshInfo* __restrict__ meshes, unsigned n_mesh, const VdInstance* __restrict__ inst,
-                                          unsigned n_inst, IdT* __restrict__ ids_out, unsigned t, Policy& policy) {
+__device__ __forceinline__ void cull_tile(const VdInstance* __restrict__ inst, unsigned n_inst, IdT* __restrict__ ids_out, unsigned t, Policy& policy) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     char* slab = smem + wave * (kSlabBytes + TileIds<IdT>::kBytes);
@@ -509,10 +563,8 @@ __device__ __forceinline__ void cull_tile(const VdMeshInfo* __restrict__ meshes,
         vd_wave_lds_sync();
         const LaneInst li = slab_read(slab, lane);
         vd_wave_lds_sync();
-        const unsigned mid = min(li.mesh, n_mesh - 1u);
-        const MeshRec m = load_mesh(meshes, mid);
-        policy.round(r, lane < n_valid, m, li);
-        s_ids[r * kWave + lane] = (IdT)mid;
+        const auto box = policy.src.fetch(li);
+        s_ids[r * kWave + lane] = (IdT)policy.round(r, lane < n_valid, box, li);
     }
     vd_wave_lds_sync();
     policy.flush(t);
@@ -531,13 +583,14 @@ __device__ __forceinline__ void store_tile_count(unsigned* __restrict__ dst, vd_
 
 // One camera: one ballot word per round, round r's in lane r.
 struct TiledPolicy {
-    const CullCamera& cam;
+    const CullCamera& cam; const MeshSource src;
     vd_u64* __restrict__ mask; unsigned* __restrict__ tile_count; unsigned n_inst;
     const unsigned lane = threadIdx.x & 63u;
     vd_u64 my_word = 0;
-    __device__ __forceinline__ void round(int r, bool live, const MeshRec& m, const LaneInst& li) {
-        const vd_u64 b = __ballot(live && is_visible(cam, m, li));
+    __device__ __forceinline__ unsigned round(int r, bool live, const MeshBox& box, const LaneInst& li) {
+        const vd_u64 b = __ballot(live && is_visible(cam, box.m, li));
         if (lane == (unsigned)r) my_word = b;
+        return box.mid;
     }
     __device__ __forceinline__ void flush(unsigned t) {
         const size_t w0 = (size_t)t * kMaskRounds, n_words = ((size_t)n_inst + 63) / 64;
@@ -553,8 +606,8 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_tiled_kernel(CullCamera c
                                                                      IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
                                                                      unsigned n_tiles) {
     for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
-        TiledPolicy policy{cam, mask, tile_count, n_inst};
-        cull_tile(meshes, n_mesh, inst, n_inst, ids_out, t, policy);
+        TiledPolicy policy{cam, MeshSource{meshes, n_mesh}, mask, tile_count, n_inst};
+        cull_tile(inst, n_inst, ids_out, t, policy);
     }
 }
 
@@ -574,11 +627,12 @@ static_assert(kMaxViews * kMaskRounds == 2 * kWave, "two ballot registers per la
 struct ViewCameras { CullCamera cam[kMaxViews]; };
 
 struct ViewsPolicy {
-    const ViewCameras& cams; unsigned n_views;
+    const ViewCameras& cams; unsigned n_views; const MeshSource src;
     vd_u64* __restrict__ mask; size_t mask_stride; unsigned* __restrict__ tile_count; unsigned count_stride; unsigned n_inst;
     const unsigned lane = threadIdx.x & 63u;
     vd_u64 word_lo = 0, word_hi = 0;      // lane l: the ballot of view (l >> 4) [+ 4] in round l & 15
-    __device__ __forceinline__ void round(int r, bool live, const MeshRec& m, const LaneInst& li) {
+    __device__ __forceinline__ unsigned round(int r, bool live, const MeshBox& box, const LaneInst& li) {
+        const MeshRec& m = box.m;
         const MeshCentre c0 = mesh_centre(m);
         const float ms = max_scale(li.T0, li.T1, li.T2);
 #pragma unroll 1
@@ -588,6 +642,7 @@ struct ViewsPolicy {
             const unsigned slot = (v & 3u) * (unsigned)kMaskRounds + (unsigned)r;
             if (lane == slot) { if (v < 4u) word_lo = b; else word_hi = b; }
         }
+        return box.mid;
     }
     // every lane stores its word of each register into its view's mask; the survivors of a view are the bits of its 16 lanes
     __device__ __forceinline__ void flush(unsigned t) {
@@ -610,8 +665,8 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_views_kernel(ViewCameras 
                                                                      IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
                                                                      unsigned count_stride, unsigned n_tiles) {
     for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
-        ViewsPolicy policy{cams, n_views, mask, mask_stride, tile_count, count_stride, n_inst};
-        cull_tile(meshes, n_mesh, inst, n_inst, ids_out, t, policy);
+        ViewsPolicy policy{cams, n_views, MeshSource{meshes, n_mesh}, mask, mask_stride, tile_count, count_stride, n_inst};
+        cull_tile(inst, n_inst, ids_out, t, policy);
     }
 }
 
@@ -628,7 +683,7 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_views_kernel(ViewCameras 
 // the instance stream is nontemporal.
 template <bool HIZ, bool PREV>
 struct OccPolicy {
-    const CullCamera& cam; const OccProj& proj; const HizView& hz;
+    const CullCamera& cam; const OccProj& proj; const HizView& hz; const MeshSource src;
     vd_u64* __restrict__ mask; vd_u64* visible_out; unsigned* __restrict__ tile_count;
     const unsigned lane = threadIdx.x & 63u;
     bool my_slot;                         // lane r holds the words of round r
@@ -640,7 +695,8 @@ struct OccPolicy {
         my_slot = lane < (unsigned)kMaskRounds && w0 + lane < n_words;
         if (PREV && my_slot) { const vd_u64 p = prev[w0 + lane]; p_lo = (unsigned)p; p_hi = (unsigned)(p >> 32); }
     }
-    __device__ __forceinline__ void round(int r, bool live, const MeshRec& m, const LaneInst& li) {
+    __device__ __forceinline__ unsigned round(int r, bool live, const MeshBox& box, const LaneInst& li) {
+        const MeshRec& m = box.m;
         const ViewCentre vc = view_centre(cam.view, m, li);
         bool keep = live && frustum_visible(cam, m, vc);
         if (HIZ) {
@@ -656,6 +712,7 @@ struct OccPolicy {
             else b &= p;
         }
         if (lane == (unsigned)r) list_word = b;
+        return box.mid;
     }
     __device__ __forceinline__ void flush(unsigned t) {
         const size_t w0 = (size_t)t * kMaskRounds;
@@ -674,12 +731,60 @@ __global__ __launch_bounds__(kBlock, 3) void cull_mask_occ_kernel(CullCamera cam
                                                                    IdT* __restrict__ ids_out, unsigned* __restrict__ tile_count,
                                                                    unsigned n_tiles) {
     for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
-        OccPolicy<HIZ, PREV> policy{cam, proj, hz, mask, visible_out, tile_count};
+        OccPolicy<HIZ, PREV> policy{cam, proj, hz, MeshSource{meshes, n_mesh}, mask, visible_out, tile_count};
         policy.begin(t, n_inst, prev);
         // (t is the same in every lane of the wave.  The early forms say so: the tile's addresses then live in scalar registers,
         // which the 4-byte-id one, at the 168-register ceiling of three waves per SIMD, needs to stay free of spills.  The forms
         // that read the pyramid measured 0.2-0.6 % slower with it: profiles/cull_pass1_refactor.md, section 3)
-        cull_tile(meshes, n_mesh, inst, n_inst, ids_out, HIZ ? t : (unsigned)__builtin_amdgcn_readfirstlane((int)t), policy);
+        cull_tile(inst, n_inst, ids_out, HIZ ? t : (unsigned)__builtin_amdgcn_readfirstlane((int)t), policy);
+    }
+}
+
+// Per-instance LOD selection written into the same id table (vd_cull_compact_lod*, vd_cull_batch_lod_dev, vd_lod_ids_dev;
+// extension, no reference counterpart - definition in include/voidin_abi.h, "Level of detail").  The box comes from the
+// instance's GROUP (one 64-byte row, four 16-byte loads, nothing that depends on another load), one view_centre feeds the
+// frustum test and the size metric, and the id the table stores is the ROW of the mesh table the metric picks: the
+// expansion and the counting sort read that table as before and never learn that a row is a level of detail.
+//   MASK = false (vd_lod_ids_dev): the rows alone, for every instance - no visibility test, no mask, no counts.
+struct LodSource {
+    const VdLodGroup* __restrict__ groups; unsigned n_group;
+    __device__ __forceinline__ LodRec fetch(const LaneInst& li) const { return load_group(groups, min(li.mesh, n_group - 1u)); }
+};
+
+template <bool MASK>
+struct LodPolicy {
+    const CullCamera& cam; const LodParams& P; const LodSource src; unsigned n_mesh;
+    vd_u64* __restrict__ mask; unsigned* __restrict__ tile_count; unsigned n_inst;
+    const unsigned lane = threadIdx.x & 63u;
+    vd_u64 my_word = 0;
+    __device__ __forceinline__ unsigned round(int r, bool live, const LodRec& G, const LaneInst& li) {
+        const ViewCentre vc = view_centre(cam.view, G.box, li);
+        const float size = lod_size(P, G.box, vc);
+        const unsigned row = lod_row(G, size, n_mesh);       // the thresholds are dead before the frustum test needs registers
+        if (MASK) {
+            const bool drawn = frustum_visible(cam, G.box, vc) && !(size < P.min_size);
+            const vd_u64 b = __ballot(live && drawn);
+            if (lane == (unsigned)r) my_word = b;
+        }
+        return row;
+    }
+    __device__ __forceinline__ void flush(unsigned t) {
+        if (!MASK) return;
+        const size_t w0 = (size_t)t * kMaskRounds, n_words = ((size_t)n_inst + 63) / 64;
+        if (lane < (unsigned)kMaskRounds && w0 + lane < n_words) mask[w0 + lane] = my_word;
+        store_tile_count(tile_count + t, my_word, lane == 0u);           // my_word is 0 in lanes >= kMaskRounds
+    }
+};
+
+template <typename IdT, bool MASK>
+__global__ __launch_bounds__(kBlock, 3) void cull_mask_lod_kernel(CullCamera cam, LodParams P, const VdLodGroup* __restrict__ groups,
+                                                                   unsigned n_group, unsigned n_mesh, const VdInstance* __restrict__ inst,
+                                                                   unsigned n_inst, vd_u64* __restrict__ mask, IdT* __restrict__ ids_out,
+                                                                   unsigned* __restrict__ tile_count, unsigned n_tiles) {
+    for (unsigned t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * kWavesPerBlock) {
+        LodPolicy<MASK> policy{cam, P, LodSource{groups, n_group}, n_mesh, mask, tile_count, n_inst};
+        // (t is wave-uniform; saying so keeps the tile's addresses in scalar registers, as in cull_mask_occ_kernel's early form)
+        cull_tile(inst, n_inst, ids_out, (unsigned)__builtin_amdgcn_readfirstlane((int)t), policy);
     }
 }
 
@@ -1509,6 +1614,8 @@ Pass1Plan pass1_plan(const VdCtx* ctx, unsigned n_inst, unsigned n_mesh, unsigne
     return p;
 }
 
+LodParams make_lod(const VdLodParams* p) { return LodParams{p->scale, p->min_distance, p->min_size}; }
+
 void launch_pad_tail(VdCtx* ctx, VdDrawIndexedIndirect* d_out, const unsigned* d_count, unsigned n_inst) {
     hipLaunchKernelGGL(pad_tail_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(kBlock), 0, ctx->stream, d_out, d_count, n_inst);
 }
@@ -1792,6 +1899,98 @@ int vd_cull_late_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     return cull_occ_list(ctx, kOccLate, "vd_cull_late", camera, d_meshes, n_mesh, d_instances, n_inst, d_pyramid, width, height,
                          d_prev_visible, d_visible_out, d_out, d_out_count, pad_tail);
+}
+
+// ---- level of detail (extension: include/voidin_abi.h, "Level of detail") ----------------------------------------------
+// What every LOD entry point refuses in the same words (`name` = the entry point).  Declared in vd_common.hpp (hidden
+// visibility): batch.hip checks its arguments with it.
+int vd_lod_check(VdCtx* ctx, const char* name, const VdCameraUniform* camera, const VdLodParams* params, const VdLodGroup* groups,
+                 uint32_t n_group, uint32_t n_mesh) {
+    const char* what = nullptr;
+    if (!camera || !params || !groups) what = "null camera/params/groups";
+    else if (n_group == 0 || n_mesh == 0) what = "n_group == 0 or n_mesh == 0";
+    else if (!(isfinite(params->scale) && params->scale >= 0.0f)) what = "params.scale must be finite and >= 0";
+    else if (!(isfinite(params->min_distance) && params->min_distance > 0.0f)) what = "params.min_distance must be finite and > 0";
+    else if (!(isfinite(params->min_size) && params->min_size >= 0.0f)) what = "params.min_size must be finite and >= 0";
+    if (!what) return VD_OK;
+    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
+    return VD_ERR_INVALID_ARG;
+}
+
+// Pass 1 of the LOD forms into ctx->scratch, laid out as launch_mask_pass lays it out (the two share the arena: whatever
+// the other left in the id table - another width included - every row that differs from this call's is rewritten).  The
+// id width follows the number of ROWS, n_mesh.  Starts the call's timer and records its stage boundary.
+int launch_lod_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdLodParams* params, const VdLodGroup* d_groups, uint32_t n_group,
+                    uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids,
+                    unsigned* out_id_bytes, unsigned** out_tile_count) {
+    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u, /*mask_first=*/true);
+    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, p.need);
+    if (rc) return rc;
+    vd_u64* d_mask = p.mask(ctx->scratch);
+    void* d_ids = p.ids(ctx->scratch);
+    unsigned* d_counts = p.counts(ctx->scratch);
+    vd_time_begin(ctx);
+    vd_dispatch_id(p.id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        hipLaunchKernelGGL((cull_mask_lod_kernel<IdT, true>), dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, make_cam(camera), make_lod(params),
+                           d_groups, n_group, n_mesh, d_instances, n_inst, d_mask, reinterpret_cast<IdT*>(d_ids), d_counts, p.n_mt);
+    });
+    vd_time_mid(ctx);
+    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = p.id_bytes; *out_tile_count = d_counts;
+    return VD_OK;
+}
+
+int vd_lod_ids_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params, const VdLodGroup* d_groups, uint32_t n_group,
+                   uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst, void* d_out_ids, uint32_t id_bytes) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    int rc = vd_lod_check(ctx, "vd_lod_ids", camera, &params, d_groups, n_group, n_mesh);
+    if (rc) return rc;
+    if (id_bytes != 1u && id_bytes != 2u && id_bytes != 4u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: id_bytes must be 1, 2 or 4");
+    if ((id_bytes == 1u && n_mesh > 256u) || (id_bytes == 2u && n_mesh > 65536u))
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: ids of id_bytes bytes cannot hold n_mesh - 1");
+    if (n_inst == 0) return VD_OK;
+    if (!d_instances || !d_out_ids) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: null instances/ids");
+    if (reinterpret_cast<uintptr_t>(d_out_ids) & 15u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: the id table must be 16-byte aligned");
+    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u);                 // the launch geometry; the id width is the caller's
+    const unsigned lds_bytes = kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * id_bytes);
+    vd_time_begin(ctx);
+    vd_dispatch_id(id_bytes, [&](auto id) {
+        using IdT = decltype(id);
+        hipLaunchKernelGGL((cull_mask_lod_kernel<IdT, false>), dim3(p.mb), dim3(kBlock), lds_bytes, ctx->stream, make_cam(camera), make_lod(&params),
+                           d_groups, n_group, n_mesh, d_instances, n_inst, (vd_u64*)nullptr, reinterpret_cast<IdT*>(d_out_ids), (unsigned*)nullptr,
+                           p.n_mt);
+    });
+    vd_time_end(ctx);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
+}
+
+// Always the two-launch form (three with pad_tail), at every size, like the views and the occlusion forms: pass 1 above,
+// then the unchanged expansion placed from the tile counts, reading d_meshes by the rows pass 1 chose.
+int vd_cull_compact_lod_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params, const VdLodGroup* d_groups, uint32_t n_group,
+                            const VdMeshInfo* d_meshes, uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst,
+                            VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    int rc = vd_lod_check(ctx, "vd_cull_compact_lod", camera, &params, d_groups, n_group, n_mesh);
+    if (rc) return rc;
+    if (!d_meshes || !d_out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null meshes/count");
+    if (n_inst == 0) {
+        VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_count, 0, 4, ctx->stream));
+        return VD_OK;
+    }
+    if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null instances/out");
+    vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
+    rc = launch_lod_pass(ctx, camera, &params, d_groups, n_group, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
+    if (rc) return rc;
+    const unsigned n_words = (n_inst + 63u) / 64u;
+    rc = launch_expand(ctx, d_mask, n_words, n_words, n_inst, n_inst, 0u, d_ids, id_bytes, d_meshes, n_mesh, d_out, d_out_count, d_tile_count);
+    if (rc) return rc;
+    vd_time_end(ctx);
+    if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
 }
 
 int vd_cull_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
@@ -2100,6 +2299,56 @@ int vd_cull_compact_hiz(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshI
     VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->host_pinned[0] > n_inst) VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_hiz: the expansion wrote no count");
+    *out_count = ctx->host_pinned[0];
+    const size_t n_copy = pad_tail ? n_inst : *out_count;
+    if (n_copy) {
+        VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n_copy * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
+        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return VD_OK;
+}
+
+// host pointers, staged like vd_cull_compact: instances; a 64-byte header that takes the count, the groups and the meshes;
+// n_inst commands.  The group table is on the host here, so it is validated (the _dev forms clamp instead).
+int vd_cull_compact_lod(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params, const VdLodGroup* groups, uint32_t n_group,
+                        const VdMeshInfo* meshes, uint32_t n_mesh, const VdInstance* instances, uint32_t n_inst,
+                        VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    int rc = vd_lod_check(ctx, "vd_cull_compact_lod", camera, &params, groups, n_group, n_mesh);
+    if (rc) return rc;
+    if (!meshes || !out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null meshes/count");
+    for (uint32_t g = 0; g < n_group; ++g) {
+        const uint32_t nl = groups[g].n_lods;
+        if (nl < 1u || nl > VD_LOD_MAX || (uint64_t)groups[g].first_row + nl > (uint64_t)n_mesh) {
+            snprintf(ctx->err, sizeof(ctx->err), "vd_cull_compact_lod: group %u: n_lods must be 1..VD_LOD_MAX and first_row + n_lods <= n_mesh", g);
+            return VD_ERR_INVALID_ARG;
+        }
+    }
+    if (n_inst > 0 && (!instances || !out)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null instances/out");
+    *out_count = 0;                                                  // (a refused call writes nothing)
+    if (n_inst == 0) return VD_OK;
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t mesh_off = 64 + (size_t)n_group * sizeof(VdLodGroup);
+    rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
+    if (rc) return rc;
+    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, mesh_off + (size_t)n_mesh * sizeof(VdMeshInfo));
+    if (rc) return rc;
+    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16);
+    if (rc) return rc;
+    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(ctx->stage_aux);
+    VdLodGroup* dg = reinterpret_cast<VdLodGroup*>(reinterpret_cast<char*>(ctx->stage_aux) + 64);
+    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + mesh_off);
+    VdDrawIndexedIndirect* dout = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(dg, groups, (size_t)n_group * sizeof(VdLodGroup), hipMemcpyHostToDevice, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
+    rc = vd_cull_compact_lod_dev(ctx, camera, params, dg, n_group, dm, n_mesh, di, n_inst, dout, d_count, pad_tail);
+    if (rc) return rc;
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->host_pinned[0] > n_inst) VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_lod: the expansion wrote no count");
     *out_count = ctx->host_pinned[0];
     const size_t n_copy = pad_tail ? n_inst : *out_count;
     if (n_copy) {

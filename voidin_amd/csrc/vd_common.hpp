@@ -112,6 +112,15 @@ extern "C" __attribute__((visibility("hidden"))) int launch_mask_pass(VdCtx* ctx
                                                                       const VdInstance* d_instances, uint32_t n_inst, unsigned long long** out_mask, void** out_ids,
                                                                       unsigned* out_id_bytes, unsigned** out_tile_count);
 
+// cull.hip: the same for the LOD forms (cull_mask_lod_kernel; the ids are rows of the mesh table, their width by n_mesh),
+// and the argument check every LOD entry point shares (`name` prefixes the message).  batch.hip groups by row from this pass.
+extern "C" __attribute__((visibility("hidden"))) int launch_lod_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdLodParams* params,
+                                                                     const VdLodGroup* d_groups, uint32_t n_group, uint32_t n_mesh,
+                                                                     const VdInstance* d_instances, uint32_t n_inst, unsigned long long** out_mask,
+                                                                     void** out_ids, unsigned* out_id_bytes, unsigned** out_tile_count);
+extern "C" __attribute__((visibility("hidden"))) int vd_lod_check(VdCtx* ctx, const char* name, const VdCameraUniform* camera, const VdLodParams* params,
+                                                                  const VdLodGroup* groups, uint32_t n_group, uint32_t n_mesh);
+
 // Calls f with a value of the mesh-id type of that width - unsigned char, unsigned short or unsigned: the one place
 // where an id width (1, 2 or 4 bytes; checked by the caller) picks a kernel instantiation.
 //   vd_dispatch_id(id_bytes, [&](auto id) { using IdT = decltype(id); hipLaunchKernelGGL(some_kernel<IdT>, ...); });

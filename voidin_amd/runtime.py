@@ -159,6 +159,31 @@ class Context:
         self._chk(self.lib.vd_cull_batch_dev(self.h, cam.ctypes.data, abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst,
                                              abi.ptr(d_out_cmds), abi.ptr(d_out_instance_ids), abi.ptr(d_count)))
 
+    # level of detail: the row of the mesh table an instance is drawn with (voidin_abi.h "Level of detail")
+    def lod_ids_dev(self, camera, params, d_groups, n_group, n_mesh, d_inst, n_inst, d_out_ids, id_bytes=None):
+        """vd_lod_ids_dev: d_out_ids[i] = the d_meshes row of instance i, for every instance (no visibility test)."""
+        if id_bytes is None:
+            id_bytes = d_out_ids.element_size() if hasattr(d_out_ids, "element_size") else 4
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
+        self._chk(self.lib.vd_lod_ids_dev(self.h, cam.ctypes.data, abi.lod_params(params), abi.ptr(d_groups), n_group, n_mesh,
+                                          abi.ptr(d_inst), n_inst, abi.ptr(d_out_ids), id_bytes))
+
+    def cull_compact_lod_dev(self, camera, params, d_groups, n_group, d_meshes, n_mesh, d_inst, n_inst, d_out, d_count,
+                             pad_tail: bool = False):
+        """vd_cull_compact_lod_dev: the ordered list of the drawn instances, each with the command of its LOD row."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
+        self._chk(self.lib.vd_cull_compact_lod_dev(self.h, cam.ctypes.data, abi.lod_params(params), abi.ptr(d_groups), n_group,
+                                                   abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst, abi.ptr(d_out),
+                                                   abi.ptr(d_count), int(pad_tail)))
+
+    def cull_batch_lod_dev(self, camera, params, d_groups, n_group, d_meshes, n_mesh, d_inst, n_inst, d_out_cmds,
+                           d_out_instance_ids, d_count):
+        """vd_cull_batch_lod_dev: one command per row of d_meshes (mesh x LOD), the drawn instances' ids grouped by row."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
+        self._chk(self.lib.vd_cull_batch_lod_dev(self.h, cam.ctypes.data, abi.lod_params(params), abi.ptr(d_groups), n_group,
+                                                 abi.ptr(d_meshes), n_mesh, abi.ptr(d_inst), n_inst, abi.ptr(d_out_cmds),
+                                                 abi.ptr(d_out_instance_ids), abi.ptr(d_count)))
+
     def compact_draws_dev(self, d_in, n, d_out, d_count):
         self._chk(self.lib.vd_compact_draws_dev(self.h, abi.ptr(d_in), n, abi.ptr(d_out), abi.ptr(d_count)))
 
@@ -197,6 +222,21 @@ class Context:
         self._chk(self.lib.vd_cull_compact(self.h, cam.ctypes.data, meshes.ctypes.data, len(meshes),
                                            instances.ctypes.data, len(instances), out.ctypes.data,
                                            C.addressof(cnt), int(pad_tail)))
+        return out, cnt.value
+
+    def cull_compact_lod(self, camera, params, groups, meshes, instances, pad_tail=False):
+        """Host arrays in, (list, count) out; the group table is validated (VD_ERR_INVALID_ARG).  Only [0, count) is
+        defined (everything with pad_tail)."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA)
+        groups = np.ascontiguousarray(groups, dtype=abi.LOD_GROUP)
+        meshes = np.ascontiguousarray(meshes, dtype=abi.MESH_INFO)
+        instances = np.ascontiguousarray(instances, dtype=abi.INSTANCE)
+        out = np.zeros(len(instances), dtype=abi.DRAW)
+        out.view(np.uint8)[:] = 0xAB
+        cnt = C.c_uint32(0)
+        self._chk(self.lib.vd_cull_compact_lod(self.h, cam.ctypes.data, abi.lod_params(params), groups.ctypes.data, len(groups),
+                                               meshes.ctypes.data, len(meshes), instances.ctypes.data, len(instances),
+                                               out.ctypes.data, C.addressof(cnt), int(pad_tail)))
         return out, cnt.value
 
     def cull_batch(self, camera, meshes, instances):
@@ -544,6 +584,19 @@ class EmitDraws:
         visible_ids_buf[0..count) = the survivors' instance ids grouped by mesh, which the vertex shader indexes with
         instance_index; the consumer is multi_draw_indexed_indirect(draw_cmd_buffer, 0, n_mesh)."""
         self.ctx.cull_batch_dev(camera, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer, visible_ids_buf, draw_count_buf)
+
+    def record_lod(self, camera, lod_params, lod_group_buf, n_group, mesh_info_buf, n_mesh, instances_buf, n_inst, draw_cmd_buffer,
+                   draw_count_buf, pad_tail=False):
+        """record_compacted with a level of detail per instance: instances name a GROUP, the command comes from the row
+        of mesh_info_buf the projected size picks; instances smaller than lod_params.min_size are dropped."""
+        self.ctx.cull_compact_lod_dev(camera, lod_params, lod_group_buf, n_group, mesh_info_buf, n_mesh, instances_buf, n_inst,
+                                      draw_cmd_buffer, draw_count_buf, pad_tail)
+
+    def record_batched_lod(self, camera, lod_params, lod_group_buf, n_group, mesh_info_buf, n_mesh, instances_buf, n_inst,
+                           draw_cmd_buffer, visible_ids_buf, draw_count_buf):
+        """record_batched over LOD rows: draw_cmd_buffer[0..n_mesh) = one command per (mesh, LOD) row."""
+        self.ctx.cull_batch_lod_dev(camera, lod_params, lod_group_buf, n_group, mesh_info_buf, n_mesh, instances_buf, n_inst,
+                                    draw_cmd_buffer, visible_ids_buf, draw_count_buf)
 
     def record_hiz(self, camera, mesh_info_buf, n_mesh, instances_buf, n_inst, pyramid_buf, width, height, draw_cmd_buffer,
                    draw_count_buf, pad_tail=False):

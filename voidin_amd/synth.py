@@ -348,3 +348,51 @@ def harness_scene(build_fn, big=(1024, 256), small_res=100):
     insts = [instance_from_matrix(mat((0, 2, 0), 5.0 / ext, math.pi / 2), 0)]
     insts += [instance_from_matrix(mat((x, y, 0), 3.0), 1) for x, y in ((8, 8), (-8, 8), (8, -8), (-8, -8))]
     return np.array(insts, dtype=abi.INSTANCE), infos, np.concatenate(B), np.concatenate(V), np.concatenate(I)
+
+
+# --- level of detail (include/voidin_abi.h "Level of detail") ---------------------------------
+
+def lod_groups(meshes: np.ndarray, n_lods: int = 4, switch_size=(64.0, 16.0, 4.0), index_ratio: float = 4.0):
+    """(rows, groups) from a mesh table: mesh g becomes group g = n_lods consecutive rows, finest first.  LOD k keeps
+    index_count / index_ratio**k indices (a multiple of 3, at least 3); the rows' index ranges are laid out one behind the
+    other as MeshPool::add would (vertex_offset = base_index / 3); every row carries the mesh's box, and so does the
+    group.  switch_size: n_lods - 1 projected sizes (the unit VdLodParams.scale gives - pixels of radius, say), one set
+    for all groups or one per group."""
+    meshes = np.ascontiguousarray(meshes, dtype=abi.MESH_INFO)
+    n = len(meshes)
+    if not 1 <= n_lods <= abi.LOD_MAX:
+        raise ValueError("n_lods must be 1..LOD_MAX")
+    sw = np.asarray(switch_size, dtype=np.float32)
+    sw = np.zeros((n, 0), np.float32) if n_lods == 1 else np.broadcast_to(sw.reshape(-1, sw.shape[-1])[:, : n_lods - 1], (n, n_lods - 1))
+    rows = np.zeros(n * n_lods, dtype=abi.MESH_INFO)
+    k = np.tile(np.arange(n_lods), n)
+    src = np.repeat(np.arange(n), n_lods)
+    ic = np.maximum((meshes["index_count"][src].astype(np.float64) / float(index_ratio) ** k).astype(np.int64) // 3 * 3, 3)
+    base = np.concatenate([[0], np.cumsum(ic)[:-1]])
+    if base[-1] + ic[-1] > 0xFFFFFFFF:
+        raise ValueError("the rows' index ranges overflow 32 bits")
+    rows["min"], rows["max"] = meshes["min"][src], meshes["max"][src]
+    rows["index_count"], rows["base_index"] = ic.astype(np.uint32), base.astype(np.uint32)
+    rows["vertex_offset"], rows["bvh_index"] = (base // 3).astype(np.int32), (2 * base // 3).astype(np.uint32)
+    groups = np.zeros(n, dtype=abi.LOD_GROUP)
+    groups["min"], groups["max"] = meshes["min"], meshes["max"]
+    groups["first_row"] = np.arange(n, dtype=np.uint32) * n_lods
+    groups["n_lods"] = n_lods
+    groups["switch_size"][:, : n_lods - 1] = sw
+    return rows, groups
+
+
+def lod_size_estimate(cam: np.ndarray, groups: np.ndarray, inst: np.ndarray, scale: float, min_distance: float) -> np.ndarray:
+    """The projected size of the definition in float64 - good for choosing thresholds (quantiles of it populate every
+    level), NOT a restatement of the float32 contract."""
+    cam = np.asarray(cam, dtype=abi.CAMERA).reshape(-1)[0]
+    V = cam["view"].astype(np.float64).reshape(4, 4).T                      # column-major -> V[row][col]
+    G = groups[np.minimum(inst["mesh"], len(groups) - 1)]
+    T = inst["transform"].astype(np.float64).reshape(-1, 4, 4)              # T[i][col][row]
+    c0 = np.concatenate([(G["max"].astype(np.float64) + G["min"]) / 2, np.ones((len(inst), 1))], axis=1)
+    world = np.einsum("icr,ic->ir", T, c0)
+    z = world @ V[2]
+    s = np.sqrt((T[:, :3, :3] ** 2).sum(axis=2)).max(axis=1)
+    r = np.sqrt(((G["max"].astype(np.float64) - G["min"]) ** 2).sum(axis=1)) * 0.5 * s
+    with np.errstate(all="ignore"):
+        return r * scale / np.fmax(-z, min_distance)
