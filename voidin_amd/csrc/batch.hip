@@ -268,6 +268,8 @@ int ensure_batch_scratch(VdCtx* ctx, unsigned n_mesh) {
     return vd_ensure(ctx, &ctx->batch_scratch, &ctx->batch_scratch_bytes, need);
 }
 
+const char kNoCamMeshesCmdsCount[] = "vd_cull_batch: null camera/meshes/cmds/count";
+const char kNoInstIds[] = "vd_cull_batch: null instances/instance-ids";
 const char* const kMeshLimitMsg =
     ": n_mesh must be 1..VD_BATCH_MAX_MESHES (4096) - the limit of the one-digit counting sort (a wave-private table of n_mesh "
     "counters in LDS); a second sort digit is future work";
@@ -314,12 +316,12 @@ int vd_cull_batch_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInf
                       uint32_t* d_out_instance_ids, uint32_t* d_out_count) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!camera || !d_meshes || !d_out_cmds || !d_out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_batch: null camera/meshes/cmds/count");
+    if (!camera || !d_meshes || !d_out_cmds || !d_out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, kNoCamMeshesCmdsCount);
     if (n_mesh == 0 || n_mesh > VD_BATCH_MAX_MESHES) {
         snprintf(ctx->err, sizeof(ctx->err), "vd_cull_batch%s", kMeshLimitMsg);
         return VD_ERR_INVALID_ARG;
     }
-    if (n_inst > 0 && (!d_instances || !d_out_instance_ids)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_batch: null instances/instance-ids");
+    if (n_inst > 0 && (!d_instances || !d_out_instance_ids)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, kNoInstIds);
     if (n_inst == 0) {
         launch_empty(ctx, d_meshes, n_mesh, d_out_cmds, d_out_count);
         VD_HIP_CHECK(ctx, hipGetLastError());
@@ -328,10 +330,9 @@ int vd_cull_batch_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInf
     int rc = ensure_batch_scratch(ctx, n_mesh);
     if (rc) return rc;
     // pass 1, unchanged: bitmask + clamped mesh ids (+ tile counts, not needed here) in ctx->scratch; stage boundary behind it
-    vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
-    rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
-    if (rc) return rc;
-    rc = launch_batch(ctx, d_mask, n_inst, d_ids, id_bytes, d_meshes, n_mesh, d_out_cmds, d_out_instance_ids, d_out_count);
+    const VdPass1 r = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst);
+    if (r.rc) return r.rc;
+    rc = launch_batch(ctx, r.mask, n_inst, r.ids, r.id_bytes, d_meshes, n_mesh, d_out_cmds, d_out_instance_ids, d_out_count);
     if (rc) return rc;
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
@@ -360,44 +361,36 @@ int vd_cull_batch_lod_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams
     }
     rc = ensure_batch_scratch(ctx, n_mesh);
     if (rc) return rc;
-    vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
-    rc = launch_lod_pass(ctx, camera, &params, d_groups, n_group, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
-    if (rc) return rc;
-    rc = launch_batch(ctx, d_mask, n_inst, d_ids, id_bytes, d_meshes, n_mesh, d_out_cmds, d_out_instance_ids, d_out_count);
+    const VdPass1 r = launch_lod_pass(ctx, camera, &params, d_groups, n_group, n_mesh, d_instances, n_inst);
+    if (r.rc) return r.rc;
+    rc = launch_batch(ctx, r.mask, n_inst, r.ids, r.id_bytes, d_meshes, n_mesh, d_out_cmds, d_out_instance_ids, d_out_count);
     if (rc) return rc;
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
 
-// host pointers: staged like vd_cull_compact - instances; meshes behind a 16-byte header that takes the count; the n_mesh
-// commands followed by n_inst id words
+// host pointers: staged like vd_cull_compact (vd_stage) - instances; meshes behind a 16-byte header that takes the count;
+// the n_mesh commands followed by n_inst id words, which is not the shape vd_fetch_lists copies back
 int vd_cull_batch(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* meshes, uint32_t n_mesh, const VdInstance* instances,
                   uint32_t n_inst, VdDrawIndexedIndirect* out_cmds, uint32_t* out_instance_ids, uint32_t* out_count) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!camera || !meshes || !out_cmds || !out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_batch: null camera/meshes/cmds/count");
+    if (!camera || !meshes || !out_cmds || !out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, kNoCamMeshesCmdsCount);
     if (n_mesh == 0 || n_mesh > VD_BATCH_MAX_MESHES) {
         snprintf(ctx->err, sizeof(ctx->err), "vd_cull_batch%s", kMeshLimitMsg);
         return VD_ERR_INVALID_ARG;
     }
-    if (n_inst > 0 && (!instances || !out_instance_ids)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_batch: null instances/instance-ids");
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance) + 16);
-    if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, (size_t)n_mesh * sizeof(VdMeshInfo) + 16);
-    if (rc) return rc;
+    if (n_inst > 0 && (!instances || !out_instance_ids)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, kNoInstIds);
     const size_t ids_off = ((size_t)n_mesh * sizeof(VdDrawIndexedIndirect) + 15) & ~(size_t)15;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, ids_off + (size_t)n_inst * 4 + 16);
+    VdBlob m = {meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 16, nullptr};
+    VdStaged s;
+    int rc = vd_stage(ctx, instances, n_inst, 16, &m, 1, ids_off + (size_t)n_inst * 4 + 16, &s);
     if (rc) return rc;
-    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(ctx->stage_aux);
-    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + 16);
-    VdDrawIndexedIndirect* d_cmds = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
-    uint32_t* d_ids = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctx->stage_out) + ids_off);
-    if (n_inst) VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
-    rc = vd_cull_batch_dev(ctx, camera, dm, n_mesh, di, n_inst, d_cmds, d_ids, d_count);
+    uint32_t* d_count = s.counts;
+    VdDrawIndexedIndirect* d_cmds = s.out;
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(s.out) + ids_off);
+    rc = vd_cull_batch_dev(ctx, camera, reinterpret_cast<VdMeshInfo*>(m.dev), n_mesh, s.inst, n_inst, d_cmds, d_ids, d_count);
     if (rc) return rc;
     VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     VD_HIP_CHECK(ctx, hipMemcpyAsync(out_cmds, d_cmds, (size_t)n_mesh * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));

@@ -1574,34 +1574,40 @@ HizView make_hiz(const float* d_pyramid, unsigned width, unsigned height, const 
     return hz;
 }
 
+// The launch geometry of pass 1 for ids of id_bytes bytes: a wave per 1024-instance tile, grid-stride beyond 3 workgroups
+// per CU, and the dynamic LDS of a workgroup (slabs + the tile's ids).
+struct Pass1Grid { unsigned n_mt, mb, lds_bytes; };
+Pass1Grid pass1_grid(const VdCtx* ctx, unsigned n_inst, unsigned id_bytes) {
+    Pass1Grid g;
+    g.n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
+    g.mb = vd_blocks(ctx, g.n_mt, kWavesPerBlock, 3u);
+    g.lds_bytes = kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * id_bytes);
+    return g;
+}
+
 // Pass 1 for n_views cameras over n_inst instances: the id width, the tile and launch geometry, and where its outputs lie
 // in the arena - [id table | n_views masks | n_views count tables], the id table at offset 0 whatever n_views is.
-// ctx->scratch keeps its older order, [mask | id table | counts] (mask_first): the common one would round the id table up
-// to 256 bytes and so need up to 240 bytes more than it has today.  What the expansion relies on holds in both: the id
-// table dword-aligned (16 bytes for full tiles: tiles are 1024 ids), every mask 256-byte aligned, every count table
-// 16-byte aligned and padded to whole groups of 4 entries (tile_prefix_partial).
-struct Pass1Plan {
-    unsigned id_bytes, n_words, n_mt;     // id width by n_mesh; mask words; 1024-instance tiles
-    unsigned mb, lds_bytes;               // workgroups (a wave per tile, grid-stride beyond 3 per CU) and their dynamic LDS
+// ctx->scratch keeps its older order, [mask | id table | counts] (kMaskFirst).  Not for the 240 bytes it saves: with the
+// common order there, single-view pass 1 timed alone measured about 1.5 % slower (profiles/cull_host_layer.md, 4b).
+// What the expansion relies on holds in both: the id table dword-aligned (16 bytes for full tiles: tiles are 1024 ids),
+// every mask 256-byte aligned, every count table 16-byte aligned and padded to whole groups of 4 entries
+// (tile_prefix_partial).
+struct Pass1Plan : Pass1Grid {
+    unsigned id_bytes, n_words;           // id width by n_mesh; mask words
     size_t ids_off, mask_off, counts_off, need;     // bytes
     size_t mask_stride, count_stride;               // words between two views' masks / entries between their count tables
-    void* ids(void* arena) const { return reinterpret_cast<char*>(arena) + ids_off; }
-    vd_u64* mask(void* arena) const { return reinterpret_cast<vd_u64*>(reinterpret_cast<char*>(arena) + mask_off); }
-    unsigned* counts(void* arena) const { return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(arena) + counts_off); }
 };
 
-Pass1Plan pass1_plan(const VdCtx* ctx, unsigned n_inst, unsigned n_mesh, unsigned n_views, bool mask_first = false) {
+enum Pass1Layout { kIdsFirst, kMaskFirst };     // the common order / ctx->scratch's
+Pass1Plan pass1_plan(const VdCtx* ctx, unsigned n_inst, unsigned n_mesh, unsigned n_views, Pass1Layout layout) {
     Pass1Plan p;
-    p.id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);
+    p.id_bytes = vd_id_bytes(n_mesh);
+    static_cast<Pass1Grid&>(p) = pass1_grid(ctx, n_inst, p.id_bytes);
     p.n_words = (n_inst + 63u) / 64u;
-    p.n_mt = (n_inst + kWave * kMaskRounds - 1) / (kWave * kMaskRounds);
-    p.mb = (p.n_mt + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (p.mb > (unsigned)ctx->num_cus * 3u) p.mb = (unsigned)ctx->num_cus * 3u;
-    p.lds_bytes = kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * p.id_bytes);
     const size_t ids_bytes = (size_t)n_inst * p.id_bytes, mask_bytes = ((size_t)p.n_words * 8 + 255) & ~(size_t)255;
     p.mask_stride = mask_bytes / 8;
     p.count_stride = ((size_t)p.n_mt + 3) & ~(size_t)3;
-    if (mask_first) {
+    if (layout == kMaskFirst) {
         p.mask_off = 0;
         p.ids_off = n_views * mask_bytes;
         p.counts_off = (p.ids_off + ids_bytes + 15) & ~(size_t)15;
@@ -1614,10 +1620,71 @@ Pass1Plan pass1_plan(const VdCtx* ctx, unsigned n_inst, unsigned n_mesh, unsigne
     return p;
 }
 
+// Pass 1 of every split form, in order: plan, arena, the call's timer, `launch(IdT(), plan, r)` with the id type of the
+// plan's width (the callable launches ONE kernel with p.mb workgroups and p.lds_bytes of LDS, writing r.ids / r.mask /
+// r.counts), the stage boundary.  The only caller of pass1_plan.
+template <typename F>
+VdPass1 run_pass1(VdCtx* ctx, void** arena, size_t* arena_bytes, Pass1Layout layout, unsigned n_inst, unsigned n_mesh, unsigned n_views, F&& launch) {
+    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, n_views, layout);
+    VdPass1 r = {};
+    r.rc = vd_ensure(ctx, arena, arena_bytes, p.need);
+    if (r.rc) return r;
+    char* base = reinterpret_cast<char*>(*arena);
+    r.ids = base + p.ids_off;
+    r.mask = reinterpret_cast<vd_u64*>(base + p.mask_off);
+    r.counts = reinterpret_cast<unsigned*>(base + p.counts_off);
+    r.id_bytes = p.id_bytes; r.n_words = p.n_words; r.n_mt = p.n_mt;
+    r.mask_stride = p.mask_stride; r.count_stride = p.count_stride;
+    vd_time_begin(ctx);
+    vd_dispatch_id(p.id_bytes, [&](auto id) { launch(id, p, r); });
+    vd_time_mid(ctx);
+    return r;
+}
+
 LodParams make_lod(const VdLodParams* p) { return LodParams{p->scale, p->min_distance, p->min_size}; }
 
 void launch_pad_tail(VdCtx* ctx, VdDrawIndexedIndirect* d_out, const unsigned* d_count, unsigned n_inst) {
     hipLaunchKernelGGL(pad_tail_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(kBlock), 0, ctx->stream, d_out, d_count, n_inst);
+}
+
+// Refusals that a host-pointer form and its _dev form (or two _dev forms) word alike, each set of words once: the text
+// behind the entry point's name, or null when the arguments pass.
+int fail_named(VdCtx* ctx, const char* name, const char* text) {
+    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, text);
+    return VD_ERR_INVALID_ARG;
+}
+const char kNoCamMeshes[] = "null camera/meshes or n_mesh == 0";
+const char kNoCamMeshesCount[] = "null camera/meshes/count or n_mesh == 0";
+const char kNoInstOut[] = "null instances/out";
+const char kNoLodMeshesCount[] = "null meshes/count";
+const char* hiz_refusal(const VdCameraUniform* camera, uint32_t width, uint32_t height, VdHizLayout* L) {
+    if (vd_hiz_layout(width, height, L)) return "bad pyramid size";
+    if (!(camera->projection[11] == -1.0f && camera->projection[15] == 0.0f))
+        return "projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)";
+    return nullptr;
+}
+const char* views_refusal(const void* cameras, const void* meshes, uint32_t n_mesh, const void* counts, uint32_t n_views, uint64_t out_stride,
+                          uint32_t n_inst) {
+    if (!cameras || !meshes || n_mesh == 0 || !counts) return "null cameras/meshes/counts or n_mesh == 0";
+    if (n_views == 0 || n_views > (uint32_t)VD_MAX_VIEWS) return "n_views must be 1..VD_MAX_VIEWS";
+    if (out_stride < n_inst) return "out_stride < n_inst";
+    return nullptr;
+}
+
+// The tail of every list form behind pass 1: the expansion of n_views masks, each placed from its own tile counts, into
+// d_out + v * out_stride; the call's timer; the pads; the launch check.  first_instance != 0: a shard's list.
+int finish_lists(VdCtx* ctx, const VdPass1& r, unsigned n_views, const VdMeshInfo* d_meshes, unsigned n_mesh, unsigned n_inst,
+                 unsigned first_instance, VdDrawIndexedIndirect* d_out, size_t out_stride, unsigned* d_out_counts, int pad_tail) {
+    for (unsigned v = 0; v < n_views; ++v) {
+        int rc = launch_expand(ctx, r.mask + (size_t)v * r.mask_stride, r.n_words, r.n_words, n_inst, n_inst, first_instance, r.ids, r.id_bytes,
+                               d_meshes, n_mesh, d_out + (size_t)v * out_stride, d_out_counts + v, r.counts + (size_t)v * r.count_stride);
+        if (rc) return rc;
+    }
+    vd_time_end(ctx);
+    if (pad_tail)
+        for (unsigned v = 0; v < n_views; ++v) launch_pad_tail(ctx, d_out + (size_t)v * out_stride, d_out_counts + v, n_inst);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
 }
 
 }  // namespace
@@ -1631,26 +1698,15 @@ int vd_cull_emit_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
 }
 
 // Pass 1 of the split forms: instances -> one bit + a compact mesh id each, and the survivors of every 1024-instance
-// tile (*out_tile_count, padded to whole 16-byte groups; the emit path ignores it), in ctx scratch.  Declared in
-// vd_common.hpp (hidden visibility): batch.hip runs the same pass.
-int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                            const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids, unsigned* out_id_bytes,
-                            unsigned** out_tile_count) {
-    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u, /*mask_first=*/true);
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, p.need);
-    if (rc) return rc;
-    vd_u64* d_mask = p.mask(ctx->scratch);
-    void* d_ids = p.ids(ctx->scratch);
-    unsigned* d_counts = p.counts(ctx->scratch);
-    vd_time_begin(ctx);
-    vd_dispatch_id(p.id_bytes, [&](auto id) {
+// tile (padded to whole 16-byte groups; the emit path ignores them), in ctx->scratch.  Declared in vd_common.hpp (hidden
+// visibility): batch.hip runs the same pass.
+VdPass1 launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                         const VdInstance* d_instances, uint32_t n_inst) {
+    return run_pass1(ctx, &ctx->scratch, &ctx->scratch_bytes, kMaskFirst, n_inst, n_mesh, 1u, [&](auto id, const Pass1Plan& p, const VdPass1& o) {
         using IdT = decltype(id);
         hipLaunchKernelGGL(cull_mask_tiled_kernel<IdT>, dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, make_cam(camera), d_meshes, n_mesh,
-                           d_instances, n_inst, d_mask, reinterpret_cast<IdT*>(d_ids), d_counts, p.n_mt);
+                           d_instances, n_inst, o.mask, reinterpret_cast<IdT*>(o.ids), o.counts, p.n_mt);
     });
-    vd_time_mid(ctx);
-    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = p.id_bytes; *out_tile_count = d_counts;
-    return VD_OK;
 }
 
 int vd_cull_emit_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
@@ -1658,36 +1714,30 @@ int vd_cull_emit_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMe
                            VdDrawIndexedIndirect* d_out) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!camera || !d_meshes || n_mesh == 0) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null camera/meshes or n_mesh == 0");
+    if (!camera || !d_meshes || n_mesh == 0) return fail_named(ctx, "vd_cull_emit", kNoCamMeshes);
     if (n_inst == 0) return VD_OK;
-    if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null instances/out");
+    if (!d_instances || !d_out) return fail_named(ctx, "vd_cull_emit", kNoInstOut);
     if (ctx->option(VD_OPT_CULL_VARIANT, 0) <= 0 && n_inst >= ctx->split_min) {
         // split form, as for the compacted list: the 20-byte stores leave the read stream
-        vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
-        int rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
-        if (rc) return rc;
-        const unsigned quads = (n_inst + 3u) / 4u;
-        unsigned eb = (quads + kBlock - 1) / kBlock;
-        if (eb > (unsigned)ctx->num_cus * 16u) eb = (unsigned)ctx->num_cus * 16u;
-        if (id_bytes == 1u) {
-            const unsigned n_words = (n_inst + 63u) / 64u;
-            hipLaunchKernelGGL(emit_all_u8_kernel, dim3((n_words + kChunkWords - 1) / kChunkWords), dim3(kBlock), 0, ctx->stream, d_mask,
-                               n_words, n_inst, first_instance, reinterpret_cast<const unsigned char*>(d_ids), d_meshes, n_mesh, d_out);
+        const VdPass1 r = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst);
+        if (r.rc) return r.rc;
+        if (r.id_bytes == 1u) {
+            hipLaunchKernelGGL(emit_all_u8_kernel, dim3((r.n_words + kChunkWords - 1) / kChunkWords), dim3(kBlock), 0, ctx->stream, r.mask,
+                               r.n_words, n_inst, first_instance, reinterpret_cast<const unsigned char*>(r.ids), d_meshes, n_mesh, d_out);
         } else {
+            const unsigned eb = vd_blocks(ctx, (n_inst + 3u) / 4u, kBlock, 16u);
             auto launch = [&](auto kernel, auto ids) {
-                hipLaunchKernelGGL(kernel, dim3(eb), dim3(kBlock), 0, ctx->stream, d_mask, ids, d_meshes, n_mesh, n_inst, first_instance, d_out);
+                hipLaunchKernelGGL(kernel, dim3(eb), dim3(kBlock), 0, ctx->stream, r.mask, ids, d_meshes, n_mesh, n_inst, first_instance, d_out);
             };
-            if (id_bytes == 2u) launch(emit_from_mask_kernel<unsigned short>, reinterpret_cast<const unsigned short*>(d_ids));
-            else launch(emit_from_mask_kernel<unsigned>, reinterpret_cast<const unsigned*>(d_ids));
+            if (r.id_bytes == 2u) launch(emit_from_mask_kernel<unsigned short>, reinterpret_cast<const unsigned short*>(r.ids));
+            else launch(emit_from_mask_kernel<unsigned>, reinterpret_cast<const unsigned*>(r.ids));
         }
         vd_time_end(ctx);
         VD_HIP_CHECK(ctx, hipGetLastError());
         return VD_OK;
     }
     const unsigned n_wave_tiles = (n_inst + kWave - 1) / kWave;
-    unsigned blocks = (n_wave_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned cap = (unsigned)ctx->num_cus * 4u;   // 4 x 36 KB LDS slabs per CU
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = vd_blocks(ctx, n_wave_tiles, kWavesPerBlock, 4u);   // 4 x 36 KB LDS slabs per CU
     vd_time_begin(ctx);
     hipLaunchKernelGGL(emit_draws_kernel, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream,
                        make_cam(camera), d_meshes, n_mesh, d_instances, n_inst, d_out, n_wave_tiles, first_instance);
@@ -1708,13 +1758,12 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
                               VdDrawIndexedIndirect* d_out, uint32_t* d_out_count, int pad_tail) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!camera || !d_meshes || n_mesh == 0 || !d_out_count)
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact: null camera/meshes/count or n_mesh == 0");
+    if (!camera || !d_meshes || n_mesh == 0 || !d_out_count) return fail_named(ctx, "vd_cull_compact", kNoCamMeshesCount);
     if (n_inst == 0) {
         VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_count, 0, 4, ctx->stream));
         return VD_OK;
     }
-    if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact: null instances/out");
+    if (!d_instances || !d_out) return fail_named(ctx, "vd_cull_compact", kNoInstOut);
     const int variant = (int)ctx->option(VD_OPT_CULL_VARIANT, 0);
     vd_u64* ticket; vd_u64* states;
     int rc = vd_scan_check_fault(ctx);       // an EARLIER launch's scan gave up: said once, here
@@ -1726,17 +1775,9 @@ int vd_cull_compact_shard_dev(VdCtx* ctx, const VdCameraUniform* camera, const V
         // command list, placing each chunk from the tile counts: two launches, no scan kernel.  Mixing
         // the command stores into the read stream costs more than the 1-5 B/instance round trip
         // (A/B: profiles/).
-        vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
-        rc = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
-        if (rc) return rc;
-        const unsigned n_words = (n_inst + 63u) / 64u;
-        rc = launch_expand(ctx, d_mask, n_words, n_words, n_inst, n_inst, first_instance, d_ids, id_bytes, d_meshes, n_mesh,
-                           d_out, d_out_count, d_tile_count);
-        if (rc) return rc;
-        vd_time_end(ctx);
-        if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
-        VD_HIP_CHECK(ctx, hipGetLastError());
-        return VD_OK;
+        const VdPass1 r = launch_mask_pass(ctx, camera, d_meshes, n_mesh, d_instances, n_inst);
+        if (r.rc) return r.rc;
+        return finish_lists(ctx, r, 1u, d_meshes, n_mesh, n_inst, first_instance, d_out, 0, d_out_count, pad_tail);
     }
 #define VD_LAUNCH_COMPACT(R)                                                                                     \
     do {                                                                                                         \
@@ -1778,42 +1819,24 @@ int vd_cull_compact_views_dev(VdCtx* ctx, const VdCameraUniform* cameras, uint32
                               uint32_t* d_out_counts, int pad_tail) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!cameras || !d_meshes || n_mesh == 0 || !d_out_counts)
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null cameras/meshes/counts or n_mesh == 0");
-    if (n_views == 0 || n_views > (uint32_t)VD_MAX_VIEWS) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: n_views must be 1..VD_MAX_VIEWS");
-    if (out_stride < n_inst) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: out_stride < n_inst");
+    if (const char* no = views_refusal(cameras, d_meshes, n_mesh, d_out_counts, n_views, out_stride, n_inst)) return fail_named(ctx, "vd_cull_compact_views", no);
     if (n_inst == 0) {
         VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_counts, 0, 4 * (size_t)n_views, ctx->stream));
         return VD_OK;
     }
-    if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null instances/out");
+    if (!d_instances || !d_out) return fail_named(ctx, "vd_cull_compact_views", kNoInstOut);
     if (n_views == 1) return vd_cull_compact_dev(ctx, cameras, d_meshes, n_mesh, d_instances, n_inst, d_out, d_out_counts, pad_tail);
-    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, n_views);
-    int rc = vd_ensure(ctx, &ctx->views_scratch, &ctx->views_scratch_bytes, p.need);
-    if (rc) return rc;
-    void* d_ids = p.ids(ctx->views_scratch);
-    vd_u64* d_mask = p.mask(ctx->views_scratch);
-    unsigned* d_counts = p.counts(ctx->views_scratch);
     ViewCameras cams;
     memset(&cams, 0, sizeof(cams));
     for (uint32_t v = 0; v < n_views; ++v) cams.cam[v] = make_cam(cameras + v);
-    vd_time_begin(ctx);
-    vd_dispatch_id(p.id_bytes, [&](auto id) {
+    const VdPass1 r = run_pass1(ctx, &ctx->views_scratch, &ctx->views_scratch_bytes, kIdsFirst, n_inst, n_mesh, n_views,
+                                [&](auto id, const Pass1Plan& p, const VdPass1& o) {
         using IdT = decltype(id);
         hipLaunchKernelGGL(cull_mask_views_kernel<IdT>, dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, cams, n_views, d_meshes, n_mesh,
-                           d_instances, n_inst, d_mask, p.mask_stride, reinterpret_cast<IdT*>(d_ids), d_counts, (unsigned)p.count_stride, p.n_mt);
+                           d_instances, n_inst, o.mask, p.mask_stride, reinterpret_cast<IdT*>(o.ids), o.counts, (unsigned)p.count_stride, p.n_mt);
     });
-    vd_time_mid(ctx);
-    for (uint32_t v = 0; v < n_views; ++v) {
-        rc = launch_expand(ctx, d_mask + (size_t)v * p.mask_stride, p.n_words, p.n_words, n_inst, n_inst, 0u, d_ids, p.id_bytes, d_meshes, n_mesh,
-                           d_out + (size_t)v * out_stride, d_out_counts + v, d_counts + (size_t)v * p.count_stride);
-        if (rc) return rc;
-    }
-    vd_time_end(ctx);
-    if (pad_tail)
-        for (uint32_t v = 0; v < n_views; ++v) launch_pad_tail(ctx, d_out + (size_t)v * out_stride, d_out_counts + v, n_inst);
-    VD_HIP_CHECK(ctx, hipGetLastError());
-    return VD_OK;
+    if (r.rc) return r.rc;
+    return finish_lists(ctx, r, n_views, d_meshes, n_mesh, n_inst, 0u, d_out, out_stride, d_out_counts, pad_tail);
 }
 
 // Occlusion-culled draw lists: ONE pass over the instances (cull_mask_occ_kernel: frustum test, occlusion test against the
@@ -1830,50 +1853,36 @@ static int cull_occ_list(VdCtx* ctx, OccMode mode, const char* name, const VdCam
     const bool hiz = mode != kOccEarly, prev = mode != kOccHiz;
     char msg[256];
 #define VD_OCC_FAIL(text) do { snprintf(msg, sizeof(msg), "%s: %s", name, text); VD_FAIL(ctx, VD_ERR_INVALID_ARG, msg); } while (0)
-    if (!camera || !d_meshes || n_mesh == 0 || !d_out_count) VD_OCC_FAIL("null camera/meshes/count or n_mesh == 0");
+    if (!camera || !d_meshes || n_mesh == 0 || !d_out_count) VD_OCC_FAIL(kNoCamMeshesCount);
     VdHizLayout L = {};
     if (hiz) {
         if (!d_pyramid) VD_OCC_FAIL("null pyramid");
-        if (vd_hiz_layout(width, height, &L)) VD_OCC_FAIL("bad pyramid size");
-        if (!(camera->projection[11] == -1.0f && camera->projection[15] == 0.0f))
-            VD_OCC_FAIL("projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)");
+        if (const char* no = hiz_refusal(camera, width, height, &L)) VD_OCC_FAIL(no);
     }
     if (n_inst == 0) {
         VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_count, 0, 4, ctx->stream));
         return VD_OK;
     }
-    if (!d_instances || !d_out) VD_OCC_FAIL("null instances/out");
+    if (!d_instances || !d_out) VD_OCC_FAIL(kNoInstOut);
     if (prev && !d_prev) VD_OCC_FAIL("null visibility mask");
     if (mode == kOccLate && !d_visible_out) VD_OCC_FAIL("null visibility mask (out)");
 #undef VD_OCC_FAIL
-    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u);
-    int rc = vd_ensure(ctx, &ctx->occ_scratch, &ctx->occ_scratch_bytes, p.need);
-    if (rc) return rc;
-    void* d_ids = p.ids(ctx->occ_scratch);
-    vd_u64* d_mask = p.mask(ctx->occ_scratch);
-    unsigned* d_counts = p.counts(ctx->occ_scratch);
     OccProj proj = {};
     HizView hz = {};
     if (hiz) { proj = make_proj(camera); hz = make_hiz(d_pyramid, width, height, L); }
-    vd_time_begin(ctx);
-    vd_dispatch_id(p.id_bytes, [&](auto id) {
+    const VdPass1 r = run_pass1(ctx, &ctx->occ_scratch, &ctx->occ_scratch_bytes, kIdsFirst, n_inst, n_mesh, 1u, [&](auto id, const Pass1Plan& p, const VdPass1& o) {
         using IdT = decltype(id);
         auto launch = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, make_cam(camera), proj, hz, d_meshes, n_mesh, d_instances,
-                               n_inst, d_mask, reinterpret_cast<const vd_u64*>(d_prev), reinterpret_cast<vd_u64*>(d_visible_out),
-                               reinterpret_cast<IdT*>(d_ids), d_counts, p.n_mt);
+                               n_inst, o.mask, reinterpret_cast<const vd_u64*>(d_prev), reinterpret_cast<vd_u64*>(d_visible_out),
+                               reinterpret_cast<IdT*>(o.ids), o.counts, p.n_mt);
         };
         if (mode == kOccHiz) launch(cull_mask_occ_kernel<IdT, true, false>);
         else if (mode == kOccEarly) launch(cull_mask_occ_kernel<IdT, false, true>);
         else launch(cull_mask_occ_kernel<IdT, true, true>);
     });
-    vd_time_mid(ctx);
-    rc = launch_expand(ctx, d_mask, p.n_words, p.n_words, n_inst, n_inst, 0u, d_ids, p.id_bytes, d_meshes, n_mesh, d_out, d_out_count, d_counts);
-    if (rc) return rc;
-    vd_time_end(ctx);
-    if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
-    VD_HIP_CHECK(ctx, hipGetLastError());
-    return VD_OK;
+    if (r.rc) return r.rc;
+    return finish_lists(ctx, r, 1u, d_meshes, n_mesh, n_inst, 0u, d_out, 0, d_out_count, pad_tail);
 }
 
 int vd_cull_compact_hiz_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
@@ -1912,34 +1921,23 @@ int vd_lod_check(VdCtx* ctx, const char* name, const VdCameraUniform* camera, co
     else if (!(isfinite(params->scale) && params->scale >= 0.0f)) what = "params.scale must be finite and >= 0";
     else if (!(isfinite(params->min_distance) && params->min_distance > 0.0f)) what = "params.min_distance must be finite and > 0";
     else if (!(isfinite(params->min_size) && params->min_size >= 0.0f)) what = "params.min_size must be finite and >= 0";
-    if (!what) return VD_OK;
-    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
-    return VD_ERR_INVALID_ARG;
+    return what ? fail_named(ctx, name, what) : VD_OK;
 }
 
 // Pass 1 of the LOD forms into ctx->scratch, laid out as launch_mask_pass lays it out (the two share the arena: whatever
 // the other left in the id table - another width included - every row that differs from this call's is rewritten).  The
-// id width follows the number of ROWS, n_mesh.  Starts the call's timer and records its stage boundary.
-int launch_lod_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdLodParams* params, const VdLodGroup* d_groups, uint32_t n_group,
-                    uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst, vd_u64** out_mask, void** out_ids,
-                    unsigned* out_id_bytes, unsigned** out_tile_count) {
-    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u, /*mask_first=*/true);
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, p.need);
-    if (rc) return rc;
-    vd_u64* d_mask = p.mask(ctx->scratch);
-    void* d_ids = p.ids(ctx->scratch);
-    unsigned* d_counts = p.counts(ctx->scratch);
-    vd_time_begin(ctx);
-    vd_dispatch_id(p.id_bytes, [&](auto id) {
+// id width follows the number of ROWS, n_mesh.
+VdPass1 launch_lod_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdLodParams* params, const VdLodGroup* d_groups, uint32_t n_group,
+                        uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst) {
+    return run_pass1(ctx, &ctx->scratch, &ctx->scratch_bytes, kMaskFirst, n_inst, n_mesh, 1u, [&](auto id, const Pass1Plan& p, const VdPass1& o) {
         using IdT = decltype(id);
         hipLaunchKernelGGL((cull_mask_lod_kernel<IdT, true>), dim3(p.mb), dim3(kBlock), p.lds_bytes, ctx->stream, make_cam(camera), make_lod(params),
-                           d_groups, n_group, n_mesh, d_instances, n_inst, d_mask, reinterpret_cast<IdT*>(d_ids), d_counts, p.n_mt);
+                           d_groups, n_group, n_mesh, d_instances, n_inst, o.mask, reinterpret_cast<IdT*>(o.ids), o.counts, p.n_mt);
     });
-    vd_time_mid(ctx);
-    *out_mask = d_mask; *out_ids = d_ids; *out_id_bytes = p.id_bytes; *out_tile_count = d_counts;
-    return VD_OK;
 }
 
+// The ids alone, of the caller's width, into the caller's table: the same kernel without a mask and without counts, on
+// pass 1's launch geometry for that width.  No arena, one launch.
 int vd_lod_ids_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params, const VdLodGroup* d_groups, uint32_t n_group,
                    uint32_t n_mesh, const VdInstance* d_instances, uint32_t n_inst, void* d_out_ids, uint32_t id_bytes) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
@@ -1947,19 +1945,17 @@ int vd_lod_ids_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params
     int rc = vd_lod_check(ctx, "vd_lod_ids", camera, &params, d_groups, n_group, n_mesh);
     if (rc) return rc;
     if (id_bytes != 1u && id_bytes != 2u && id_bytes != 4u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: id_bytes must be 1, 2 or 4");
-    if ((id_bytes == 1u && n_mesh > 256u) || (id_bytes == 2u && n_mesh > 65536u))
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: ids of id_bytes bytes cannot hold n_mesh - 1");
+    if (id_bytes < vd_id_bytes(n_mesh)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: ids of id_bytes bytes cannot hold n_mesh - 1");
     if (n_inst == 0) return VD_OK;
     if (!d_instances || !d_out_ids) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: null instances/ids");
     if (reinterpret_cast<uintptr_t>(d_out_ids) & 15u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_lod_ids: the id table must be 16-byte aligned");
-    const Pass1Plan p = pass1_plan(ctx, n_inst, n_mesh, 1u);                 // the launch geometry; the id width is the caller's
-    const unsigned lds_bytes = kWavesPerBlock * (kSlabBytes + kMaskRounds * kWave * id_bytes);
+    const Pass1Grid g = pass1_grid(ctx, n_inst, id_bytes);
     vd_time_begin(ctx);
     vd_dispatch_id(id_bytes, [&](auto id) {
         using IdT = decltype(id);
-        hipLaunchKernelGGL((cull_mask_lod_kernel<IdT, false>), dim3(p.mb), dim3(kBlock), lds_bytes, ctx->stream, make_cam(camera), make_lod(&params),
+        hipLaunchKernelGGL((cull_mask_lod_kernel<IdT, false>), dim3(g.mb), dim3(kBlock), g.lds_bytes, ctx->stream, make_cam(camera), make_lod(&params),
                            d_groups, n_group, n_mesh, d_instances, n_inst, (vd_u64*)nullptr, reinterpret_cast<IdT*>(d_out_ids), (unsigned*)nullptr,
-                           p.n_mt);
+                           g.n_mt);
     });
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
@@ -1975,22 +1971,15 @@ int vd_cull_compact_lod_dev(VdCtx* ctx, const VdCameraUniform* camera, VdLodPara
     if (!ctx) return VD_ERR_INVALID_ARG;
     int rc = vd_lod_check(ctx, "vd_cull_compact_lod", camera, &params, d_groups, n_group, n_mesh);
     if (rc) return rc;
-    if (!d_meshes || !d_out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null meshes/count");
+    if (!d_meshes || !d_out_count) return fail_named(ctx, "vd_cull_compact_lod", kNoLodMeshesCount);
     if (n_inst == 0) {
         VD_HIP_CHECK(ctx, hipMemsetAsync(d_out_count, 0, 4, ctx->stream));
         return VD_OK;
     }
-    if (!d_instances || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null instances/out");
-    vd_u64* d_mask; void* d_ids; unsigned id_bytes; unsigned* d_tile_count;
-    rc = launch_lod_pass(ctx, camera, &params, d_groups, n_group, n_mesh, d_instances, n_inst, &d_mask, &d_ids, &id_bytes, &d_tile_count);
-    if (rc) return rc;
-    const unsigned n_words = (n_inst + 63u) / 64u;
-    rc = launch_expand(ctx, d_mask, n_words, n_words, n_inst, n_inst, 0u, d_ids, id_bytes, d_meshes, n_mesh, d_out, d_out_count, d_tile_count);
-    if (rc) return rc;
-    vd_time_end(ctx);
-    if (pad_tail) launch_pad_tail(ctx, d_out, d_out_count, n_inst);
-    VD_HIP_CHECK(ctx, hipGetLastError());
-    return VD_OK;
+    if (!d_instances || !d_out) return fail_named(ctx, "vd_cull_compact_lod", kNoInstOut);
+    const VdPass1 r = launch_lod_pass(ctx, camera, &params, d_groups, n_group, n_mesh, d_instances, n_inst);
+    if (r.rc) return r.rc;
+    return finish_lists(ctx, r, 1u, d_meshes, n_mesh, n_inst, 0u, d_out, 0, d_out_count, pad_tail);
 }
 
 int vd_cull_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
@@ -2001,9 +1990,7 @@ int vd_cull_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo
     if (n_inst == 0) return VD_OK;
     if (!d_instances || !d_mask) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_mask: null instances/mask");
     const unsigned n_wave_tiles = (n_inst + kWave - 1) / kWave;
-    unsigned blocks = (n_wave_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned cap = (unsigned)ctx->num_cus * 4u;
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = vd_blocks(ctx, n_wave_tiles, kWavesPerBlock, 4u);
     vd_time_begin(ctx);
     hipLaunchKernelGGL(cull_mask_kernel, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream, make_cam(camera),
                        d_meshes, n_mesh, d_instances, n_inst, reinterpret_cast<vd_u64*>(d_mask), n_wave_tiles);
@@ -2019,15 +2006,11 @@ int vd_occlusion_mask_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdMes
     if (!ctx) return VD_ERR_INVALID_ARG;
     if (!camera || !d_meshes || n_mesh == 0 || !d_pyramid) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_occlusion_mask: null camera/meshes/pyramid or n_mesh == 0");
     VdHizLayout L;
-    if (vd_hiz_layout(width, height, &L)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_occlusion_mask: bad pyramid size");
-    if (!(camera->projection[11] == -1.0f && camera->projection[15] == 0.0f))
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_occlusion_mask: projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)");
+    if (const char* no = hiz_refusal(camera, width, height, &L)) return fail_named(ctx, "vd_occlusion_mask", no);
     if (n_inst == 0) return VD_OK;
     if (!d_instances || !d_mask_in || !d_mask_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_occlusion_mask: null instances/masks");
     const unsigned n_wave_tiles = (n_inst + kWave - 1) / kWave;
-    unsigned blocks = (n_wave_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned cap = (unsigned)ctx->num_cus * 8u;
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = vd_blocks(ctx, n_wave_tiles, kWavesPerBlock, 8u);
     vd_time_begin(ctx);
     hipLaunchKernelGGL(occlusion_mask_kernel, dim3(blocks), dim3(kBlock), kWavesPerBlock * kSlabBytes, ctx->stream, make_cam(camera),
                        make_proj(camera), make_hiz(d_pyramid, width, height, L), d_meshes, n_mesh,
@@ -2091,8 +2074,7 @@ int vd_indices_to_draws_dev(VdCtx* ctx, const uint32_t* d_indices, uint32_t n_in
     if (n_indices == 0) return VD_OK;
     if (!d_indices || !d_mesh_ids || !d_out || n_total == 0) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_indices_to_draws: null indices/ids/out or n_total == 0");
     if (id_bytes != 1u && id_bytes != 2u && id_bytes != 4u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_indices_to_draws: id_bytes must be 1, 2 or 4");
-    unsigned blocks = (n_indices + kBlock - 1) / kBlock;
-    if (blocks > (unsigned)ctx->num_cus * 16u) blocks = (unsigned)ctx->num_cus * 16u;
+    const unsigned blocks = vd_blocks(ctx, n_indices, kBlock, 16u);
     vd_time_begin(ctx);
     vd_dispatch_id(id_bytes, [&](auto id) {
         using IdT = decltype(id);
@@ -2144,22 +2126,65 @@ int vd_compute_update_dev(VdCtx* ctx, const uint32_t* d_indices, uint32_t n_indi
     return VD_OK;
 }
 
-// ---- host-pointer variants: stage through ctx-owned device buffers ----------------------
-static int stage_cull_inputs(VdCtx* ctx, const VdMeshInfo* meshes, uint32_t n_mesh, const VdInstance* instances,
-                             uint32_t n_inst, VdMeshInfo** d_meshes, VdInstance** d_inst, VdDrawIndexedIndirect** d_out) {
+// ---- host-pointer variants: one staged round trip through ctx-owned device buffers (declared in vd_common.hpp, hidden
+// visibility: batch.hip stages the same way) --------------------------------------------------------------------------
+int vd_stage(VdCtx* ctx, const VdInstance* instances, uint32_t n_inst, size_t header, VdBlob* blobs, unsigned n_blobs, size_t out_bytes,
+             VdStaged* s) {
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    size_t aux_bytes = header;
+    for (unsigned b = 0; b < n_blobs; ++b) {           // (dev holds the blob's offset until the arena exists)
+        aux_bytes = (aux_bytes + blobs[b].align - 1) & ~(blobs[b].align - 1);
+        blobs[b].dev = reinterpret_cast<void*>(aux_bytes);
+        aux_bytes += blobs[b].bytes;
+    }
     int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, (size_t)n_mesh * sizeof(VdMeshInfo) + 16);
+    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, aux_bytes);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16);
+    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, out_bytes);
     if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->stage_in, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(reinterpret_cast<char*>(ctx->stage_aux) + 16, meshes, (size_t)n_mesh * sizeof(VdMeshInfo),
-                                     hipMemcpyHostToDevice, ctx->stream));
-    *d_inst = reinterpret_cast<VdInstance*>(ctx->stage_in);
-    *d_meshes = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + 16);
-    *d_out = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
+    s->inst = reinterpret_cast<VdInstance*>(ctx->stage_in);
+    s->counts = reinterpret_cast<uint32_t*>(ctx->stage_aux);
+    s->out = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
+    if (n_inst) VD_HIP_CHECK(ctx, hipMemcpyAsync(s->inst, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
+    for (unsigned b = 0; b < n_blobs; ++b) {
+        blobs[b].dev = reinterpret_cast<char*>(ctx->stage_aux) + reinterpret_cast<size_t>(blobs[b].dev);
+        VD_HIP_CHECK(ctx, hipMemcpyAsync(blobs[b].dev, blobs[b].host, blobs[b].bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return VD_OK;
+}
+
+int vd_fetch_lists(VdCtx* ctx, const char* name, bool scan, const VdStaged* s, uint32_t n_views, uint32_t n_inst, int pad_tail,
+                   VdDrawIndexedIndirect* out, uint64_t out_stride, uint32_t* out_counts) {
+    if (out_counts) {
+        VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, s->counts, 4 * (size_t)n_views, hipMemcpyDeviceToHost, ctx->stream));
+        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (uint32_t v = 0; v < n_views; ++v) {
+        uint32_t c = n_inst;
+        if (out_counts) {
+            c = ctx->host_pinned[v];
+            // scan: a cross-workgroup wait of the fused form's scan timed out (vd_common.hpp) - the fault word is up and the count
+            // is 0, or the launch lost its LAST workgroup and the count still holds the value the first one pre-stored,
+            // VD_SCAN_STUCK.  No list was written either way; whatever state the launch left, start over.
+            if (scan && (c > n_inst || ctx->host_pinned[kScanFaultWord] != 0u)) {
+                ctx->host_pinned[kScanFaultWord] = 0u;
+                if (ctx->scan_state) (void)hipMemsetAsync(ctx->scan_state, 0, ctx->scan_state_bytes, ctx->stream);
+                snprintf(ctx->err, sizeof(ctx->err), "%s: the compaction scan gave up waiting for a workgroup", name);
+                return VD_ERR_HIP;
+            }
+            if (c > n_inst) {
+                snprintf(ctx->err, sizeof(ctx->err), "%s: the expansion wrote no count", name);
+                return VD_ERR_HIP;
+            }
+            out_counts[v] = c;
+        }
+        const size_t n_copy = pad_tail ? n_inst : c;
+        if (n_copy)
+            VD_HIP_CHECK(ctx, hipMemcpyAsync(out + (size_t)v * out_stride, s->out + (size_t)v * n_inst, n_copy * sizeof(VdDrawIndexedIndirect),
+                                             hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return VD_OK;
 }
 
@@ -2167,17 +2192,16 @@ int vd_cull_emit(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* me
                  const VdInstance* instances, uint32_t n_inst, VdDrawIndexedIndirect* out) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!camera || !meshes || n_mesh == 0) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null camera/meshes or n_mesh == 0");
+    if (!camera || !meshes || n_mesh == 0) return fail_named(ctx, "vd_cull_emit", kNoCamMeshes);
     if (n_inst == 0) return VD_OK;
-    if (!instances || !out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_emit: null instances/out");
-    VdMeshInfo* dm; VdInstance* di; VdDrawIndexedIndirect* dout;
-    int rc = stage_cull_inputs(ctx, meshes, n_mesh, instances, n_inst, &dm, &di, &dout);
+    if (!instances || !out) return fail_named(ctx, "vd_cull_emit", kNoInstOut);
+    VdBlob m = {meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 16, nullptr};
+    VdStaged s;
+    int rc = vd_stage(ctx, instances, n_inst, 16, &m, 1, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16, &s);
     if (rc) return rc;
-    rc = vd_cull_emit_dev(ctx, camera, dm, n_mesh, di, n_inst, dout);
+    rc = vd_cull_emit_dev(ctx, camera, reinterpret_cast<VdMeshInfo*>(m.dev), n_mesh, s.inst, n_inst, s.out);
     if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, (size_t)n_inst * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    return vd_fetch_lists(ctx, "vd_cull_emit", false, &s, 1u, n_inst, 0, out, 0, nullptr);   // no count: all n_inst commands
 }
 
 int vd_cull_compact(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* meshes, uint32_t n_mesh,
@@ -2185,83 +2209,40 @@ int vd_cull_compact(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo*
                     int pad_tail) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!camera || !meshes || n_mesh == 0 || !out_count)
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact: null camera/meshes/count or n_mesh == 0");
+    if (!camera || !meshes || n_mesh == 0 || !out_count) return fail_named(ctx, "vd_cull_compact", kNoCamMeshesCount);
     *out_count = 0;
     if (n_inst == 0) return VD_OK;
-    if (!instances || !out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact: null instances/out");
-    VdMeshInfo* dm; VdInstance* di; VdDrawIndexedIndirect* dout;
-    int rc = stage_cull_inputs(ctx, meshes, n_mesh, instances, n_inst, &dm, &di, &dout);
+    if (!instances || !out) return fail_named(ctx, "vd_cull_compact", kNoInstOut);
+    VdBlob m = {meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 16, nullptr};
+    VdStaged s;
+    int rc = vd_stage(ctx, instances, n_inst, 16, &m, 1, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16, &s);
     if (rc) return rc;
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(ctx->stage_aux);
-    rc = vd_cull_compact_dev(ctx, camera, dm, n_mesh, di, n_inst, dout, d_count, pad_tail);
+    rc = vd_cull_compact_dev(ctx, camera, reinterpret_cast<VdMeshInfo*>(m.dev), n_mesh, s.inst, n_inst, s.out, s.counts, pad_tail);
     if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *out_count = ctx->host_pinned[0];
-    // a cross-workgroup wait of the scan timed out (vd_common.hpp): the fault word is up and the count is 0 - or the launch lost its
-    // LAST workgroup and the count still holds the value the first one pre-stored, VD_SCAN_STUCK.  No list was written either way.
-    if (*out_count > n_inst || ctx->host_pinned[kScanFaultWord] != 0u) {
-        *out_count = 0;
-        ctx->host_pinned[kScanFaultWord] = 0u;
-        if (ctx->scan_state) (void)hipMemsetAsync(ctx->scan_state, 0, ctx->scan_state_bytes, ctx->stream);   // whatever state the launch left: start over
-        VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact: the compaction scan gave up waiting for a workgroup");
-    }
-    const size_t n_copy = pad_tail ? n_inst : *out_count;
-    if (n_copy) {
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n_copy * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
-        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return VD_OK;
+    return vd_fetch_lists(ctx, "vd_cull_compact", true, &s, 1u, n_inst, pad_tail, out, 0, out_count);
 }
 
+// n_views lists of n_inst commands; a 64-byte header takes the counts.  n_views == 1 below the split size runs the fused
+// form, whose scan can give up (vd_cull_compact).
 int vd_cull_compact_views(VdCtx* ctx, const VdCameraUniform* cameras, uint32_t n_views, const VdMeshInfo* meshes, uint32_t n_mesh,
                           const VdInstance* instances, uint32_t n_inst, VdDrawIndexedIndirect* out, uint64_t out_stride,
                           uint32_t* out_counts, int pad_tail) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!cameras || !meshes || n_mesh == 0 || !out_counts)
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null cameras/meshes/counts or n_mesh == 0");
-    if (n_views == 0 || n_views > (uint32_t)VD_MAX_VIEWS) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: n_views must be 1..VD_MAX_VIEWS");
-    if (out_stride < n_inst) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: out_stride < n_inst");
-    if (n_inst > 0 && (!instances || !out)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_views: null instances/out");
+    if (const char* no = views_refusal(cameras, meshes, n_mesh, out_counts, n_views, out_stride, n_inst)) return fail_named(ctx, "vd_cull_compact_views", no);
+    if (n_inst > 0 && (!instances || !out)) return fail_named(ctx, "vd_cull_compact_views", kNoInstOut);
     for (uint32_t v = 0; v < n_views; ++v) out_counts[v] = 0;      // (a refused call writes nothing)
     if (n_inst == 0) return VD_OK;
-    // staged like vd_cull_compact: instances, meshes behind a 64-byte header that takes the counts, n_views lists of n_inst commands
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
+    VdBlob m = {meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 16, nullptr};
+    VdStaged s;
+    int rc = vd_stage(ctx, instances, n_inst, 64, &m, 1, (size_t)n_views * n_inst * sizeof(VdDrawIndexedIndirect) + 16, &s);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, (size_t)n_mesh * sizeof(VdMeshInfo) + 64);
+    rc = vd_cull_compact_views_dev(ctx, cameras, n_views, reinterpret_cast<VdMeshInfo*>(m.dev), n_mesh, s.inst, n_inst, s.out, n_inst, s.counts, pad_tail);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_views * n_inst * sizeof(VdDrawIndexedIndirect) + 16);
-    if (rc) return rc;
-    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
-    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + 64);
-    VdDrawIndexedIndirect* dout = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(ctx->stage_aux);
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
-    rc = vd_cull_compact_views_dev(ctx, cameras, n_views, dm, n_mesh, di, n_inst, dout, n_inst, d_counts, pad_tail);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_counts, 4 * (size_t)n_views, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t v = 0; v < n_views; ++v) {
-        const uint32_t c = ctx->host_pinned[v];
-        if (c > n_inst || ctx->host_pinned[kScanFaultWord] != 0u) {   // n_views == 1 below the split size runs the fused form, whose scan can give up (vd_cull_compact)
-            ctx->host_pinned[kScanFaultWord] = 0u;
-            if (ctx->scan_state) (void)hipMemsetAsync(ctx->scan_state, 0, ctx->scan_state_bytes, ctx->stream);
-            VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_views: the compaction scan gave up waiting for a workgroup");
-        }
-        out_counts[v] = c;
-        const size_t n_copy = pad_tail ? n_inst : c;
-        if (n_copy)
-            VD_HIP_CHECK(ctx, hipMemcpyAsync(out + (size_t)v * out_stride, dout + (size_t)v * n_inst, n_copy * sizeof(VdDrawIndexedIndirect),
-                                             hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    return vd_fetch_lists(ctx, "vd_cull_compact_views", true, &s, n_views, n_inst, pad_tail, out, out_stride, out_counts);
 }
 
+// behind the 16-byte header: the meshes, then the pyramid on a 256-byte boundary
 int vd_cull_compact_hiz(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* meshes, uint32_t n_mesh,
                         const VdInstance* instances, uint32_t n_inst, const float* pyramid, uint32_t width, uint32_t height,
                         VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail) {
@@ -2270,46 +2251,22 @@ int vd_cull_compact_hiz(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshI
     if (!camera || !meshes || n_mesh == 0 || !out_count || !pyramid)
         VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: null camera/meshes/count/pyramid or n_mesh == 0");
     VdHizLayout L;
-    if (vd_hiz_layout(width, height, &L)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: bad pyramid size");
-    if (!(camera->projection[11] == -1.0f && camera->projection[15] == 0.0f))
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: projection is not a right-handed perspective matrix (projection[11] == -1, [15] == 0)");
-    if (n_inst > 0 && (!instances || !out)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_hiz: null instances/out");
+    if (const char* no = hiz_refusal(camera, width, height, &L)) return fail_named(ctx, "vd_cull_compact_hiz", no);
+    if (n_inst > 0 && (!instances || !out)) return fail_named(ctx, "vd_cull_compact_hiz", kNoInstOut);
     *out_count = 0;                                                  // (a refused call writes nothing)
     if (n_inst == 0) return VD_OK;
-    // staged like vd_cull_compact: instances; a 16-byte header that takes the count, the meshes and the pyramid; n_inst commands
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t pyr_off = (16 + (size_t)n_mesh * sizeof(VdMeshInfo) + 255) & ~(size_t)255;
-    const size_t pyr_bytes = (size_t)L.total_texels * sizeof(float);
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
+    VdBlob b[2] = {{meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 16, nullptr}, {pyramid, (size_t)L.total_texels * sizeof(float), 256, nullptr}};
+    VdStaged s;
+    int rc = vd_stage(ctx, instances, n_inst, 16, b, 2, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16, &s);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, pyr_off + pyr_bytes);
+    rc = vd_cull_compact_hiz_dev(ctx, camera, reinterpret_cast<VdMeshInfo*>(b[0].dev), n_mesh, s.inst, n_inst, reinterpret_cast<float*>(b[1].dev), width,
+                                 height, s.out, s.counts, pad_tail);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16);
-    if (rc) return rc;
-    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
-    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + 16);
-    float* dp = reinterpret_cast<float*>(reinterpret_cast<char*>(ctx->stage_aux) + pyr_off);
-    VdDrawIndexedIndirect* dout = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(ctx->stage_aux);
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(dp, pyramid, pyr_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = vd_cull_compact_hiz_dev(ctx, camera, dm, n_mesh, di, n_inst, dp, width, height, dout, d_count, pad_tail);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->host_pinned[0] > n_inst) VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_hiz: the expansion wrote no count");
-    *out_count = ctx->host_pinned[0];
-    const size_t n_copy = pad_tail ? n_inst : *out_count;
-    if (n_copy) {
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n_copy * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
-        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return VD_OK;
+    return vd_fetch_lists(ctx, "vd_cull_compact_hiz", false, &s, 1u, n_inst, pad_tail, out, 0, out_count);
 }
 
-// host pointers, staged like vd_cull_compact: instances; a 64-byte header that takes the count, the groups and the meshes;
-// n_inst commands.  The group table is on the host here, so it is validated (the _dev forms clamp instead).
+// behind the 64-byte header: the groups, then the meshes.  The group table is on the host here, so it is validated (the
+// _dev forms clamp instead).
 int vd_cull_compact_lod(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams params, const VdLodGroup* groups, uint32_t n_group,
                         const VdMeshInfo* meshes, uint32_t n_mesh, const VdInstance* instances, uint32_t n_inst,
                         VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail) {
@@ -2317,7 +2274,7 @@ int vd_cull_compact_lod(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams p
     if (!ctx) return VD_ERR_INVALID_ARG;
     int rc = vd_lod_check(ctx, "vd_cull_compact_lod", camera, &params, groups, n_group, n_mesh);
     if (rc) return rc;
-    if (!meshes || !out_count) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null meshes/count");
+    if (!meshes || !out_count) return fail_named(ctx, "vd_cull_compact_lod", kNoLodMeshesCount);
     for (uint32_t g = 0; g < n_group; ++g) {
         const uint32_t nl = groups[g].n_lods;
         if (nl < 1u || nl > VD_LOD_MAX || (uint64_t)groups[g].first_row + nl > (uint64_t)n_mesh) {
@@ -2325,37 +2282,17 @@ int vd_cull_compact_lod(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams p
             return VD_ERR_INVALID_ARG;
         }
     }
-    if (n_inst > 0 && (!instances || !out)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_cull_compact_lod: null instances/out");
+    if (n_inst > 0 && (!instances || !out)) return fail_named(ctx, "vd_cull_compact_lod", kNoInstOut);
     *out_count = 0;                                                  // (a refused call writes nothing)
     if (n_inst == 0) return VD_OK;
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t mesh_off = 64 + (size_t)n_group * sizeof(VdLodGroup);
-    rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n_inst * sizeof(VdInstance));
+    VdBlob b[2] = {{groups, (size_t)n_group * sizeof(VdLodGroup), 16, nullptr}, {meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 16, nullptr}};
+    VdStaged s;
+    rc = vd_stage(ctx, instances, n_inst, 64, b, 2, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16, &s);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, mesh_off + (size_t)n_mesh * sizeof(VdMeshInfo));
+    rc = vd_cull_compact_lod_dev(ctx, camera, params, reinterpret_cast<VdLodGroup*>(b[0].dev), n_group, reinterpret_cast<VdMeshInfo*>(b[1].dev), n_mesh,
+                                 s.inst, n_inst, s.out, s.counts, pad_tail);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n_inst * sizeof(VdDrawIndexedIndirect) + 16);
-    if (rc) return rc;
-    VdInstance* di = reinterpret_cast<VdInstance*>(ctx->stage_in);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(ctx->stage_aux);
-    VdLodGroup* dg = reinterpret_cast<VdLodGroup*>(reinterpret_cast<char*>(ctx->stage_aux) + 64);
-    VdMeshInfo* dm = reinterpret_cast<VdMeshInfo*>(reinterpret_cast<char*>(ctx->stage_aux) + mesh_off);
-    VdDrawIndexedIndirect* dout = reinterpret_cast<VdDrawIndexedIndirect*>(ctx->stage_out);
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(di, instances, (size_t)n_inst * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(dg, groups, (size_t)n_group * sizeof(VdLodGroup), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(dm, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
-    rc = vd_cull_compact_lod_dev(ctx, camera, params, dg, n_group, dm, n_mesh, di, n_inst, dout, d_count, pad_tail);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->host_pinned[0] > n_inst) VD_FAIL(ctx, VD_ERR_HIP, "vd_cull_compact_lod: the expansion wrote no count");
-    *out_count = ctx->host_pinned[0];
-    const size_t n_copy = pad_tail ? n_inst : *out_count;
-    if (n_copy) {
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n_copy * sizeof(VdDrawIndexedIndirect), hipMemcpyDeviceToHost, ctx->stream));
-        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return VD_OK;
+    return vd_fetch_lists(ctx, "vd_cull_compact_lod", false, &s, 1u, n_inst, pad_tail, out, 0, out_count);
 }
 
 #ifdef VD_TUNING

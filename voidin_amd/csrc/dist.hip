@@ -210,7 +210,7 @@ int vd_dist_set_scene_dev(VdDist* d, const VdInstance* d_shard_instances, uint32
     dist_free_scene(d);
     d->n_total = n_total; d->shard = S; d->first = lo; d->n_local = n_local; d->n_mesh = n_mesh;
     d->wps = (S + 63u) / 64u;
-    d->id_bytes = n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u);     // the width rule of launch_mask_pass (cull.hip)
+    d->id_bytes = vd_id_bytes(n_mesh);
     const size_t rows = (size_t)S * (size_t)d->world;
     if (hipMalloc(reinterpret_cast<void**>(&d->d_mask), 8 * (size_t)d->wps) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&d->d_mask_all), 8 * (size_t)d->wps * (size_t)d->world) != hipSuccess ||
@@ -225,9 +225,9 @@ int vd_dist_set_scene_dev(VdDist* d, const VdInstance* d_shard_instances, uint32
     // mesh assignment is static, only transforms animate - shaders/compute_update.wgsl:10-28)
     char* own = reinterpret_cast<char*>(d->d_mesh_ids) + (size_t)d->rank * S * d->id_bytes;
     const dim3 grid((S + 255u) / 256u), block(256);
-    if (d->id_bytes == 1u) hipLaunchKernelGGL(mesh_ids_kernel<unsigned char>, grid, block, 0, ctx->stream, d_shard_instances, n_local, S, n_mesh, reinterpret_cast<unsigned char*>(own));
-    else if (d->id_bytes == 2u) hipLaunchKernelGGL(mesh_ids_kernel<unsigned short>, grid, block, 0, ctx->stream, d_shard_instances, n_local, S, n_mesh, reinterpret_cast<unsigned short*>(own));
-    else hipLaunchKernelGGL(mesh_ids_kernel<unsigned>, grid, block, 0, ctx->stream, d_shard_instances, n_local, S, n_mesh, reinterpret_cast<unsigned*>(own));
+    vd_dispatch_id(d->id_bytes, [&](auto id) {
+        hipLaunchKernelGGL(mesh_ids_kernel<decltype(id)>, grid, block, 0, ctx->stream, d_shard_instances, n_local, S, n_mesh, reinterpret_cast<decltype(id)*>(own));
+    });
     VD_HIP_CHECK(ctx, hipGetLastError());
     VD_RCCL_CHECK(d, g_rccl.AllGather(own, d->d_mesh_ids, (size_t)S * d->id_bytes, ncclUint8, d->comm, ctx->stream));
     return VD_OK;

@@ -105,21 +105,48 @@ int vd_scan_scratch(VdCtx* ctx, unsigned n_tiles, unsigned long long** ticket, u
 // that launches a look-back scan, so a renderer that only uses the *_dev forms hears about it on its next frame.
 int vd_scan_check_fault(VdCtx* ctx);
 static inline unsigned* vd_scan_fault_word(VdCtx* ctx) { return ctx->fault_dev; }
-// cull.hip: pass 1 of the split forms (cull_mask_tiled_kernel) into ctx->scratch - the visibility bitmask, the clamped
-// mesh-id table (*out_id_bytes = 1, 2 or 4 by n_mesh) and the survivors per 1024-instance tile.  Starts the call's timer
-// and records its stage boundary.  batch.hip groups by mesh from the same pass.  Not part of the C ABI.
-extern "C" __attribute__((visibility("hidden"))) int launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                                                                      const VdInstance* d_instances, uint32_t n_inst, unsigned long long** out_mask, void** out_ids,
-                                                                      unsigned* out_id_bytes, unsigned** out_tile_count);
+// The width of a mesh id by the size of the mesh table - 1, 2 or 4 bytes: the one statement of the rule (pass 1, the sharded
+// scene's replicated table, the width check of vd_lod_ids_dev).
+static inline unsigned vd_id_bytes(unsigned n_mesh) { return n_mesh <= 256u ? 1u : (n_mesh <= 65536u ? 2u : 4u); }
+// Workgroups of a grid-stride launch: ceil(items / per_block), at most per_cu on every CU.
+static inline unsigned vd_blocks(const VdCtx* ctx, unsigned items, unsigned per_block, unsigned per_cu) {
+    const unsigned blocks = (items + per_block - 1u) / per_block, cap = (unsigned)ctx->num_cus * per_cu;
+    return blocks < cap ? blocks : cap;
+}
 
-// cull.hip: the same for the LOD forms (cull_mask_lod_kernel; the ids are rows of the mesh table, their width by n_mesh),
-// and the argument check every LOD entry point shares (`name` prefixes the message).  batch.hip groups by row from this pass.
-extern "C" __attribute__((visibility("hidden"))) int launch_lod_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdLodParams* params,
-                                                                     const VdLodGroup* d_groups, uint32_t n_group, uint32_t n_mesh,
-                                                                     const VdInstance* d_instances, uint32_t n_inst, unsigned long long** out_mask,
-                                                                     void** out_ids, unsigned* out_id_bytes, unsigned** out_tile_count);
+// What pass 1 of a split form leaves behind in its arena (where in the arena: cull.hip, pass1_plan - callers use these
+// pointers, never offsets): view v's mask at mask + v * mask_stride, its survivors per 1024-instance tile at
+// counts + v * count_stride.  rc != VD_OK: the arena could not be made, nothing was launched.
+struct VdPass1 {
+    int rc;
+    unsigned long long* mask; void* ids; unsigned* counts;
+    unsigned id_bytes, n_words, n_mt;          // id width by n_mesh; mask words; 1024-instance tiles
+    size_t mask_stride, count_stride;          // words / entries between two views
+};
+// cull.hip: pass 1 of the single-view forms into ctx->scratch - cull_mask_tiled_kernel, and cull_mask_lod_kernel (the ids are
+// rows of the mesh table, their width by n_mesh).  Both start the call's timer and record its stage boundary.  batch.hip
+// groups by mesh / by row from the same passes.  Not part of the C ABI.
+extern "C" __attribute__((visibility("hidden"))) VdPass1 launch_mask_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                                                                          const VdInstance* d_instances, uint32_t n_inst);
+extern "C" __attribute__((visibility("hidden"))) VdPass1 launch_lod_pass(VdCtx* ctx, const VdCameraUniform* camera, const VdLodParams* params,
+                                                                         const VdLodGroup* d_groups, uint32_t n_group, uint32_t n_mesh,
+                                                                         const VdInstance* d_instances, uint32_t n_inst);
+// ... and the argument check every LOD entry point shares (`name` prefixes the message).
 extern "C" __attribute__((visibility("hidden"))) int vd_lod_check(VdCtx* ctx, const char* name, const VdCameraUniform* camera, const VdLodParams* params,
                                                                   const VdLodGroup* groups, uint32_t n_group, uint32_t n_mesh);
+
+// cull.hip: the staged round trip of the host-pointer forms.  vd_stage drains the stream, sizes ctx->stage_in / stage_aux /
+// stage_out and uploads the instances and, behind a header of `header` bytes at the front of stage_aux that takes the
+// counts, the blobs in order, each at its alignment (*dev = where it went).  vd_fetch_lists reads n_views counts through
+// host_pinned, refuses an implausible one (`scan`: the fused form's scan may have given up - fault word, state reset;
+// otherwise "the expansion wrote no count"), and copies pad_tail ? n_inst : count commands per view from s.out + v * n_inst
+// to out + v * out_stride.  out_counts == null: a list without a count, n_inst commands (vd_cull_emit).
+struct VdBlob { const void* host; size_t bytes, align; void* dev; };
+struct VdStaged { VdInstance* inst; uint32_t* counts; VdDrawIndexedIndirect* out; };
+extern "C" __attribute__((visibility("hidden"))) int vd_stage(VdCtx* ctx, const VdInstance* instances, uint32_t n_inst, size_t header, VdBlob* blobs,
+                                                              unsigned n_blobs, size_t out_bytes, VdStaged* s);
+extern "C" __attribute__((visibility("hidden"))) int vd_fetch_lists(VdCtx* ctx, const char* name, bool scan, const VdStaged* s, uint32_t n_views, uint32_t n_inst,
+                                                                    int pad_tail, VdDrawIndexedIndirect* out, uint64_t out_stride, uint32_t* out_counts);
 
 // Calls f with a value of the mesh-id type of that width - unsigned char, unsigned short or unsigned: the one place
 // where an id width (1, 2 or 4 bytes; checked by the caller) picks a kernel instantiation.
