@@ -206,6 +206,28 @@ class Tlas {
         if (nodes.size() != 2 * n + 1) throw Error(VD_ERR_INVALID_ARG, "Tlas::refit: node count does not match instance count");
         gpu.check(vd_tlas_refit(gpu.ctx(), instances, (uint32_t)n, meshes, (uint32_t)n_mesh, nodes.data()));
     }
+    // NEW (voidin_abi.h "LBVH top level"): a top level over the same leaf boxes built on the whole GPU in a fraction of a
+    // millisecond - not the reference's tree - in the reference's node layout: refit() and the unchanged WGSL traverse_tlas take it.
+    void build_fast(const Gpu& gpu, const Instance* instances, size_t n, const MeshInfo* meshes, size_t n_mesh) {
+        nodes.assign(2 * n + 1, TlasNode{});
+        gpu.check(vd_tlas_build_lbvh(gpu.ctx(), instances, (uint32_t)n, meshes, (uint32_t)n_mesh, nodes.data()));
+    }
+};
+
+// More than 32 768 instances (no reference counterpart: tlas.rs:71 packs two 16-bit child ids): 32-bit child ids, walked by
+// traverse_tlas(gpu, VdTraceSceneWide, rays) below.
+class TlasWide {
+   public:
+    std::vector<VdTlasNodeWide> nodes;
+    static TlasWide empty() { return TlasWide(); }
+    void build(const Gpu& gpu, const Instance* instances, size_t n, const MeshInfo* meshes, size_t n_mesh) {
+        nodes.assign(2 * n + 1, VdTlasNodeWide{});
+        gpu.check(vd_tlas_build_wide(gpu.ctx(), instances, (uint32_t)n, meshes, (uint32_t)n_mesh, nodes.data()));
+    }
+    void build_fast(const Gpu& gpu, const Instance* instances, size_t n, const MeshInfo* meshes, size_t n_mesh) {
+        nodes.assign(2 * n + 1, VdTlasNodeWide{});
+        gpu.check(vd_tlas_build_lbvh_wide(gpu.ctx(), instances, (uint32_t)n, meshes, (uint32_t)n_mesh, nodes.data()));
+    }
 };
 
 // ---- crates/pools (CPU-side bookkeeping only; GPU buffers stay with the renderer) --------------
@@ -586,6 +608,13 @@ class EmitDraws {
 inline std::vector<VdHit> traverse_tlas(const Gpu& gpu, const VdTraceScene& scene, const std::vector<VdRay>& rays) {
     std::vector<VdHit> out(rays.size());
     gpu.check(vd_trace(gpu.ctx(), &scene, rays.data(), (uint32_t)rays.size(), out.data()));
+    return out;
+}
+
+// ... and over a wide top level (VdTlasNodeWide: 32-bit child ids, voidin_abi.h "vd_trace_wide")
+inline std::vector<VdHit> traverse_tlas(const Gpu& gpu, const VdTraceSceneWide& scene, const std::vector<VdRay>& rays) {
+    std::vector<VdHit> out(rays.size());
+    gpu.check(vd_trace_wide(gpu.ctx(), &scene, rays.data(), (uint32_t)rays.size(), out.data()));
     return out;
 }
 

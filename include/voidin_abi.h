@@ -124,6 +124,7 @@ typedef struct VdHit {
 
 #define VD_MAX_DIST 1e30f
 #define VD_TLAS_MAX_INSTANCES 32768u
+#define VD_TLAS_WIDE_MAX_INSTANCES (1u << 24)   /* vd_tlas_build_lbvh_wide*, vd_trace_wide*: 2^25 + 1 nodes at the most */
 
 #if defined(__cplusplus)
 static_assert(sizeof(VdInstance) == 144, "Instance is 144 B (shared.rs:67-75)");
@@ -621,6 +622,33 @@ int vd_tlas_refit_wide_dev(VdCtx* ctx, const VdInstance* d_instances, uint32_t n
                            const VdMeshInfo* d_meshes, uint32_t n_mesh,
                            VdTlasNodeWide* d_nodes_inout);
 
+/* LBVH top level (NEW, not in the reference): a top level over the reference's LEAF boxes (tlas.rs:34-54, the boxes
+ * vd_tlas_build* writes) that is built on all CUs in a fraction of a millisecond, so it can be REBUILT every frame where the
+ * exact builder - the reference's sequential chain - takes hundreds of milliseconds.  Not the reference's tree: what a ray
+ * hits does not depend on the top level's shape except where two instances tie in distance.
+ * Codes: 30-bit Morton code of the leaf-box centre (10 bits per axis) in the extent of all FINITE centres; a centre with a
+ * non-finite coordinate gets the code 0x3fffffff (it sorts last; its box still folds in with the NaN-ignoring union).  Equal
+ * codes are told apart by their position after the stable sort, so the tree depends on the input alone: two builds of the
+ * same instances give the same bytes.  Boxes fold bottom-up with the union the refit uses (a NaN operand is ignored).
+ * Node array, 2n + 1 slots, shaped like the reference's so that vd_tlas_refit[_wide]_dev takes it as it is:
+ *   1 + j        the leaf of the j-th instance in sorted code order (instance_idx says which instance);
+ *   n+1 .. 2n-2  the interior nodes below the root;
+ *   2n - 1       the TRUE root (n >= 2);
+ *   2n           {left = right = 2n - 1} with the root's box: the reference's closing self-merge (tlas.rs:59);
+ *   0            a copy of node 2n - 1 - not of 2n - so a ray that misses everything walks the tree once.
+ *   n == 1:      node 1 the leaf, node 2 = {left = right = 1}, node 0 a copy of the leaf.
+ * The *_dev forms only enqueue: no host read-back, and no allocation once the context's work memory has reached the size
+ * (one warm-up call at the largest n), so a build can be captured into a HIP graph and replayed.
+ * n > VD_TLAS_MAX_INSTANCES (narrow) => VD_ERR_TLAS_OVERFLOW; n > VD_TLAS_WIDE_MAX_INSTANCES (wide) => VD_ERR_INVALID_ARG.   */
+int vd_tlas_build_lbvh(VdCtx* ctx, const VdInstance* instances, uint32_t n,
+                       const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNode* out_nodes /* 2n+1 */);
+int vd_tlas_build_lbvh_dev(VdCtx* ctx, const VdInstance* d_instances, uint32_t n,
+                           const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNode* d_out_nodes /* 2n+1 */);
+int vd_tlas_build_lbvh_wide(VdCtx* ctx, const VdInstance* instances, uint32_t n,
+                            const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNodeWide* out_nodes /* 2n+1 */);
+int vd_tlas_build_lbvh_wide_dev(VdCtx* ctx, const VdInstance* d_instances, uint32_t n,
+                                const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNodeWide* d_out_nodes /* 2n+1 */);
+
 /* ------------------------------------------------------------------------------------ */
 /* Traversal                                                           */
 /* ------------------------------------------------------------------------------------ */
@@ -654,6 +682,32 @@ int vd_trace(VdCtx* ctx, const VdTraceScene* scene, const VdRay* rays, uint32_t 
              VdHit* out);
 int vd_trace_dev(VdCtx* ctx, const VdTraceScene* d_scene /* struct on host, pointers on device */,
                  const VdRay* d_rays, uint32_t n_rays, VdHit* d_out);
+
+/* The same walk over a WIDE top level (VdTlasNodeWide: 32-bit child ids, more than 32 768 instances).  The record of every
+ * ray is what `traverse_tlas` (bvh.wgsl:89-123) returns when its child ids are 32 bits wide: same visits, near child first,
+ * the far child pushed on `<` in the TLAS loop and on `<=` in the BLAS loop, same arithmetic - so a narrow scene whose nodes
+ * are rewritten as wide ones (left = left_right & 0xffff, right = left_right >> 16), at any indices, gives the records of
+ * vd_trace_dev bit for bit.  Node 0 is the root; a node with left == 0 && right == 0 is a leaf; the array may be ANY
+ * arrangement (leaves need not sit at 1..n) and unreachable slots may hold anything.  VD_ERR_INVALID_ARG for a node a ray
+ * REACHES with a child index >= n_tlas_nodes or, being interior, with left == 0; for everything vd_trace_dev refuses; and,
+ * before anything is launched, for n_tlas_nodes > 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1.  Total like the narrow call (second
+ * pass over a global-memory stack, same limits), same fan-out rule, same per-call de-indexing of the leaves.  Every call
+ * first writes one 64-byte record per top-level node - 48 B read, 64 B written, nothing filled: 235 MB at 2 Mi nodes - into an arena of the
+ * context that only wide calls use, so narrow and wide calls may alternate.  Prepared (VdTraceAccel) wide scenes and
+ * VD_OPT_TRACE_TIGHT_TLAS for them do not exist.                                                                       */
+typedef struct VdTraceSceneWide {
+    const VdTlasNodeWide* tlas_nodes; uint32_t n_tlas_nodes;
+    const VdInstance* instances;    uint32_t n_instances;
+    const VdMeshInfo* meshes;       uint32_t n_meshes;
+    const VdBvhNode*  bvh_nodes;    uint32_t n_bvh_nodes;
+    const float*      vertices;     uint32_t n_vertices;
+    const uint32_t*   indices;      uint32_t n_indices;
+} VdTraceSceneWide;
+int vd_trace_wide(VdCtx* ctx, const VdTraceSceneWide* scene, const VdRay* rays, uint32_t n_rays, VdHit* out);
+int vd_trace_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene /* struct on host, pointers on device */,
+                      const VdRay* d_rays, uint32_t n_rays, VdHit* d_out);
+int vd_trace_any_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays,
+                          uint32_t* d_out_hit);
 
 /* Per-scene preparation for many trace calls over static geometry (the reference binds the six
  * buffers once per scene: app.rs:255-287): the leaf triangles are written out de-indexed, 36 bytes

@@ -52,6 +52,7 @@ assert LOD_GROUP.itemsize == 64 and LOD_PARAMS.itemsize == 16
 MAX_DIST = np.float32(1e30)
 CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run their split form from this many instances
 TLAS_MAX_INSTANCES = 32768
+TLAS_WIDE_MAX_INSTANCES = 1 << 24   # VD_TLAS_WIDE_MAX_INSTANCES: vd_tlas_build_lbvh_wide*, vd_trace_wide*
 MAX_VIEWS = 8             # VD_MAX_VIEWS: cameras per vd_cull_compact_views* call
 BATCH_MAX_MESHES = 4096   # VD_BATCH_MAX_MESHES: meshes per vd_cull_batch* / vd_batch_mask_dev call (one-digit counting sort)
 
@@ -90,6 +91,10 @@ class TraceScene(C.Structure):
                 ("bvh_nodes", C.c_void_p), ("n_bvh_nodes", C.c_uint32),
                 ("vertices", C.c_void_p), ("n_vertices", C.c_uint32),
                 ("indices", C.c_void_p), ("n_indices", C.c_uint32)]
+
+
+class TraceSceneWide(TraceScene):
+    """VdTraceSceneWide (include/voidin_abi.h): the same six buffers with tlas_nodes pointing at VdTlasNodeWide."""
 
 
 class LodParams(C.Structure):
@@ -195,7 +200,14 @@ PROTOTYPES = {
     "vd_tlas_refit": (_I, [_P, _P, _U, _P, _U, _P]),
     "vd_tlas_refit_dev": (_I, [_P, _P, _U, _P, _U, _P]),
     "vd_tlas_refit_wide_dev": (_I, [_P, _P, _U, _P, _U, _P]),
+    "vd_tlas_build_lbvh": (_I, [_P, _P, _U, _P, _U, _P]),
+    "vd_tlas_build_lbvh_dev": (_I, [_P, _P, _U, _P, _U, _P]),
+    "vd_tlas_build_lbvh_wide": (_I, [_P, _P, _U, _P, _U, _P]),
+    "vd_tlas_build_lbvh_wide_dev": (_I, [_P, _P, _U, _P, _U, _P]),
     "vd_trace": (_I, [_P, C.POINTER(TraceScene), _P, _U, _P]),
+    "vd_trace_wide": (_I, [_P, C.POINTER(TraceSceneWide), _P, _U, _P]),
+    "vd_trace_wide_dev": (_I, [_P, C.POINTER(TraceSceneWide), _P, _U, _P]),
+    "vd_trace_any_wide_dev": (_I, [_P, C.POINTER(TraceSceneWide), _P, _U, _P]),
     "vd_trace_dev": (_I, [_P, C.POINTER(TraceScene), _P, _U, _P]),
     "vd_import_external_buffer": (_I, [_P, C.c_int, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "vd_release_external_buffer": (_I, [_P, _P]),

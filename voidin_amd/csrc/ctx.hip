@@ -117,6 +117,8 @@ int vd_ctx_destroy(VdCtx* ctx) {
     if (ctx->trace_ovf) (void)hipFree(ctx->trace_ovf);
     if (ctx->trace_deep) (void)hipFree(ctx->trace_deep);
     if (ctx->refit_state) (void)hipFree(ctx->refit_state);
+    if (ctx->trace_wide) (void)hipFree(ctx->trace_wide);
+    if (ctx->lbvh_state) (void)hipFree(ctx->lbvh_state);
     if (ctx->stage_in) (void)hipFree(ctx->stage_in);
     if (ctx->stage_out) (void)hipFree(ctx->stage_out);
     if (ctx->stage_aux) (void)hipFree(ctx->stage_aux);

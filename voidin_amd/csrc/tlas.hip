@@ -18,6 +18,9 @@
 //        words, which reproduces "strict <, first slot wins";
 //  * refit: leaves recomputed, interior boxes by a bottom-up walk with per-node handshake counters
 //    (write-through agent-scope stores, no fences; boxes re-read L1/L2-bypassing).
+//  * LBVH top level (vd_tlas_build_lbvh*, NOT the reference's tree; also trace.hip's private top level): Morton codes of the
+//    same leaf boxes, a radix sort, Karras' radix tree, boxes bottom-up - a fraction of a millisecond on all CUs, in the
+//    reference's node layout so that the refit above takes it (see lbvh_from_boxes).
 #include "vd_common.hpp"
 
 #include <stdlib.h>
@@ -1210,6 +1213,256 @@ __global__ __launch_bounds__(256) void tlas_refit_up_kernel(Node* nodes, unsigne
     }
 }
 
+// Stable LSD radix sort of (key, value) pairs, 8 bits per pass, for the Morton codes of the LBVH top level
+// (lbvh_from_boxes below).  A UNIT is one wave's 1024 consecutive pairs; units are
+// independent: pass 1 counts a unit's digits, a single-workgroup scan turns the [digit][unit] table into start offsets,
+// pass 2 re-reads the unit in order - 16 groups of 64 - and ranks every pair among the equal digits before it (8 ballots
+// give the lanes with the same digit; the unit's running offsets sit in LDS).
+constexpr unsigned kSortUnit = 1024;
+constexpr int kSortWaves = 4;
+__global__ __launch_bounds__(64 * kSortWaves) void rs_count_kernel(const unsigned* __restrict__ keys, unsigned n, unsigned shift, unsigned n_units,
+                                                                   unsigned* __restrict__ table) {
+    __shared__ unsigned s_h[kSortWaves][256];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
+    for (unsigned d = lane; d < 256u; d += 64u) s_h[wave][d] = 0u;
+    vd_wave_lds_sync();
+    if (unit < n_units) {
+        const unsigned b0 = unit * kSortUnit;
+        for (unsigned g = 0; g < kSortUnit; g += 64u) {
+            const unsigned i = b0 + g + lane;
+            if (i < n) atomicAdd(&s_h[wave][(keys[i] >> shift) & 255u], 1u);
+        }
+        vd_wave_lds_sync();
+        for (unsigned d = lane; d < 256u; d += 64u) table[(size_t)d * n_units + unit] = s_h[wave][d];
+    }
+}
+// exclusive scan of `m` counters in place (single workgroup; thread t owns a contiguous range)
+__global__ __launch_bounds__(1024) void rs_scan_kernel(unsigned* __restrict__ table, unsigned m) {
+    __shared__ unsigned s_wave[16];
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const unsigned per = (m + 1023u) / 1024u;
+    const unsigned lo = min(m, tid * per), hi = min(m, lo + per);
+    unsigned sum = 0;
+    for (unsigned i = lo; i < hi; ++i) sum += table[i];
+    unsigned incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const unsigned t = __shfl_up(incl, off); if (lane >= (unsigned)off) incl += t; }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned run = incl - sum;
+    for (unsigned w = 0; w < wave; ++w) run += s_wave[w];
+    for (unsigned i = lo; i < hi; ++i) { const unsigned c = table[i]; table[i] = run; run += c; }
+}
+__global__ __launch_bounds__(64 * kSortWaves) void rs_scatter_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, unsigned n,
+                                                                     unsigned shift, unsigned n_units, const unsigned* __restrict__ table,
+                                                                     unsigned* __restrict__ keys_out, unsigned* __restrict__ vals_out) {
+    __shared__ unsigned s_off[kSortWaves][256];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
+    if (unit >= n_units) return;
+    for (unsigned d = lane; d < 256u; d += 64u) s_off[wave][d] = table[(size_t)d * n_units + unit];
+    vd_wave_lds_sync();
+    const unsigned b0 = unit * kSortUnit;
+    for (unsigned g = 0; g < kSortUnit; g += 64u) {
+        const unsigned i = b0 + g + lane;
+        const bool valid = i < n;
+        const unsigned key = valid ? keys[i] : 0u, val = valid ? vals[i] : 0u;
+        const unsigned d = (key >> shift) & 255u;
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long bm = __ballot((d >> bit) & 1u);
+            same &= ((d >> bit) & 1u) ? bm : ~bm;
+        }
+        const unsigned rank = vd_mbcnt(same), cnt = (unsigned)__popcll(same);
+        unsigned dst = 0;
+        if (valid) dst = s_off[wave][d] + rank;
+        vd_wave_lds_sync();
+        if (valid && rank == 0u) s_off[wave][d] += cnt;      // the first lane of each digit advances the unit's offset
+        vd_wave_lds_sync();
+        if (valid) { keys_out[dst] = key; vals_out[dst] = val; }
+    }
+}
+
+// ---- LBVH top level (vd_tlas_build_lbvh*, and trace.hip's private top level through vd_tlas_lbvh_from_boxes) ------------
+// ONE implementation for both node types: Morton codes of the box centres (10 bits per axis of the extent of the finite
+// centres), the radix sort above, Karras' binary radix tree (one thread per interior node; equal codes are told apart by
+// their position), boxes bottom-up with box_union (the second child to arrive at a node goes on).  Layout (voidin_abi.h):
+// 1 + j = the leaf of the j-th code in sorted order, n + i = Karras' interior node i >= 1, 2n - 1 = the root (node 0 of
+// Karras), 2n = the reference's self-merge of the root, 0 = a copy of 2n - 1.  Everything is a function of the input
+// alone: the extent is an integer min / max, the sort is stable, a box is the union of its two children whoever computes it.
+constexpr unsigned kLbvhBadCode = 0x3fffffffu;       // a centre with a non-finite coordinate: sorts last
+__device__ __forceinline__ unsigned ord_of(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float of_ord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+__device__ __forceinline__ bool lbvh_centre(const float* __restrict__ boxes, unsigned i, float (&c)[3]) {
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { c[k] = 0.5f * (boxes[6u * i + k] + boxes[6u * i + 3 + k]); finite = finite && fabsf(c[k]) < __builtin_inff(); }
+    return finite;
+}
+__global__ __launch_bounds__(256) void lbvh_leaf_boxes_kernel(const VdInstance* __restrict__ inst, unsigned n, const VdMeshInfo* __restrict__ meshes,
+                                                              unsigned n_mesh, float* __restrict__ boxes) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const Box b = leaf_box(inst, meshes, n_mesh, i);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { boxes[6u * i + k] = b.mn[k]; boxes[6u * i + 3 + k] = b.mx[k]; }
+}
+__global__ __launch_bounds__(256) void lbvh_extent_kernel(const float* __restrict__ boxes, unsigned n, unsigned* __restrict__ ext /*[6]: min xyz, max xyz of the centres*/) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float c[3];
+    if (!lbvh_centre(boxes, i, c)) return;
+    for (int k = 0; k < 3; ++k) { atomicMin(ext + k, ord_of(c[k])); atomicMax(ext + 3 + k, ord_of(c[k])); }
+}
+__device__ __forceinline__ unsigned spread10(unsigned v) {
+    v = (v | (v << 16)) & 0x030000ffu; v = (v | (v << 8)) & 0x0300f00fu; v = (v | (v << 4)) & 0x030c30c3u; v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+__global__ __launch_bounds__(256) void lbvh_keys_kernel(const float* __restrict__ boxes, unsigned n, const unsigned* __restrict__ ext,
+                                                        unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float c[3];
+    unsigned key = kLbvhBadCode;
+    if (lbvh_centre(boxes, i, c)) {
+        unsigned q[3];
+        for (int k = 0; k < 3; ++k) {
+            const float lo = of_ord(ext[k]), hi = of_ord(ext[3 + k]);
+            const float t = hi > lo ? (c[k] - lo) / (hi - lo) : 0.0f;
+            q[k] = (unsigned)fminf(fmaxf(t * 1024.0f, 0.0f), 1023.0f);
+        }
+        key = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
+    }
+    keys[i] = key;
+    vals[i] = i;
+}
+// length of the common prefix of the codes at sorted positions i and j (-1 outside the array); equal codes: their positions decide
+__device__ __forceinline__ int lbvh_delta(const unsigned* __restrict__ keys, int n, int i, int j) {
+    if (j < 0 || j >= n) return -1;
+    const unsigned a = keys[i], b = keys[j];
+    return a != b ? __clz((int)(a ^ b)) : 32 + __clz((int)((unsigned)i ^ (unsigned)j));
+}
+template <typename Node> __device__ __forceinline__ Node lbvh_node(const Box& b, unsigned l, unsigned r, unsigned instance_idx) {
+    Node nd;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { nd.min[k] = b.mn[k]; nd.max[k] = b.mx[k]; }
+    node_set_children(nd, l, r);
+    nd.instance_idx = instance_idx;
+    return nd;
+}
+template <typename Node>
+__global__ __launch_bounds__(256) void lbvh_tree_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, const float* __restrict__ boxes,
+                                                        unsigned n, Node* __restrict__ nodes, unsigned* __restrict__ parent, unsigned* __restrict__ arrived) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x), N = (int)n;
+    if (i >= N) return;
+    {   // the leaf of sorted position i
+        const unsigned inst = vals[i];
+        Box b;
+        for (int k = 0; k < 3; ++k) { b.mn[k] = boxes[6u * inst + k]; b.mx[k] = boxes[6u * inst + 3 + k]; }
+        const Node lf = lbvh_node<Node>(b, 0u, 0u, inst);
+        nodes[1 + i] = lf;
+        if (N == 1) { nodes[0] = lf; nodes[2] = lbvh_node<Node>(b, 1u, 1u, 0xffffffffu); }      // one instance: node 0 is its leaf, node 2 the self-merge
+    }
+    if (i >= N - 1) return;
+    // Karras 2012: direction of the node's range, its other end, the split
+    const int d = lbvh_delta(keys, N, i, i + 1) - lbvh_delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = lbvh_delta(keys, N, i, i - d);
+    int lmax = 2;
+    while (lbvh_delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
+    int l = 0;
+    for (int t = lmax >> 1; t >= 1; t >>= 1) if (lbvh_delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = lbvh_delta(keys, N, i, j);
+    int sp = 0;
+    for (int t = (l + 1) >> 1; ; t = (t + 1) >> 1) {
+        if (lbvh_delta(keys, N, i, i + (sp + t) * d) > dnode) sp += t;
+        if (t == 1) break;
+    }
+    const int gamma = i + sp * d + min(d, 0);
+    const int lo = min(i, j), hi = max(i, j);
+    const unsigned self = i == 0 ? 2u * n - 1u : n + (unsigned)i;
+    const unsigned left = lo == gamma ? 1u + (unsigned)gamma : n + (unsigned)gamma;            // gamma >= 1 when interior: the root is nobody's child
+    const unsigned right = hi == gamma + 1 ? 2u + (unsigned)gamma : n + (unsigned)gamma + 1u;
+    const Box zero = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    const Node nd = lbvh_node<Node>(zero, left, right, 0xffffffffu);
+    nodes[self] = nd;
+    if (i == 0) { nodes[0] = nd; nodes[2u * n] = lbvh_node<Node>(zero, self, self, 0xffffffffu); }      // their boxes: lbvh_fit_kernel, with the root's
+    parent[left] = self; parent[right] = self;
+    arrived[self] = 0u;
+}
+template <typename Node> __device__ __forceinline__ void store_box_agent(Node* nodes, unsigned k, const Box& b) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        __hip_atomic_store(&nodes[k].min[q], b.mn[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&nodes[k].max[q], b.mx[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+template <typename Node>
+__global__ __launch_bounds__(256) void lbvh_fit_kernel(unsigned n, Node* nodes, const unsigned* __restrict__ parent, unsigned* arrived) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || n < 2u) return;
+    unsigned k = 1u + i;                                   // climb from leaf i
+    for (;;) {
+        const unsigned p = parent[k];
+        __threadfence();                                   // my node's box is written before I announce myself
+        if (atomicAdd(arrived + p, 1u) == 0u) return;      // the first child to arrive leaves; the second finds both boxes written
+        __threadfence();
+        unsigned l, r;
+        node_get_children(nodes[p], l, r);
+        const Box b = box_union(load_box_agent(nodes, l), load_box_agent(nodes, r));
+        store_box_agent(nodes, p, b);
+        if (p == 2u * n - 1u) { store_box_agent(nodes, 0u, b); store_box_agent(nodes, 2u * n, b); return; }
+        k = p;
+    }
+}
+
+// work memory of one build: two key and two value arrays, parent links and arrival words for 2n + 2 nodes, the extent, the sort's table
+size_t lbvh_arr_bytes(uint32_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
+template <typename Node>
+int lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, Node* d_nodes, void* work) {
+    hipStream_t st = ctx->stream;
+    const unsigned n_units = (n + kSortUnit - 1u) / kSortUnit;
+    const size_t arr = lbvh_arr_bytes(n);
+    char* base = reinterpret_cast<char*>(work);
+    unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
+    unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
+    unsigned* parent = reinterpret_cast<unsigned*>(base + 4 * arr);                 // 2n + 2 words
+    unsigned* arrived = parent + 2 * (size_t)n + 2;                                 // 2n + 2 words
+    unsigned* ext = arrived + 2 * (size_t)n + 2;                                    // 8 words
+    unsigned* table = ext + 8;                                                      // 256 * n_units words
+    VD_HIP_CHECK(ctx, hipMemsetAsync(ext, 0xff, 12, st));
+    VD_HIP_CHECK(ctx, hipMemsetAsync(ext + 3, 0, 12, st));
+    const unsigned grid = (n + 255u) / 256u;
+    hipLaunchKernelGGL(lbvh_extent_kernel, dim3(grid), dim3(256), 0, st, d_boxes, n, ext);
+    hipLaunchKernelGGL(lbvh_keys_kernel, dim3(grid), dim3(256), 0, st, d_boxes, n, ext, k[0], v[0]);
+    const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int x = pass & 1, y = x ^ 1;
+        hipLaunchKernelGGL(rs_count_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], n, 8u * pass, n_units, table);
+        hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, 256u * n_units);
+        hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], n, 8u * pass, n_units, table, k[y], v[y]);
+    }
+    hipLaunchKernelGGL((lbvh_tree_kernel<Node>), dim3(grid), dim3(256), 0, st, k[0], v[0], d_boxes, n, d_nodes, parent, arrived);
+    hipLaunchKernelGGL((lbvh_fit_kernel<Node>), dim3(grid), dim3(256), 0, st, n, d_nodes, parent, arrived);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
+}
+
+// vd_tlas_build_lbvh*: the reference's leaf boxes, then the builder above.  The work memory is an arena of the context
+// that only grows: once it has reached the size of the largest n, a call enqueues and nothing else.
+template <typename Node>
+int tlas_lbvh_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, Node* d_nodes) {
+    const size_t box_bytes = ((size_t)24 * n + 255) & ~(size_t)255;
+    int rc = vd_ensure(ctx, &ctx->lbvh_state, &ctx->lbvh_state_bytes, box_bytes + vd_lbvh_work_bytes(n));
+    if (rc) return rc;
+    float* boxes = reinterpret_cast<float*>(ctx->lbvh_state);
+    vd_time_begin(ctx);
+    hipLaunchKernelGGL(lbvh_leaf_boxes_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_inst, n, d_meshes, n_mesh, boxes);
+    rc = lbvh_from_boxes<Node>(ctx, boxes, n, d_nodes, reinterpret_cast<char*>(ctx->lbvh_state) + box_bytes);
+    vd_time_end(ctx);
+    return rc;
+}
+
 template <typename Node>
 int tlas_build_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
                     Node* d_nodes) {
@@ -1351,11 +1604,12 @@ int tlas_refit_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMe
     return VD_OK;
 }
 
-int check_args(VdCtx* ctx, const void* inst, uint32_t n, const void* meshes, uint32_t n_mesh, const void* nodes, bool wide) {
+int check_args(VdCtx* ctx, const void* inst, uint32_t n, const void* meshes, uint32_t n_mesh, const void* nodes, bool wide, bool lbvh = false) {
     if (!ctx) return VD_ERR_INVALID_ARG;
     if (!inst || !meshes || !nodes || n == 0 || n_mesh == 0) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_tlas_*: null pointer or zero count");
     if (!wide && n > VD_TLAS_MAX_INSTANCES)
         VD_FAIL(ctx, VD_ERR_TLAS_OVERFLOW, "vd_tlas_*: n > 32768 does not fit the 16-bit left_right packing (tlas.rs:71); use the _wide variant");
+    if (lbvh && n > VD_TLAS_WIDE_MAX_INSTANCES) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_tlas_build_lbvh_wide: n > VD_TLAS_WIDE_MAX_INSTANCES");
     if (n > 0x3fffffffu) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_tlas_*: n too large");
     return VD_OK;
 }
@@ -1391,7 +1645,47 @@ int vd_tlas_build_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTla
     return tlas_build_impl<VdTlasNode>(ctx, reinterpret_cast<const VdInstance*>(d_boxes), n, nullptr, 0u, d_nodes);
 }
 
+size_t vd_lbvh_work_bytes(uint32_t n) {
+    return 4 * lbvh_arr_bytes(n) + 4 * (4 * (size_t)n + 4 + 8 + 256 * (size_t)((n + kSortUnit - 1u) / kSortUnit)) + 256;
+}
+int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes, void* work) {
+    if (!ctx || !d_boxes || !d_nodes || !work || n == 0 || n > VD_TLAS_MAX_INSTANCES) return VD_ERR_INVALID_ARG;
+    return lbvh_from_boxes<VdTlasNode>(ctx, d_boxes, n, d_nodes, work);
+}
+
 extern "C" {
+
+int vd_tlas_build_lbvh_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                           VdTlasNode* d_nodes) {
+    VdDeviceGuard vd_guard_(ctx);
+    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, false, true);
+    if (!rc) ctx->fan_forget(d_nodes);
+    return rc ? rc : tlas_lbvh_impl<VdTlasNode>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+}
+int vd_tlas_build_lbvh_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                                VdTlasNodeWide* d_nodes) {
+    VdDeviceGuard vd_guard_(ctx);
+    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, true, true);
+    if (!rc) ctx->fan_forget(d_nodes);
+    return rc ? rc : tlas_lbvh_impl<VdTlasNodeWide>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+}
+int vd_tlas_build_lbvh(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNode* nodes) {
+    VdDeviceGuard vd_guard_(ctx);
+    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, false, true);
+    if (rc) return rc;
+    return tlas_host<VdTlasNode>(ctx, inst, n, meshes, n_mesh, nodes, false, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNode* dn) {
+        return tlas_lbvh_impl<VdTlasNode>(ctx, di, n, dm, n_mesh, dn);
+    });
+}
+int vd_tlas_build_lbvh_wide(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh,
+                            VdTlasNodeWide* nodes) {
+    VdDeviceGuard vd_guard_(ctx);
+    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, true, true);
+    if (rc) return rc;
+    return tlas_host<VdTlasNodeWide>(ctx, inst, n, meshes, n_mesh, nodes, false, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNodeWide* dn) {
+        return tlas_lbvh_impl<VdTlasNodeWide>(ctx, di, n, dm, n_mesh, dn);
+    });
+}
 
 int vd_tlas_build_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
                       VdTlasNode* d_nodes) {

@@ -145,7 +145,21 @@ constexpr unsigned kWavesPerCu = 24;    // persistent grid = what is resident (6
 // FAN: the fan-out's code is compiled in (src.fan says what this launch hands out and whether it may append jobs).
 // DEEP: the second pass over the rays whose stack overflowed (launch_trace) - same walk, entries 128.. in s.deep.
 // Every kernel that calls this runs one wave per workgroup.
-template <bool ANY, bool PREP, bool FAN = false, bool DEEP = false>
+// WIDE: the top level is an array of VdTlasNodeWide (vd_trace_wide*: 32-bit child ids), which Scene::tlas then points at.
+// What differs is how a TLAS node is named.  Narrow: an interior node is its left_right word, a leaf its index << 16 - in
+// a stack entry, in FanJob.node and as the current node cn = {left_right, own index}.  Wide: a node is its own INDEX, with
+// bit 31 set for a leaf, and cn = {1 interior / 0 leaf, index}; the 64-byte record of an interior node sits at the node's
+// own index and holds both children's boxes with their cn words (records_wide_kernel), so a step is one line as before
+// and no record is shared between two parents.
+// (The narrow forms stay written out where they are used, behind `WIDE ? ... :` - a constant the front end folds: moved
+// into functions like these, the narrow kernels came out with other register numbers.)
+__device__ __forceinline__ uint2 tl_node_wide(unsigned w) { return make_uint2((w >> 31) ^ 1u, w & 0x7fffffffu); }
+__device__ __forceinline__ unsigned tl_word_wide(const uint2 cn) { return cn.x != 0u ? cn.y : (cn.y | 0x80000000u); }
+template <bool WIDE, typename S> __device__ __forceinline__ unsigned tl_instance(const S& s, unsigned leaf) {
+    if constexpr (WIDE) return reinterpret_cast<const VdTlasNodeWide*>(s.tlas)[leaf].instance_idx;
+    else return s.tlas[leaf].instance_idx;
+}
+template <bool ANY, bool PREP, bool FAN = false, bool DEEP = false, bool WIDE = false>
 __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restrict__ rays, const RaySource& src, VdHit* __restrict__ out,
                                            unsigned* __restrict__ out_any, unsigned* __restrict__ overflow) {
     const unsigned lane = threadIdx.x & 63u;
@@ -189,7 +203,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
         if (DEEP && head >= 2u * (unsigned)kStack) w = s.deep[deep_base + (size_t)(head - 2u * (unsigned)kStack) * 64u];
         else w = head < (unsigned)kLdsStack ? s_stack[head][lane] : stack[head - (unsigned)kLdsStack];
         if (((st & kInBlas) != 0u)) cn = make_uint2(w & 0x3fffffffu, w >> 30);
-        else cn = (w & 0xffffu) ? make_uint2(w, 0xffffffffu) : make_uint2(0u, w >> 16);
+        else cn = WIDE ? tl_node_wide(w) : ((w & 0xffffu) ? make_uint2(w, 0xffffffffu) : make_uint2(0u, w >> 16));
     };
     for (;;) {
         // ---- retire finished rays, refill idle lanes ----
@@ -203,14 +217,14 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                     const unsigned rid = J->ray_id;
                     if (ANY) out_any[rid] = 1u;
                     else {
-                        J->lim = res.dist; J->node = s.tlas[res.instance].instance_idx; J->tri = res.triangle;
+                        J->lim = res.dist; J->node = tl_instance<WIDE>(s, res.instance); J->tri = res.triangle;
                         atomicMin(src.fan.best + rid, ((unsigned long long)__float_as_uint(res.dist) << 32) | J->key);
                     }
                 }
                 J->state = (res.hit && !ANY) ? FAN_HIT : FAN_MISS;
             } else
             if (ANY) out_any[ray_id] = res.hit;
-            else { if (res.hit) res.instance = s.tlas[res.instance].instance_idx; out[ray_id] = res; }   // hits carry the leaf node until here
+            else { if (res.hit) res.instance = tl_instance<WIDE>(s, res.instance); out[ray_id] = res; }   // hits carry the leaf node until here
             st &= ~kBusy;
         }
         const unsigned long long busy_mask = __ballot(((st & kBusy) != 0u));
@@ -248,7 +262,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                         }
                         res.dist = lim; res.hit = 0u; res.instance = 0xffffffffu; res.triangle = 0xffffffffu;
                         const unsigned w = j2.y;                       // the subtree, as the stack held it (pop)
-                        cn = (w & 0xffffu) ? make_uint2(w, 0xffffffffu) : make_uint2(0u, w >> 16);
+                        cn = WIDE ? tl_node_wide(w) : ((w & 0xffffu) ? make_uint2(w, 0xffffffffu) : make_uint2(0u, w >> 16));
                         ray_id = 0x80000000u | (job_begin + pos); st |= kBusy; st &= ~kDone; st &= ~kInBlas; head = 0; blas_base = 0;
                         if (FAN && kFanAge) s_born[lane] = wave_iters;
                     }
@@ -260,8 +274,13 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                     world.ix = 1.0f / world.dx; world.iy = 1.0f / world.dy; world.iz = 1.0f / world.dz;   // ray_new: inv_dir = 1. / dir
                     ray = world;
                     res.dist = kMaxDist; res.hit = 0u; res.instance = 0xffffffffu; res.triangle = 0xffffffffu;
+                    if constexpr (WIDE) {
+                        const VdTlasNodeWide* root = reinterpret_cast<const VdTlasNodeWide*>(s.tlas);
+                        cn = make_uint2((root->left | root->right) != 0u ? 1u : 0u, 0u);
+                    } else {
                     const VdTlasNode root = s.tlas[0];
                     cn = make_uint2(root.left_right, 0u);          // .y of a TLAS leaf = its node index
+                    }
                     ray_id = id; st |= kBusy; st &= ~kDone; st &= ~kInBlas; head = 0; blas_base = 0;
                     if (FAN && kFanAge) s_born[lane] = wave_iters;
                 }
@@ -278,7 +297,13 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                 const bool can = live && (st & kInBlas) == 0u && (!kFanAge || wave_iters - s_born[kFanAge ? lane : 0u] >= kFanAge);
                 // the bottom entry of a ray that came through the reference's root: the true root's second visit (see above)
                 unsigned dup_word = 0u;
-                {
+                if constexpr (WIDE) {      // the root's own record names both children as stack words
+                    const VdTlasNodeWide* root = reinterpret_cast<const VdTlasNodeWide*>(s.tlas);
+                    if (root->left != 0u && root->left == root->right) {
+                        const float4 c0 = s.tpair[0], c1 = s.tpair[1];
+                        if (__float_as_uint(c0.w) != 0xffffffffu) dup_word = tl_word_wide(make_uint2(__float_as_uint(c0.w), __float_as_uint(c1.w)));
+                    }
+                } else {
                     const unsigned lr = s.tlas[0].left_right, l = lr & 0xffffu;
                     if (lr != 0u && l == (lr >> 16)) { const unsigned w2 = s.tlas[l].left_right; dup_word = w2 != 0u ? w2 : (l << 16); }
                 }
@@ -310,7 +335,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                         const uint4 r0 = make_uint4(__float_as_uint(world.ex), __float_as_uint(world.ey), __float_as_uint(world.ez), __float_as_uint(world.dx));
                         const unsigned dyb = __float_as_uint(world.dy), dzb = __float_as_uint(world.dz), limb = __float_as_uint(res.dist);
                         // digit 0: what the ray has found so far, as a finished job
-                        const unsigned inst0 = res.hit ? s.tlas[res.instance].instance_idx : 0xffffffffu;
+                        const unsigned inst0 = res.hit ? tl_instance<WIDE>(s, res.instance) : 0xffffffffu;
                         O[0] = r0; O[1] = make_uint4(dyb, dzb, limb, rid);
                         O[2] = make_uint4(pkey, inst0, (res.hit && !ANY) ? FAN_HIT : FAN_MISS, res.triangle);
                         if (res.hit && !ANY) atomicMin(src.fan.best + rid, ((unsigned long long)limb << 32) | pkey);
@@ -320,7 +345,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                         }
                         // digit 1: the node the ray is at; digits 2..: the stack, top first
                         O[3] = r0; O[4] = make_uint4(dyb, dzb, limb, rid);
-                        O[5] = make_uint4(pkey | (1u << shift), cn.x != 0u ? cn.x : (cn.y << 16), FAN_PENDING, 0u);
+                        O[5] = make_uint4(pkey | (1u << shift), WIDE ? tl_word_wide(cn) : (cn.x != 0u ? cn.x : (cn.y << 16)), FAN_PENDING, 0u);
                         for (unsigned e = 0; e < n_ent; ++e) {
                             const unsigned at = head - 1u - e;
                             const unsigned w = at < (unsigned)kLdsStack ? s_stack[at][lane] : stack[at - (unsigned)kLdsStack];
@@ -386,6 +411,9 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
             } else if (((st & kInBlas) != 0u)) {
                 p0 = reinterpret_cast<const char*>(s.bvh + (bvh_index + cn.x));
                 p1 = p0 + sizeof(VdBvhNode);
+            } else if constexpr (WIDE) {      // both children as ONE line: the node's own record
+                p0 = reinterpret_cast<const char*>(s.tpair + 4u * (size_t)cn.y);
+                p1 = p0 + sizeof(VdBvhNode);
             } else {
                 idx0 = cn.x & 0xffffu; idx1 = cn.x >> 16u;       // both children as ONE line: the pair record at the left child's index
                 p0 = reinterpret_cast<const char*>(s.tpair + 4u * (size_t)idx0);
@@ -426,6 +454,9 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                 blas_base = head;
                 cn = make_uint2(rw & 0x3fffffffu, rw >> 30);
                 if (cn.y != 0u) continue;                                // a mesh of <= 3 triangles: its root is a leaf
+            } else if (WIDE) {
+                // a child index outside the array, or an interior node without a left child (records_wide_kernel)
+                if (!((st & kInBlas) != 0u) && __float_as_uint(a0.w) == 0xffffffffu) { st |= kBadEntry; st |= kDone; continue; }
             } else if (!((st & kInBlas) != 0u) && __float_as_uint(a1.w) != idx1) {
                 // the pair record at idx0 was written for another right child: some unreachable slot of the TLAS array names
                 // the same left child (records_kernel) - read the two nodes themselves
@@ -440,6 +471,9 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
             // payload of a child: BLAS {left_first, count}; TLAS {left_right, its own node index}
             uint2 near = make_uint2(__float_as_uint(a0.w), ((st & kInBlas) != 0u) ? __float_as_uint(a1.w) : idx0);
             uint2 far = make_uint2(__float_as_uint(b0.w), ((st & kInBlas) != 0u) ? __float_as_uint(b1.w) : idx1);
+            if constexpr (WIDE) {      // a TLAS record holds its children's cn words where a BLAS node holds {left_first, count}
+                near.y = __float_as_uint(a1.w); far.y = __float_as_uint(b1.w);
+            }
             if (min_dist > max_dist) {
                 const uint2 tu = near; near = far; far = tu;
                 const float tf = min_dist; min_dist = max_dist; max_dist = tf;
@@ -461,7 +495,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                     if (head - 2u * (unsigned)kStack >= s.deep_cap) { st |= kOvf; st |= kDone; continue; }
                 }
                 if (blas_now && far.y > 3u) st |= kBadLeaf;   // not representable in a stack entry
-                const unsigned w_blas = far.x | (far.y << 30), w_tlas = far.x != 0u ? far.x : (far.y << 16);
+                const unsigned w_blas = far.x | (far.y << 30), w_tlas = WIDE ? tl_word_wide(far) : (far.x != 0u ? far.x : (far.y << 16));
                 const unsigned w = blas_now ? w_blas : w_tlas;
                 if (DEEP && head >= 2u * (unsigned)kStack) s.deep[deep_base + (size_t)(head - 2u * (unsigned)kStack) * 64u] = w;
                 else if (head < (unsigned)kLdsStack) s_stack[head][lane] = w; else stack[head - (unsigned)kLdsStack] = w;
@@ -554,6 +588,25 @@ void trace_deep_kernel(Scene s, const VdRay* __restrict__ rays, const unsigned* 
     const unsigned n = *n_list;
     const RaySource src{list, n, next_ray};
     trace_body<ANY, PREP, false, true>(s, rays, src, out, out_any, overflow);
+}
+// The same three entry points over a wide top level (vd_trace_wide*): a.tlas / s.tlas point at VdTlasNodeWide, irec and tpair at
+// the one record table (records_wide_kernel).
+template <bool ANY, bool PREP, bool FAN>
+__global__ __launch_bounds__(64, FAN ? kFanWps : 6)
+void trace_wide_kernel(SceneArgs a, const VdRay* __restrict__ rays, unsigned n_rays, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
+                       unsigned* __restrict__ overflow, unsigned* next_ray, const float* __restrict__ tris, const unsigned* __restrict__ gate, Fan fan) {
+    if (gate && (*gate != 0u) == PREP) return;          // as above: the de-indexing of this call decides which of the two kernels walks
+    const Scene s{a.tlas, a.inst, a.meshes, a.bvh, a.verts, a.indices, a.n_meshes, PREP ? tris : nullptr, a.irec, a.tpair, a.mrec, a.yield, a.ovf_bits};
+    const RaySource src{nullptr, n_rays, next_ray, fan};
+    trace_body<ANY, PREP, FAN, false, true>(s, rays, src, out, out_any, overflow);
+}
+template <bool ANY, bool PREP>
+__global__ __launch_bounds__(64, 4)
+void trace_deep_wide_kernel(Scene s, const VdRay* __restrict__ rays, const unsigned* __restrict__ list, const unsigned* __restrict__ n_list,
+                            VdHit* __restrict__ out, unsigned* __restrict__ out_any, unsigned* __restrict__ overflow, unsigned* next_ray) {
+    const unsigned n = *n_list;
+    const RaySource src{list, n, next_ray};
+    trace_body<ANY, PREP, false, true, true>(s, rays, src, out, out_any, overflow);
 }
 // bitmap of the first pass -> list of ray ids (any order: a ray's record depends on the ray alone).  n_words = ceil(n_rays / 32);
 // bits of the last word that name no ray of this call are dropped: the list holds n_rays ids, rays[] and out[] n_rays records.
@@ -751,76 +804,6 @@ __global__ __launch_bounds__(64) void traverse_rec_kernel(const VdBvhNode* __res
     if (ovf) atomicOr(overflow, 1u);
 }
 
-// Stable LSD radix sort of (key, value) pairs, 8 bits per pass, for the Morton codes of the LBVH top level
-// (build_tight_tlas, VD_OPT_TRACE_TIGHT_TLAS = 2).  A UNIT is one wave's 1024 consecutive pairs; units are
-// independent: pass 1 counts a unit's digits, a single-workgroup scan turns the [digit][unit] table into start offsets,
-// pass 2 re-reads the unit in order - 16 groups of 64 - and ranks every pair among the equal digits before it (8 ballots
-// give the lanes with the same digit; the unit's running offsets sit in LDS).
-constexpr unsigned kSortUnit = 1024;
-constexpr int kSortWaves = 4;
-__global__ __launch_bounds__(64 * kSortWaves) void rs_count_kernel(const unsigned* __restrict__ keys, unsigned n, unsigned shift, unsigned n_units,
-                                                                   unsigned* __restrict__ table) {
-    __shared__ unsigned s_h[kSortWaves][256];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
-    for (unsigned d = lane; d < 256u; d += 64u) s_h[wave][d] = 0u;
-    vd_wave_lds_sync();
-    if (unit < n_units) {
-        const unsigned b0 = unit * kSortUnit;
-        for (unsigned g = 0; g < kSortUnit; g += 64u) {
-            const unsigned i = b0 + g + lane;
-            if (i < n) atomicAdd(&s_h[wave][(keys[i] >> shift) & 255u], 1u);
-        }
-        vd_wave_lds_sync();
-        for (unsigned d = lane; d < 256u; d += 64u) table[(size_t)d * n_units + unit] = s_h[wave][d];
-    }
-}
-// exclusive scan of `m` counters in place (single workgroup; thread t owns a contiguous range)
-__global__ __launch_bounds__(1024) void rs_scan_kernel(unsigned* __restrict__ table, unsigned m) {
-    __shared__ unsigned s_wave[16];
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const unsigned per = (m + 1023u) / 1024u;
-    const unsigned lo = min(m, tid * per), hi = min(m, lo + per);
-    unsigned sum = 0;
-    for (unsigned i = lo; i < hi; ++i) sum += table[i];
-    unsigned incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const unsigned t = __shfl_up(incl, off); if (lane >= (unsigned)off) incl += t; }
-    if (lane == 63u) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned run = incl - sum;
-    for (unsigned w = 0; w < wave; ++w) run += s_wave[w];
-    for (unsigned i = lo; i < hi; ++i) { const unsigned c = table[i]; table[i] = run; run += c; }
-}
-__global__ __launch_bounds__(64 * kSortWaves) void rs_scatter_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, unsigned n,
-                                                                     unsigned shift, unsigned n_units, const unsigned* __restrict__ table,
-                                                                     unsigned* __restrict__ keys_out, unsigned* __restrict__ vals_out) {
-    __shared__ unsigned s_off[kSortWaves][256];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
-    if (unit >= n_units) return;
-    for (unsigned d = lane; d < 256u; d += 64u) s_off[wave][d] = table[(size_t)d * n_units + unit];
-    vd_wave_lds_sync();
-    const unsigned b0 = unit * kSortUnit;
-    for (unsigned g = 0; g < kSortUnit; g += 64u) {
-        const unsigned i = b0 + g + lane;
-        const bool valid = i < n;
-        const unsigned key = valid ? keys[i] : 0u, val = valid ? vals[i] : 0u;
-        const unsigned d = (key >> shift) & 255u;
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const unsigned long long bm = __ballot((d >> bit) & 1u);
-            same &= ((d >> bit) & 1u) ? bm : ~bm;
-        }
-        const unsigned rank = vd_mbcnt(same), cnt = (unsigned)__popcll(same);
-        unsigned dst = 0;
-        if (valid) dst = s_off[wave][d] + rank;
-        vd_wave_lds_sync();
-        if (valid && rank == 0u) s_off[wave][d] += cnt;      // the first lane of each digit advances the unit's offset
-        vd_wave_lds_sync();
-        if (valid) { keys_out[dst] = key; vals_out[dst] = val; }
-    }
-}
-
 // Per-call records: what the walk reads at a TLAS step and when it enters an instance, re-laid so that each is ONE line.
 // The bound of this kernel family is the number of distinct lines a CU can fetch (tools/probe_gather.hip:
 // profiles/r03_probe_gather.log), so the lines per ray are what counts:
@@ -848,6 +831,42 @@ __global__ __launch_bounds__(256) void pair_owner_kernel(const VdTlasNode* __res
     if (lr != 0u && (lr & 0xffffu) < n_nodes && (lr >> 16u) < n_nodes) atomicMin(owner + (lr & 0xffffu), k);
 }
 
+// (the two records every top level shares, as functions for records_wide_kernel; records_kernel below keeps its own text:
+//  written through these it compiled to other instructions)
+__device__ __forceinline__ void mesh_record(const VdMeshInfo* __restrict__ meshes, const VdBvhNode* __restrict__ bvh, unsigned n_bvh,
+                                            float4* __restrict__ mrec, unsigned k) {
+    {
+        const VdMeshInfo mesh = meshes[k];
+        float4* R = mrec + 8u * (size_t)k;
+        unsigned rw = 0xffffffffu;
+        if (mesh.bvh_index < n_bvh) {
+            const VdBvhNode root = bvh[mesh.bvh_index];
+            if (root.count <= 3u && root.left_first < (1u << 30)) {        // else: not a BvhBuilder tree (blas.rs:108)
+                if (root.count != 0u) rw = root.left_first | (root.count << 30);
+                else {
+                    const size_t c = (size_t)mesh.bvh_index + root.left_first;
+                    if (c + 1u < n_bvh) {
+                        const float4* src = reinterpret_cast<const float4*>(bvh + c);
+                        R[4] = src[0]; R[5] = src[1]; R[6] = src[2]; R[7] = src[3];
+                        rw = root.left_first;
+                    }
+                }
+            }
+        }
+        R[0] = make_float4(__uint_as_float(mesh.bvh_index), __uint_as_float(mesh.base_index), __uint_as_float((unsigned)mesh.vertex_offset),
+                           __uint_as_float(rw));
+    }
+}
+__device__ __forceinline__ void entry_record(const VdInstance* __restrict__ inst, unsigned n_inst, unsigned n_meshes, unsigned instance_idx,
+                                             float4* __restrict__ R) {
+    if (instance_idx >= n_inst) { R[3] = make_float4(0.0f, __uint_as_float(1u), 0.0f, 0.0f); return; }
+    const VdInstance* I = inst + instance_idx;
+    const float* M = I->inv_transform;
+    R[0] = make_float4(M[0], M[4], M[8], M[12]);
+    R[1] = make_float4(M[1], M[5], M[9], M[13]);
+    R[2] = make_float4(M[2], M[6], M[10], M[14]);
+    R[3] = make_float4(__uint_as_float(min(I->mesh, n_meshes - 1u)), __uint_as_float(0u), 0.0f, 0.0f);
+}
 __global__ __launch_bounds__(256) void records_kernel(const VdTlasNode* __restrict__ tlas, unsigned n_nodes, const VdInstance* __restrict__ inst,
                                                       unsigned n_inst, const VdMeshInfo* __restrict__ meshes, unsigned n_meshes,
                                                       const VdBvhNode* __restrict__ bvh, unsigned n_bvh, float4* __restrict__ irec,
@@ -895,6 +914,34 @@ __global__ __launch_bounds__(256) void records_kernel(const VdTlasNode* __restri
     R[1] = make_float4(M[1], M[5], M[9], M[13]);
     R[2] = make_float4(M[2], M[6], M[10], M[14]);
     R[3] = make_float4(__uint_as_float(min(I->mesh, n_meshes - 1u)), __uint_as_float(0u), 0.0f, 0.0f);
+}
+
+// The records of a WIDE top level: ONE 64-byte record per node, at the node's own index (grid-stride: up to 2^25 + 1 nodes).
+//   leaf (left == right == 0): its entry record, as above;
+//   interior: {min0, x0 | max0, y0 | min1, x1 | max1, y1} - the boxes of both children with the words the walk holds for
+//   a node it is at: x = 1 interior / 0 leaf, y = the child's index (tl_node).  x0 = 0xffffffff marks a node no ray may
+//   step: a child index outside the array, or left == 0 (what a leaf's word would say).
+// Every slot below n_nodes is written by its own node and no child index above n_nodes is ever followed, so nothing is
+// filled beforehand and no record has two writers - what the narrow walk needs owners and tags for.
+__global__ __launch_bounds__(256) void records_wide_kernel(const VdTlasNodeWide* __restrict__ tlas, unsigned n_nodes, const VdInstance* __restrict__ inst,
+                                                           unsigned n_inst, const VdMeshInfo* __restrict__ meshes, unsigned n_meshes,
+                                                           const VdBvhNode* __restrict__ bvh, unsigned n_bvh, float4* __restrict__ rec,
+                                                           float4* __restrict__ mrec) {
+    for (unsigned k = blockIdx.x * 256u + threadIdx.x; k < max(n_nodes, n_meshes); k += gridDim.x * 256u) {
+        if (k < n_meshes) mesh_record(meshes, bvh, n_bvh, mrec, k);
+        if (k >= n_nodes) continue;
+        const uint4* N = reinterpret_cast<const uint4*>(tlas + k);
+        const unsigned left = N[0].w, right = N[1].w;
+        float4* R = rec + 4u * (size_t)k;
+        if (left == 0u && right == 0u) { entry_record(inst, n_inst, n_meshes, N[2].x, R); continue; }
+        if (left == 0u || left >= n_nodes || right >= n_nodes) { R[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu)); continue; }
+        const float4* c0 = reinterpret_cast<const float4*>(tlas + left);
+        const float4* c1 = reinterpret_cast<const float4*>(tlas + right);
+        float4 a0 = c0[0], a1 = c0[1], b0 = c1[0], b1 = c1[1];
+        a0.w = __uint_as_float((__float_as_uint(a0.w) | __float_as_uint(a1.w)) != 0u ? 1u : 0u); a1.w = __uint_as_float(left);
+        b0.w = __uint_as_float((__float_as_uint(b0.w) | __float_as_uint(b1.w)) != 0u ? 1u : 0u); b1.w = __uint_as_float(right);
+        R[0] = a0; R[1] = a1; R[2] = b0; R[3] = b1;
+    }
 }
 
 // De-indexed leaf triangles: tris[9 * (base_index / 3 + t)] = the three vertices fetch_vertex (bvh.wgsl:30-33) returns for
@@ -997,115 +1044,25 @@ __global__ void tight_root_kernel(VdTlasNode* nodes, unsigned n) {
     if (threadIdx.x == 0 && blockIdx.x == 0 && n >= 2u) nodes[0] = nodes[2u * n - 1u];
 }
 
-// ---- the private top level as an LBVH (VD_OPT_TRACE_TIGHT_TLAS = 2): built on all CUs in ~0.1 ms, so it can follow moving
-// instances every frame (vd_trace_accel_update_dev); the agglomerative builder (= 1) makes the better tree and takes the
-// reference's sequential chain to do it.  Morton codes of the box centres (10 bits per axis of the scene's extent), the
-// radix sort above (rs_*_kernel), Karras' binary radix tree (one thread per interior node; equal codes are told apart by
-// their position), boxes bottom-up (the second child to arrive at a node goes on).  Nodes: 0 = the root, 1 + j = the
-// leaf of the j-th code in sorted order, n + i = interior node i (i >= 1): indices stay below 2n <= 65 536.
-__device__ __forceinline__ unsigned ord_of(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float of_ord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-__global__ __launch_bounds__(256) void lbvh_extent_kernel(const float* __restrict__ boxes, unsigned n, unsigned* __restrict__ ext /*[6]: min xyz, max xyz of the centres*/) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    for (int k = 0; k < 3; ++k) {
-        const float c = 0.5f * (boxes[6u * i + k] + boxes[6u * i + 3 + k]);
-        atomicMin(ext + k, ord_of(c)); atomicMax(ext + 3 + k, ord_of(c));
-    }
-}
-__device__ __forceinline__ unsigned spread10(unsigned v) {
-    v = (v | (v << 16)) & 0x030000ffu; v = (v | (v << 8)) & 0x0300f00fu; v = (v | (v << 4)) & 0x030c30c3u; v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-__global__ __launch_bounds__(256) void lbvh_keys_kernel(const float* __restrict__ boxes, unsigned n, const unsigned* __restrict__ ext,
-                                                        unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    unsigned q[3];
-    for (int k = 0; k < 3; ++k) {
-        const float lo = of_ord(ext[k]), hi = of_ord(ext[3 + k]);
-        const float c = 0.5f * (boxes[6u * i + k] + boxes[6u * i + 3 + k]);
-        const float t = hi > lo ? (c - lo) / (hi - lo) : 0.0f;
-        q[k] = (unsigned)fminf(fmaxf(t * 1024.0f, 0.0f), 1023.0f);
-    }
-    keys[i] = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
-    vals[i] = i;
-}
-// length of the common prefix of the codes at sorted positions i and j (-1 outside the array); equal codes: their positions decide
-__device__ __forceinline__ int lbvh_delta(const unsigned* __restrict__ keys, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    const unsigned a = keys[i], b = keys[j];
-    return a != b ? __clz((int)(a ^ b)) : 32 + __clz((int)((unsigned)i ^ (unsigned)j));
-}
-__global__ __launch_bounds__(256) void lbvh_tree_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, const float* __restrict__ boxes,
-                                                        unsigned n, VdTlasNode* __restrict__ nodes, unsigned* __restrict__ parent, unsigned* __restrict__ arrived) {
-    const int i = (int)(blockIdx.x * 256u + threadIdx.x), N = (int)n;
-    if (i >= N) return;
-    {   // the leaf of sorted position i
-        const unsigned inst = vals[i];
-        VdTlasNode lf;
-        for (int k = 0; k < 3; ++k) { lf.min[k] = boxes[6u * inst + k]; lf.max[k] = boxes[6u * inst + 3 + k]; }
-        lf.left_right = 0u; lf.instance_idx = inst;
-        nodes[1 + i] = lf;
-    }
-    if (i >= N - 1) return;
-    // Karras 2012: direction of the node's range, its other end, the split
-    const int d = lbvh_delta(keys, N, i, i + 1) - lbvh_delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = lbvh_delta(keys, N, i, i - d);
-    int lmax = 2;
-    while (lbvh_delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1) if (lbvh_delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = lbvh_delta(keys, N, i, j);
-    int sp = 0;
-    for (int t = (l + 1) >> 1; ; t = (t + 1) >> 1) {
-        if (lbvh_delta(keys, N, i, i + (sp + t) * d) > dnode) sp += t;
-        if (t == 1) break;
-    }
-    const int gamma = i + sp * d + min(d, 0);
-    const int lo = min(i, j), hi = max(i, j);
-    const unsigned self = i == 0 ? 0u : n + (unsigned)i;
-    const unsigned left = lo == gamma ? 1u + (unsigned)gamma : n + (unsigned)gamma;            // gamma >= 1 when interior: the root is nobody's child
-    const unsigned right = hi == gamma + 1 ? 2u + (unsigned)gamma : n + (unsigned)gamma + 1u;
-    VdTlasNode nd;
-    for (int k = 0; k < 3; ++k) { nd.min[k] = 0.0f; nd.max[k] = 0.0f; }
-    nd.left_right = left | (right << 16); nd.instance_idx = 0xffffffffu;
-    nodes[self] = nd;
-    parent[left] = self; parent[right] = self;
-    arrived[self] = 0u;
-}
-__global__ __launch_bounds__(256) void lbvh_fit_kernel(unsigned n, VdTlasNode* nodes, const unsigned* __restrict__ parent, unsigned* arrived) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    unsigned k = 1u + i;                                   // climb from leaf i
-    for (;;) {
-        const unsigned p = parent[k];
-        __threadfence();                                   // my node's box is written before I announce myself
-        if (atomicAdd(arrived + p, 1u) == 0u) return;      // the first child to arrive leaves; the second finds both boxes written
-        __threadfence();
-        const unsigned lr = nodes[p].left_right, l = lr & 0xffffu, r = lr >> 16;
-        float mn[3], mx[3];
-        for (int q = 0; q < 3; ++q) {
-            mn[q] = fminf(__hip_atomic_load(&nodes[l].min[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(&nodes[r].min[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            mx[q] = fmaxf(__hip_atomic_load(&nodes[l].max[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(&nodes[r].max[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        }
-        for (int q = 0; q < 3; ++q) {
-            __hip_atomic_store(&nodes[p].min[q], mn[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&nodes[p].max[q], mx[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (p == 0u) return;
-        k = p;
-    }
-}
+// ---- the private top level as an LBVH (VD_OPT_TRACE_TIGHT_TLAS = 2): the builder of vd_tlas_build_lbvh* (tlas.hip:
+// vd_tlas_lbvh_from_boxes) over the tight boxes, on all CUs in ~0.1 ms, so it can follow moving instances every frame
+// (vd_trace_accel_update_dev); the agglomerative builder (= 1) makes the better tree and takes the reference's
+// sequential chain to do it.  Node 0 is the true root there and node 2n is nobody's child: the walk sees 2n nodes.
 
-int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out,
-                 uint32_t* d_any = nullptr) {
+// WIDE: the scene's top level is VdTlasNodeWide (vd_trace_wide*).  Same call, except that the records are one table of
+// n_tlas_nodes x 64 B that needs no fill (records_wide_kernel), in an arena of its own (ctx->trace_wide) so that the narrow
+// calls' scratch does not grow with a wide scene's node count, and the wide instantiations of the kernels walk.
+template <bool WIDE = false>
+int launch_trace(VdCtx* ctx, const std::conditional_t<WIDE, VdTraceSceneWide, VdTraceScene>* sc, const float* d_tris, const VdRay* d_rays,
+                 uint32_t n_rays, VdHit* d_out, uint32_t* d_any = nullptr) {
+    void** arena = WIDE ? &ctx->trace_wide : &ctx->scratch;
+    size_t* arena_bytes = WIDE ? &ctx->trace_wide_bytes : &ctx->scratch_bytes;
     // idle waves keep drawing from the ray counter after the last ray: leave it room below 2^32
     if (n_rays > 0xf0000000u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: more than 0xf0000000 rays in one call");
     // scratch: [256 B flags and counters][TLAS child pairs, 64 B x 65 536][entry records, 64 B x 65 536][mesh records][de-indexed triangles][fan-out]
     // (pairs and entry records for all 65 536 indices a 16-bit child field can name: a stray index reads a poisoned slot, not beyond)
-    const size_t pair_bytes = (size_t)64 * kTlasSlots, irec_bytes = (size_t)64 * kTlasSlots, owner_bytes = (size_t)4 * kTlasSlots;
+    const size_t pair_bytes = (size_t)64 * (WIDE ? sc->n_tlas_nodes : kTlasSlots), irec_bytes = WIDE ? 0 : (size_t)64 * kTlasSlots,
+                 owner_bytes = WIDE ? 0 : (size_t)4 * kTlasSlots;
     const size_t mrec_bytes = (size_t)128 * sc->n_meshes;
     const size_t tris_at = 256 + pair_bytes + irec_bytes + owner_bytes + ((mrec_bytes + 255) & ~(size_t)255);
     // A call that was not given prepared leaves de-indexes them itself when that is cheap next to the walk (one pass over the
@@ -1135,8 +1092,9 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
     if (ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1) >= 0) fan_cap = (unsigned)std::min<long long>(fan_cap, ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1));      // tests: a list that fills up
     const size_t best_bytes = ((size_t)n_rays * 8u + 255) & ~(size_t)255;
     const size_t fan_bytes = phases > 1u ? 256 + best_bytes + (size_t)fan_cap * sizeof(FanJob) : 0;
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, fan_at + fan_bytes);
+    int rc = vd_ensure(ctx, arena, arena_bytes, fan_at + fan_bytes);
     if (rc) return rc;
+    char* const scratch = reinterpret_cast<char*>(*arena);
     // one bit per ray: "ran out of its 128 stack entries" (second pass below).  All zero between calls: zeroed when (re)allocated
     // and again after a call that set any, so a call that overflows nowhere pays nothing for it.
     const unsigned ovf_words = (n_rays + 31u) / 32u;
@@ -1149,45 +1107,53 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
     }
     unsigned* d_ovf = reinterpret_cast<unsigned*>(ctx->trace_ovf);
     vd_time_begin(ctx);
-    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
+    unsigned* d_flag = reinterpret_cast<unsigned*>(scratch);
 #ifdef VD_TUNING
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 256, ctx->stream));
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag + 16, 0xff, 8, ctx->stream));
 #else
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 64, ctx->stream));
 #endif
-    unsigned* fan_ctl = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctx->scratch) + fan_at);      // [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
+    unsigned* fan_ctl = reinterpret_cast<unsigned*>(scratch + fan_at);      // [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
     unsigned long long* fan_best = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(fan_ctl) + 256);
     FanJob* fan_jobs = reinterpret_cast<FanJob*>(reinterpret_cast<char*>(fan_best) + best_bytes);
     if (phases > 1u) {
         VD_HIP_CHECK(ctx, hipMemsetAsync(fan_ctl, 0, 256, ctx->stream));
         if (!d_any) VD_HIP_CHECK(ctx, hipMemsetAsync(fan_best, 0xff, best_bytes, ctx->stream));
     }
-    float4* d_pair = reinterpret_cast<float4*>(reinterpret_cast<char*>(ctx->scratch) + 256);
+    float4* d_pair = reinterpret_cast<float4*>(scratch + 256);
     float4* d_rec = reinterpret_cast<float4*>(reinterpret_cast<char*>(d_pair) + pair_bytes);
     unsigned* d_owner = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_rec) + irec_bytes);
     float4* d_mrec = reinterpret_cast<float4*>(reinterpret_cast<char*>(d_owner) + owner_bytes);
+    if (WIDE) d_rec = d_pair;      // one table: a node is a leaf or an interior node
     const unsigned yield = (unsigned)std::max<long long>(1, ctx->option(VD_OPT_TRACE_YIELD, kYieldDefault));
+    if constexpr (WIDE) {
+        const unsigned items = std::max(sc->n_tlas_nodes, sc->n_meshes);
+        hipLaunchKernelGGL(records_wide_kernel, dim3(vd_blocks(ctx, items, 256u, 64u)), dim3(256), 0, ctx->stream, sc->tlas_nodes, sc->n_tlas_nodes,
+                           sc->instances, sc->n_instances, sc->meshes, sc->n_meshes, sc->bvh_nodes, sc->n_bvh_nodes, d_pair, d_mrec);
+    } else {
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_pair, 0xff, pair_bytes + irec_bytes + owner_bytes, ctx->stream));      // no pair slot carries a tag or has an owner yet, every entry record says "bad"
     const unsigned n_rec = std::min(sc->n_tlas_nodes, kTlasSlots);      // nodes past 65 535 cannot be named by a 16-bit child field
     hipLaunchKernelGGL(pair_owner_kernel, dim3((n_rec + 255u) / 256u), dim3(256), 0, ctx->stream, sc->tlas_nodes, n_rec, d_owner);
     hipLaunchKernelGGL(records_kernel, dim3((std::max(n_rec, sc->n_meshes) + 255u) / 256u), dim3(256), 0, ctx->stream, sc->tlas_nodes,
                        n_rec, sc->instances, sc->n_instances, sc->meshes, sc->n_meshes, sc->bvh_nodes, sc->n_bvh_nodes, d_rec, d_pair, d_mrec, d_owner);
+    }
     const unsigned* gate = nullptr;
     if (auto_prep) {
-        float* t = reinterpret_cast<float*>(reinterpret_cast<char*>(ctx->scratch) + tris_at);
+        float* t = reinterpret_cast<float*>(scratch + tris_at);
         hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, sc->n_meshes), dim3(256), 0, ctx->stream, sc->meshes, sc->vertices, sc->indices, sc->n_indices,
                            sc->n_vertices, t, d_flag + 2);
         d_tris = t; gate = d_flag + 2;        // non-zero: some mesh's index range cannot be de-indexed - the indexed kernel takes the call
     }
-    Scene s{sc->tlas_nodes, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, d_tris, d_rec, d_pair, d_mrec, yield, d_ovf};
+    const VdTlasNode* tlas_arg = reinterpret_cast<const VdTlasNode*>(sc->tlas_nodes);      // WIDE: the kernels cast it back (tl_instance)
+    Scene s{tlas_arg, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, d_tris, d_rec, d_pair, d_mrec, yield, d_ovf};
     // two run-time booleans -> the template arguments of a launch: f(std::integral_constant<bool, a>{}, std::integral_constant<bool, b>{})
     auto with_bools = [](bool x, bool y, auto&& f) {
         using T = std::integral_constant<bool, true>; using F = std::integral_constant<bool, false>;
         if (x) { if (y) f(T{}, T{}); else f(T{}, F{}); }
         else { if (y) f(F{}, T{}); else f(F{}, F{}); }
     };
-    const SceneArgs a{sc->tlas_nodes, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, yield, d_rec, d_pair, d_mrec, d_ovf};
+    const SceneArgs a{tlas_arg, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, yield, d_rec, d_pair, d_mrec, d_ovf};
     // fan-out: launch 0 hands out the rays; launch p >= 1 the jobs appended before it started (fan_snapshot_kernel);
     // every launch but the last may append; fan_resolve_kernel writes the records of the rays that were fanned out
     for (unsigned ph = 0; ph < phases; ++ph) {
@@ -1201,6 +1167,13 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
         unsigned* next = ph == 0 ? d_flag + 1 : fan_ctl + ph;
         with_bools(d_any != nullptr, phases > 1u, [&](auto any, auto fanned) {
             constexpr bool A = decltype(any)::value, F = decltype(fanned)::value;
+            if constexpr (WIDE) {
+                if (d_tris) hipLaunchKernelGGL((trace_wide_kernel<A, true, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any, d_flag,
+                                               next, d_tris, gate, fan);
+                if (!d_tris || gate) hipLaunchKernelGGL((trace_wide_kernel<A, false, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any,
+                                                        d_flag, next, d_tris, gate, fan);
+                return;
+            }
             if (d_tris) hipLaunchKernelGGL((trace_single_prep_kernel<A, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any, d_flag,
                                            next, d_tris, gate, fan);
             if (!d_tris || gate) hipLaunchKernelGGL((trace_single_kernel<A, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any,
@@ -1248,8 +1221,10 @@ int launch_trace(VdCtx* ctx, const VdTraceScene* sc, const float* d_tris, const 
             sd.deep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(list) + list_bytes);
             sd.deep_cap = (unsigned)cap;
             with_bools(d_any != nullptr, prep_walked, [&](auto any, auto prep) {
-                hipLaunchKernelGGL((trace_deep_kernel<decltype(any)::value, decltype(prep)::value>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays,
-                                   list, ctl, d_out, d_any, d_flag, ctl + 1);
+                constexpr bool A = decltype(any)::value, P = decltype(prep)::value;
+                if constexpr (WIDE) hipLaunchKernelGGL((trace_deep_wide_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays, list, ctl, d_out,
+                                                       d_any, d_flag, ctl + 1);
+                else hipLaunchKernelGGL((trace_deep_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays, list, ctl, d_out, d_any, d_flag, ctl + 1);
             });
             vd_time_end(ctx);                                                              // vd_last_gpu_ms covers the second pass too
             VD_HIP_CHECK(ctx, hipGetLastError());
@@ -1275,28 +1250,8 @@ int build_tight_tlas(VdCtx* ctx, VdTraceAccel* a) {
     hipLaunchKernelGGL(tight_boxes_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a->scene.instances, n, a->scene.meshes, a->scene.n_meshes,
                        a->scene.bvh_nodes, a->scene.n_bvh_nodes, a->user_tlas, a->user_n_nodes, a->boxes, d_fb);
     if (a->tight_mode == 2u) {
-        const unsigned n_units = (n + kSortUnit - 1u) / kSortUnit;
-        const size_t arr = ((size_t)n * 4 + 255) & ~(size_t)255;
-        char* base = reinterpret_cast<char*>(a->lbvh);
-        unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
-        unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
-        unsigned* parent = reinterpret_cast<unsigned*>(base + 4 * arr);                 // 2n + 2 words
-        unsigned* arrived = parent + 2 * (size_t)n + 2;                                 // 2n + 2 words
-        unsigned* ext = arrived + 2 * (size_t)n + 2;                                    // 8 words
-        unsigned* table = ext + 8;                                                      // 256 * n_units words
-        VD_HIP_CHECK(ctx, hipMemsetAsync(ext, 0xff, 12, st));
-        VD_HIP_CHECK(ctx, hipMemsetAsync(ext + 3, 0, 12, st));
-        hipLaunchKernelGGL(lbvh_extent_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a->boxes, n, ext);
-        hipLaunchKernelGGL(lbvh_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a->boxes, n, ext, k[0], v[0]);
-        const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int x = pass & 1, y = x ^ 1;
-            hipLaunchKernelGGL(rs_count_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], n, 8u * pass, n_units, table);
-            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, 256u * n_units);
-            hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], n, 8u * pass, n_units, table, k[y], v[y]);
-        }
-        hipLaunchKernelGGL(lbvh_tree_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, k[0], v[0], a->boxes, n, a->tight, parent, arrived);
-        hipLaunchKernelGGL(lbvh_fit_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, a->tight, parent, arrived);
+        const int rc = vd_tlas_lbvh_from_boxes(ctx, a->boxes, n, a->tight, a->lbvh);
+        if (rc) return rc;
     } else {
         const int rc = vd_tlas_build_from_boxes(ctx, a->boxes, n, a->tight);
         if (rc) return rc;
@@ -1312,9 +1267,49 @@ int build_tight_tlas(VdCtx* ctx, VdTraceAccel* a) {
     return VD_OK;
 }
 
-bool scene_ok(const VdTraceScene* s) {
+template <typename S> bool scene_ok(const S* s) {
     return s && s->tlas_nodes && s->instances && s->meshes && s->bvh_nodes && s->vertices && s->indices && s->n_meshes &&
            s->n_tlas_nodes && s->n_instances;
+}
+// what every vd_trace_wide* entry point checks before anything is launched
+int wide_scene_check(VdCtx* ctx, const VdTraceSceneWide* s) {
+    if (!scene_ok(s)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: incomplete scene");
+    if (s->n_tlas_nodes > 2u * VD_TLAS_WIDE_MAX_INSTANCES + 1u)
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: more than 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1 top-level nodes");
+    return VD_OK;
+}
+
+// host-pointer form of a trace call: the six buffers and the rays staged in, the records out
+template <bool WIDE>
+int trace_host(VdCtx* ctx, const std::conditional_t<WIDE, VdTraceSceneWide, VdTraceScene>* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
+    using Node = std::conditional_t<WIDE, VdTlasNodeWide, VdTlasNode>;
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    // one staging arena, sub-allocated at 256-B boundaries
+    const size_t sz[8] = {(size_t)scene->n_tlas_nodes * sizeof(Node), (size_t)scene->n_instances * sizeof(VdInstance),
+                          (size_t)scene->n_meshes * sizeof(VdMeshInfo), (size_t)scene->n_bvh_nodes * sizeof(VdBvhNode),
+                          (size_t)scene->n_vertices * 12, (size_t)scene->n_indices * 4, (size_t)n_rays * sizeof(VdRay),
+                          (size_t)n_rays * sizeof(VdHit)};
+    const void* src[7] = {scene->tlas_nodes, scene->instances, scene->meshes, scene->bvh_nodes, scene->vertices, scene->indices, rays};
+    size_t off[8], total = 0;
+    for (int k = 0; k < 8; ++k) { off[k] = total; total += (sz[k] + 255) & ~(size_t)255; }
+    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, total);
+    if (rc) return rc;
+    char* base = reinterpret_cast<char*>(ctx->stage_in);
+    for (int k = 0; k < 7; ++k)
+        if (sz[k]) VD_HIP_CHECK(ctx, hipMemcpyAsync(base + off[k], src[k], sz[k], hipMemcpyHostToDevice, ctx->stream));
+    auto d = *scene;
+    d.tlas_nodes = reinterpret_cast<const Node*>(base + off[0]);
+    d.instances = reinterpret_cast<const VdInstance*>(base + off[1]);
+    d.meshes = reinterpret_cast<const VdMeshInfo*>(base + off[2]);
+    d.bvh_nodes = reinterpret_cast<const VdBvhNode*>(base + off[3]);
+    d.vertices = reinterpret_cast<const float*>(base + off[4]);
+    d.indices = reinterpret_cast<const uint32_t*>(base + off[5]);
+    VdHit* d_out = reinterpret_cast<VdHit*>(base + off[7]);
+    rc = launch_trace<WIDE>(ctx, &d, nullptr, reinterpret_cast<const VdRay*>(base + off[6]), n_rays, d_out);
+    if (rc) return rc;
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, sz[7], hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VD_OK;
 }
 
 }  // namespace
@@ -1390,8 +1385,7 @@ int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel**
     if (tight != 0 && d_scene->n_instances >= 2u && d_scene->n_instances <= (tight == 2 ? VD_TLAS_MAX_INSTANCES - 1u : VD_TLAS_MAX_INSTANCES)) {
         const unsigned n = d_scene->n_instances;
         a->tight_mode = tight == 2 ? 2u : 1u;
-        const size_t arr = ((size_t)n * 4 + 255) & ~(size_t)255;
-        const size_t lbvh_bytes = 4 * arr + 4 * (4 * (size_t)n + 4 + 8 + 256 * (size_t)((n + kSortUnit - 1u) / kSortUnit)) + 256;
+        const size_t lbvh_bytes = vd_lbvh_work_bytes(n);
         bool good = hipMalloc(reinterpret_cast<void**>(&a->boxes), 24 * (size_t)n + 16) == hipSuccess &&       // (not in the context's scratch: the agglomerative builder lays that out for itself)
                     hipMalloc(reinterpret_cast<void**>(&a->tight), sizeof(VdTlasNode) * (2 * (size_t)n + 1)) == hipSuccess &&
                     (a->tight_mode != 2u || hipMalloc(reinterpret_cast<void**>(&a->lbvh), lbvh_bytes) == hipSuccess);
@@ -1550,33 +1544,34 @@ int vd_trace(VdCtx* ctx, const VdTraceScene* scene, const VdRay* rays, uint32_t 
     if (!scene_ok(scene)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: incomplete scene");
     if (n_rays == 0) return VD_OK;
     if (!rays || !out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: null rays/out");
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    // one staging arena, sub-allocated at 256-B boundaries
-    const size_t sz[8] = {(size_t)scene->n_tlas_nodes * sizeof(VdTlasNode), (size_t)scene->n_instances * sizeof(VdInstance),
-                          (size_t)scene->n_meshes * sizeof(VdMeshInfo), (size_t)scene->n_bvh_nodes * sizeof(VdBvhNode),
-                          (size_t)scene->n_vertices * 12, (size_t)scene->n_indices * 4, (size_t)n_rays * sizeof(VdRay),
-                          (size_t)n_rays * sizeof(VdHit)};
-    const void* src[7] = {scene->tlas_nodes, scene->instances, scene->meshes, scene->bvh_nodes, scene->vertices, scene->indices, rays};
-    size_t off[8], total = 0;
-    for (int k = 0; k < 8; ++k) { off[k] = total; total += (sz[k] + 255) & ~(size_t)255; }
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, total);
-    if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->stage_in);
-    for (int k = 0; k < 7; ++k)
-        if (sz[k]) VD_HIP_CHECK(ctx, hipMemcpyAsync(base + off[k], src[k], sz[k], hipMemcpyHostToDevice, ctx->stream));
-    VdTraceScene d = *scene;
-    d.tlas_nodes = reinterpret_cast<const VdTlasNode*>(base + off[0]);
-    d.instances = reinterpret_cast<const VdInstance*>(base + off[1]);
-    d.meshes = reinterpret_cast<const VdMeshInfo*>(base + off[2]);
-    d.bvh_nodes = reinterpret_cast<const VdBvhNode*>(base + off[3]);
-    d.vertices = reinterpret_cast<const float*>(base + off[4]);
-    d.indices = reinterpret_cast<const uint32_t*>(base + off[5]);
-    VdHit* d_out = reinterpret_cast<VdHit*>(base + off[7]);
-    rc = launch_trace(ctx, &d, nullptr, reinterpret_cast<const VdRay*>(base + off[6]), n_rays, d_out);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, sz[7], hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    return trace_host<false>(ctx, scene, rays, n_rays, out);
+}
+
+int vd_trace_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (const int rc = wide_scene_check(ctx, d_scene)) return rc;
+    if (n_rays == 0) return VD_OK;
+    if (!d_rays || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: null rays/out");
+    return launch_trace<true>(ctx, d_scene, nullptr, d_rays, n_rays, d_out);
+}
+
+int vd_trace_any_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (const int rc = wide_scene_check(ctx, d_scene)) return rc;
+    if (n_rays == 0) return VD_OK;
+    if (!d_rays || !d_out_hit) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_any_wide: null rays/out");
+    return launch_trace<true>(ctx, d_scene, nullptr, d_rays, n_rays, nullptr, d_out_hit);
+}
+
+int vd_trace_wide(VdCtx* ctx, const VdTraceSceneWide* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (const int rc = wide_scene_check(ctx, scene)) return rc;
+    if (n_rays == 0) return VD_OK;
+    if (!rays || !out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: null rays/out");
+    return trace_host<true>(ctx, scene, rays, n_rays, out);
 }
 
 int vd_primary_rays(VdCtx* ctx, const VdCameraUniform* camera, uint32_t width, uint32_t height, VdRay* rays) {

@@ -38,6 +38,8 @@ struct VdCtx {
     void* trace_ovf = nullptr;   size_t trace_ovf_bytes = 0;      // traversal: one bit per ray of the call = "its 128-entry stack overflowed"
     bool trace_ovf_dirty = false;                                 // a call left early (error) and may have left bits set
     void* trace_deep = nullptr;  size_t trace_deep_bytes = 0;     // traversal, second pass over those rays: their list + stack entries beyond 128 (allocated when first needed)
+    void* trace_wide = nullptr;  size_t trace_wide_bytes = 0;     // vd_trace_wide*: the per-call records of a wide top level (64 B per node), mesh records, triangles, fan-out
+    void* lbvh_state = nullptr;  size_t lbvh_state_bytes = 0;     // vd_tlas_build_lbvh*: leaf boxes, codes, the sort's tables, parent links, arrival words
     void* refit_state = nullptr; size_t refit_state_bytes = 0;    // TLAS refit: epoch-tagged {parent, sibling} links + arrival words
     unsigned refit_epoch = 0;                                     // tag of the last refit launch (0 = the arena is freshly zeroed)
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
@@ -97,6 +99,10 @@ int vd_ensure(VdCtx* ctx, void** buf, size_t* cur, size_t need);
 int vd_ensure_host(VdCtx* ctx, size_t need);   // ctx->host_stage: grow-only pinned host memory
 // tlas.hip: the agglomerative build of tlas.rs:56-105 over ready leaf boxes (six floats {min xyz, max xyz} per leaf; n <= 32 768)
 int vd_tlas_build_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes);
+// tlas.hip: the LBVH build (vd_tlas_build_lbvh*) over ready leaf boxes, into 2n + 1 narrow nodes, with `work` (vd_lbvh_work_bytes(n)
+// bytes of device memory, 256-byte aligned) as its work memory.  Enqueues only.  n <= 32 768.
+size_t vd_lbvh_work_bytes(uint32_t n);
+int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes, void* work);
 // Look-back scan state for n_tiles tiles: *ticket = 64-bit {epoch | ticket} word, *states = granules.
 // Zeroed once when (re)allocated; the epoch tags make per-launch clearing unnecessary.
 int vd_scan_scratch(VdCtx* ctx, unsigned n_tiles, unsigned long long** ticket, unsigned long long** states, bool start_timer);

@@ -391,6 +391,19 @@ class Context:
         fn = self.lib.vd_tlas_refit_wide_dev if wide else self.lib.vd_tlas_refit_dev
         self._chk(fn(self.h, abi.ptr(d_inst), n, abi.ptr(d_meshes), n_mesh, abi.ptr(d_nodes)))
 
+    def tlas_build_lbvh(self, instances, meshes, wide=False) -> np.ndarray:
+        """vd_tlas_build_lbvh[_wide]: the LBVH top level (2n + 1 nodes, layout in include/voidin_abi.h), host arrays."""
+        instances = np.ascontiguousarray(instances, dtype=abi.INSTANCE)
+        meshes = np.ascontiguousarray(meshes, dtype=abi.MESH_INFO)
+        out = np.zeros(2 * len(instances) + 1, dtype=abi.TLAS_NODE_WIDE if wide else abi.TLAS_NODE)
+        fn = self.lib.vd_tlas_build_lbvh_wide if wide else self.lib.vd_tlas_build_lbvh
+        self._chk(fn(self.h, instances.ctypes.data, len(instances), meshes.ctypes.data, len(meshes), out.ctypes.data))
+        return out
+
+    def tlas_build_lbvh_dev(self, d_inst, n, d_meshes, n_mesh, d_nodes, wide=False):
+        fn = self.lib.vd_tlas_build_lbvh_wide_dev if wide else self.lib.vd_tlas_build_lbvh_dev
+        self._chk(fn(self.h, abi.ptr(d_inst), n, abi.ptr(d_meshes), n_mesh, abi.ptr(d_nodes)))
+
     # -- traversal ----------------------------------------------------------------------------
     def trace(self, scene_arrays, rays) -> np.ndarray:
         """scene_arrays = (tlas_nodes, instances, meshes, bvh_nodes, vertices, indices), host."""
@@ -408,15 +421,29 @@ class Context:
         self._chk(self.lib.vd_trace(self.h, C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data))
         return out
 
+    def trace_wide(self, scene_arrays, rays) -> np.ndarray:
+        """vd_trace_wide: as trace(), with scene_arrays[0] an array of TLAS_NODE_WIDE."""
+        dts = [abi.TLAS_NODE_WIDE, abi.INSTANCE, abi.MESH_INFO, abi.BVH_NODE, np.float32, np.uint32]
+        arrs = [np.ascontiguousarray(a, dtype=d).reshape(-1) for a, d in zip(scene_arrays, dts)]
+        s = abi.TraceSceneWide()
+        for k, name in enumerate(("tlas_nodes", "instances", "meshes", "bvh_nodes", "vertices", "indices")):
+            setattr(s, name, arrs[k].ctypes.data)
+            setattr(s, "n_" + name, len(arrs[k]) // (3 if name == "vertices" else 1))
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        out = np.zeros(len(rays), dtype=abi.HIT)
+        self._chk(self.lib.vd_trace_wide(self.h, C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data))
+        return out
 
     class DeviceScene:
-        """Device-resident copy of a trace scene; keeps the tensors alive next to the VdTraceScene."""
+        """Device-resident copy of a trace scene; keeps the tensors alive next to the VdTraceScene.  A node array of
+        dtype TLAS_NODE_WIDE makes it a VdTraceSceneWide (`wide`): what trace_wide_dev / trace_any_wide_dev take."""
 
         def __init__(self, ctx, scene_arrays):
-            dts = [abi.TLAS_NODE, abi.INSTANCE, abi.MESH_INFO, abi.BVH_NODE, np.float32, np.uint32]
+            self.wide = getattr(scene_arrays[0], "dtype", None) == abi.TLAS_NODE_WIDE
+            dts = [abi.TLAS_NODE_WIDE if self.wide else abi.TLAS_NODE, abi.INSTANCE, abi.MESH_INFO, abi.BVH_NODE, np.float32, np.uint32]
             arrs = [np.ascontiguousarray(a, dtype=d).reshape(-1) for a, d in zip(scene_arrays, dts)]
             self.tensors = [ctx.upload(a) for a in arrs]
-            s = abi.TraceScene()
+            s = abi.TraceSceneWide() if self.wide else abi.TraceScene()
             s.tlas_nodes, s.n_tlas_nodes = self.tensors[0].data_ptr(), len(arrs[0])
             s.instances, s.n_instances = self.tensors[1].data_ptr(), len(arrs[1])
             s.meshes, s.n_meshes = self.tensors[2].data_ptr(), len(arrs[2])
@@ -429,10 +456,25 @@ class Context:
         return Context.DeviceScene(self, scene_arrays)
 
     def trace_dev(self, scene: "Context.DeviceScene", d_rays, n_rays, d_out):
+        if scene.wide:
+            raise TypeError("a scene whose top level is TLAS_NODE_WIDE goes through trace_wide_dev")
         self._chk(self.lib.vd_trace_dev(self.h, C.byref(scene.struct), abi.ptr(d_rays), n_rays, abi.ptr(d_out)))
+
+    def trace_wide_dev(self, scene: "Context.DeviceScene", d_rays, n_rays, d_out):
+        """vd_trace_wide_dev over a DeviceScene made from TLAS_NODE_WIDE nodes."""
+        if not scene.wide:
+            raise TypeError("trace_wide_dev needs a scene whose top level is TLAS_NODE_WIDE")
+        self._chk(self.lib.vd_trace_wide_dev(self.h, C.byref(scene.struct), abi.ptr(d_rays), n_rays, abi.ptr(d_out)))
+
+    def trace_any_wide_dev(self, scene: "Context.DeviceScene", d_rays, n_rays, d_out_hit):
+        if not scene.wide:
+            raise TypeError("trace_any_wide_dev needs a scene whose top level is TLAS_NODE_WIDE")
+        self._chk(self.lib.vd_trace_any_wide_dev(self.h, C.byref(scene.struct), abi.ptr(d_rays), n_rays, abi.ptr(d_out_hit)))
 
     def trace_any_dev(self, scene: "Context.DeviceScene", d_rays, n_rays, d_out_hit):
         """Occlusion query: d_out_hit[i] (u32) = 1 iff ray i hits anything (raytraced_shadows.wgsl:97-102)."""
+        if scene.wide:
+            raise TypeError("a scene whose top level is TLAS_NODE_WIDE goes through trace_any_wide_dev")
         self._chk(self.lib.vd_trace_any_dev(self.h, C.byref(scene.struct), abi.ptr(d_rays), n_rays, abi.ptr(d_out_hit)))
 
     class TraceAccel:
