@@ -26,6 +26,32 @@ int vd_ensure(VdCtx* ctx, void** buf, size_t* cur, size_t need) {
     return VD_OK;
 }
 
+// The staged round trip of a host-pointer form (vd_common.hpp): every host form drains the stream before it stages, so one
+// arena serves them all, whatever layout the last one left in it.  Blobs of no bytes are placed and not copied.  A blob
+// may be both uploaded here and fetched later: the node array of vd_tlas_refit is.
+int vd_stage_blobs(VdCtx* ctx, VdBlob* blobs, unsigned n_blobs) {
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    size_t total = 0;
+    for (unsigned b = 0; b < n_blobs; ++b) {           // (dev holds the blob's offset until the arena exists)
+        total = (total + blobs[b].align - 1) & ~(blobs[b].align - 1);
+        blobs[b].dev = reinterpret_cast<void*>(total);
+        total += blobs[b].bytes;
+    }
+    const int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, total);
+    if (rc) return rc;
+    for (unsigned b = 0; b < n_blobs; ++b) {
+        blobs[b].dev = reinterpret_cast<char*>(ctx->stage_in) + reinterpret_cast<size_t>(blobs[b].dev);
+        if (blobs[b].host && blobs[b].bytes) VD_HIP_CHECK(ctx, hipMemcpyAsync(blobs[b].dev, blobs[b].host, blobs[b].bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return VD_OK;
+}
+
+int vd_fetch_blob(VdCtx* ctx, void* host, const VdBlob* blob) {
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(host, blob->dev, blob->bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VD_OK;
+}
+
 // grow-only pinned host staging
 int vd_ensure_host(VdCtx* ctx, size_t need) {
     if (need <= ctx->host_stage_bytes && ctx->host_stage) return VD_OK;

@@ -1463,113 +1463,127 @@ int tlas_lbvh_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMes
     return rc;
 }
 
-template <typename Node>
-int tlas_build_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                    Node* d_nodes) {
+// What one exact build will do, decided before anything is launched: which builder, its tuning, and where the parts of
+// ctx->scratch lie - 6 float slot arrays + slot node ids (capacity n), the several-workgroup exchange words, and - only when
+// the indexed build runs - the entries, the slot -> entry map, two key / value pairs of the sort and the control words.
+struct TlasBuildPlan {
+    bool indexed; unsigned phase2, refresh, groups, spin_limit, E;
+    size_t cap, off_sh, off_ent, off_map, off_sort, sort_stride, off_ctl, need, chain_lds;
+    int chain_in_lds;
+};
+TlasBuildPlan tlas_build_plan(const VdCtx* ctx, uint32_t n) {
+    TlasBuildPlan p;
     // The indexed build (one workgroup, exact pruning) from a few thousand instances up to what its corner table fits in
     // LDS; above that the scans are spread over several workgroups.  Per-context options (vd_ctx_set_option):
     // VD_OPT_TLAS_INDEX = 0 switches it off (A/B), VD_OPT_TLAS_INDEX_MIN / _PHASE2 / _REFRESH tune it.
     const int env_index = (int)ctx->option(VD_OPT_TLAS_INDEX, 1);
     const unsigned ix_min = (unsigned)ctx->option(VD_OPT_TLAS_INDEX_MIN, 6800);    // below: the chain is faster (from LDS up to 5600 instances; A/B in profiles/NOTEBOOK_r01_r04.md, the script is in the history)
-    unsigned phase2 = (unsigned)ctx->option(VD_OPT_TLAS_PHASE2, 4096);     // 2048 until the final scans moved into LDS (round 4): 184.6 -> 182.7 ms at 32 768, 41.1 -> 39.2 at 8192
-    const unsigned refresh = (unsigned)ctx->option(VD_OPT_TLAS_REFRESH, 512);      // re-swept in round 4: 256: 183.4 ms at 32 768, 512: 182.4, 1024: 183.1, 2048: 185.5
-    if (phase2 < 64u) phase2 = 64u;
-    const bool indexed = env_index != 0 && n >= ix_min && n > phase2 && n <= kIxMaxInstances;
-    // scratch: 6 float slot arrays + slot node ids (capacity n), the several-workgroup exchange words, and - only when the
-    // indexed build runs - the entries, the slot -> entry map, two key / value pairs of the sort and the control words
-    const size_t cap = ((size_t)n + 7) & ~(size_t)3;   // multiple of 4 (+ slack): slot arrays are read 16 B at a time
-    const size_t off_sh = (cap * 7 * 4 + 255) & ~(size_t)255;
-    const unsigned E = (n + kIxBlock - 1u) / kIxBlock * kIxBlock;
-    const size_t off_ent = (off_sh + sizeof(MwShared) + 255) & ~(size_t)255;
-    const size_t off_map = off_ent + (size_t)E * sizeof(IxEntry);
-    const size_t off_sort = off_map + (((size_t)n * 4 + 255) & ~(size_t)255);
-    const size_t sort_stride = ((size_t)n * 4 + 255) & ~(size_t)255;
-    const size_t off_ctl = off_sort + 4 * sort_stride;
-    const size_t need = indexed ? off_ctl + 256 : off_ent;
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, need);
-    if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->scratch);
-    float* sb = reinterpret_cast<float*>(base);
-    unsigned* slot_node = reinterpret_cast<unsigned*>(sb + 6 * cap);
-    MwShared* sh = reinterpret_cast<MwShared*>(base + off_sh);
+    p.phase2 = std::max(64u, (unsigned)ctx->option(VD_OPT_TLAS_PHASE2, 4096));     // 2048 until the final scans moved into LDS (round 4): 184.6 -> 182.7 ms at 32 768, 41.1 -> 39.2 at 8192
+    p.refresh = (unsigned)ctx->option(VD_OPT_TLAS_REFRESH, 512);      // re-swept in round 4: 256: 183.4 ms at 32 768, 512: 182.4, 1024: 183.1, 2048: 185.5
+    p.indexed = env_index != 0 && n >= ix_min && n > p.phase2 && n <= kIxMaxInstances;
+    p.cap = ((size_t)n + 7) & ~(size_t)3;   // multiple of 4 (+ slack): slot arrays are read 16 B at a time
+    p.off_sh = (p.cap * 7 * 4 + 255) & ~(size_t)255;
+    p.E = (n + kIxBlock - 1u) / kIxBlock * kIxBlock;
+    p.off_ent = (p.off_sh + sizeof(MwShared) + 255) & ~(size_t)255;
+    p.off_map = p.off_ent + (size_t)p.E * sizeof(IxEntry);
+    p.sort_stride = ((size_t)n * 4 + 255) & ~(size_t)255;
+    p.off_sort = p.off_map + p.sort_stride;
+    p.off_ctl = p.off_sort + 4 * p.sort_stride;
+    p.need = p.indexed ? p.off_ctl + 256 : p.off_ent;
     // several workgroups from a few thousand instances on (below, the exchange costs more than the shorter scans save);
     // the slot field of the exchanged key holds 20 bits.  VD_OPT_TLAS_GROUPS = 1 forces the single-workgroup kernel.
     const int env_groups = (int)ctx->option(VD_OPT_TLAS_GROUPS, 0);
-    const unsigned spin_limit = (unsigned)ctx->option(VD_OPT_TLAS_SPIN_LIMIT, kSpinLimit);   // tests: 0 forces the fallback
-    unsigned groups = env_groups > 0 ? (unsigned)env_groups : (n >= 12288u ? 16u : 1u);
-    if (groups > kMwMaxGroups) groups = kMwMaxGroups;
-    if (groups > (unsigned)ctx->num_cus) groups = (unsigned)ctx->num_cus;
-    if (n >= (1u << 20)) groups = 1u;
+    p.spin_limit = (unsigned)ctx->option(VD_OPT_TLAS_SPIN_LIMIT, kSpinLimit);   // tests: 0 forces the fallback
+    p.groups = env_groups > 0 ? (unsigned)env_groups : (n >= 12288u ? 16u : 1u);
+    p.groups = std::min(std::min(p.groups, kMwMaxGroups), (unsigned)ctx->num_cus);
+    if (n >= (1u << 20)) p.groups = 1u;
     // the single-workgroup chain over LDS-resident slot arrays (28 B per slot) for small scenes
-    const int chain_in_lds = n <= kChainLdsMax && ctx->option(VD_OPT_TLAS_CHAIN_LDS, 1) != 0 ? 1 : 0;
-    const size_t chain_lds = chain_in_lds ? cap * 28 : 0;
-    if (chain_in_lds) {
-        constexpr int which = std::is_same<Node, VdTlasNode>::value ? 0 : 1;
-        if (!ctx->tlas_chain_lds_opt_in[which]) {
-            const int max_lds = (int)((((size_t)kChainLdsMax + 7) & ~(size_t)3) * 28);
-            VD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlas_build_kernel<Node>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            ctx->tlas_chain_lds_opt_in[which] = true;
-        }
+    p.chain_in_lds = n <= kChainLdsMax && ctx->option(VD_OPT_TLAS_CHAIN_LDS, 1) != 0 ? 1 : 0;
+    p.chain_lds = p.chain_in_lds ? p.cap * 28 : 0;
+    return p;
+}
+
+// The indexed build's two launches (sort the entries, build).  *fallback: the word that tells the plain chain behind them to
+// run after all.  Decided on the device: leaf coordinates the fast arithmetic cannot order (NaN, inf, |x| >= 1e18), or boxes
+// that defeat the pruning (all union areas tie).  The indexed kernel then returned early and left the slot arrays as the
+// leaves kernel wrote them; the plain chain runs instead, with ITS redo behind it.
+template <typename Node>
+int launch_indexed_build(VdCtx* ctx, const TlasBuildPlan& p, uint32_t n, Node* d_nodes, char* base, const unsigned** fallback) {
+    float* sb = reinterpret_cast<float*>(base);
+    unsigned* slot_node = reinterpret_cast<unsigned*>(sb + 6 * p.cap);
+    const unsigned cap = (unsigned)p.cap;
+    IxEntry* entries = reinterpret_cast<IxEntry*>(base + p.off_ent);
+    unsigned* slot_ent = reinterpret_cast<unsigned*>(base + p.off_map);
+    unsigned* keys[4];
+    for (int k = 0; k < 4; ++k) keys[k] = reinterpret_cast<unsigned*>(base + p.off_sort + k * p.sort_stride);
+    IxCtl* ctl = reinterpret_cast<IxCtl*>(base + p.off_ctl);
+    const unsigned n_slices = p.E / kIxSlice, n_super = (n_slices + kIxSuper - 1u) / kIxSuper;
+    const int chain_in_lds_ix = ctx->option(VD_OPT_TLAS_CHAIN_LDS, 1) != 0 && (size_t)p.phase2 * 28 <= 120000 ? 1 : 0;
+    hipLaunchKernelGGL(tlas_index_kernel, dim3(1), dim3(kSortThreads), 0, ctx->stream, sb, cap, n, p.E, keys[0], keys[1], keys[2], keys[3],
+                       entries, slot_ent, ctl);
+    constexpr unsigned waves = 2 * kIxGroup;          // kIxGroup waves answer the chain's question, as many the speculative one
+    // (+ room for the slot arrays of the plain scans the build ends with: they take the corner tables' place)
+    const size_t lds_chain = chain_in_lds_ix ? ((sizeof(IxShared) + 15) & ~(size_t)15) + (size_t)((p.phase2 + 8u + 3u) & ~3u) * 28 : 0;
+    const size_t lds = std::max(ix_lds_bytes(n_slices, n_super, kIxGroup, waves), lds_chain);
+    constexpr int which = std::is_same<Node, VdTlasNode>::value ? 0 : 1;
+    if (!ctx->tlas_ix_lds_opt_in[which]) {            // per context (= per device): up to 160 KB of dynamic LDS
+        constexpr unsigned max_slices = kIxMaxInstances / kIxSlice;
+        VD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlas_build_indexed_kernel<Node, kIxGroup>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)ix_lds_bytes(max_slices, max_slices / kIxSuper, kIxGroup, waves)));
+        ctx->tlas_ix_lds_opt_in[which] = true;
+    }
+    hipLaunchKernelGGL((tlas_build_indexed_kernel<Node, kIxGroup>), dim3(1), dim3(64 * waves), lds, ctx->stream, d_nodes, n, entries, slot_ent, p.E,
+                       sb, slot_node, cap, ctl, p.phase2, p.refresh, ctx->option(VD_OPT_TLAS_PROFILE, 0) ? 1 : 0, chain_in_lds_ix);
+    *fallback = (const unsigned*)&ctl->fallback;
+    return VD_OK;
+}
+
+template <typename Node>
+int tlas_build_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
+                    Node* d_nodes) {
+    const TlasBuildPlan p = tlas_build_plan(ctx, n);
+    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, p.need);
+    if (rc) return rc;
+    char* base = reinterpret_cast<char*>(ctx->scratch);
+    float* sb = reinterpret_cast<float*>(base);
+    unsigned* slot_node = reinterpret_cast<unsigned*>(sb + 6 * p.cap);
+    MwShared* sh = reinterpret_cast<MwShared*>(base + p.off_sh);
+    const unsigned cap = (unsigned)p.cap;
+    constexpr int which = std::is_same<Node, VdTlasNode>::value ? 0 : 1;
+    if (p.chain_in_lds && !ctx->tlas_chain_lds_opt_in[which]) {
+        const int max_lds = (int)((((size_t)kChainLdsMax + 7) & ~(size_t)3) * 28);
+        VD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlas_build_kernel<Node>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        ctx->tlas_chain_lds_opt_in[which] = true;
     }
     // (fewer waves for small scenes - 256 lanes up to 1024 instances, 512 up to 2048 - were measured: no change; a scan is
     //  ~1 us of dependent instructions whatever the size: target, loads, arithmetic, two reductions around one barrier)
     auto launch_chain = [&](const unsigned* only_if) {
-        hipLaunchKernelGGL((tlas_build_kernel<Node>), dim3(1), dim3(kBuildThreads), chain_lds, ctx->stream, d_nodes, n, sb, slot_node, (unsigned)cap, only_if, chain_in_lds);
+        hipLaunchKernelGGL((tlas_build_kernel<Node>), dim3(1), dim3(kBuildThreads), p.chain_lds, ctx->stream, d_nodes, n, sb, slot_node, cap, only_if, p.chain_in_lds);
+    };
+    auto launch_leaves = [&](const unsigned* only_if) {
+        hipLaunchKernelGGL((tlas_leaves_kernel<Node>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_inst, n, d_meshes,
+                           n_mesh, d_nodes, sb, slot_node, cap, 0, only_if);
+    };
+    // The plain chain - when only_if is null or points at a non-zero word: on 16 workgroups where that pays.  If those did not
+    // hear from each other in time (not co-resident: spin limit) they set sh->fail and leave; the two launches behind them
+    // then redo the build on one workgroup, and return at once otherwise - decided on the device, so the call stays
+    // asynchronous.  Every node a build writes is written again by the redo.
+    auto launch_plain = [&](const unsigned* only_if) -> int {
+        if (p.groups <= 1u) { launch_chain(only_if); return VD_OK; }
+        VD_HIP_CHECK(ctx, hipMemsetAsync(sh, 0, sizeof(MwShared), ctx->stream));
+        hipLaunchKernelGGL((tlas_build_mw_kernel<Node>), dim3(p.groups * 8u), dim3(kMwThreads), 0, ctx->stream, d_nodes, n, sb, slot_node,
+                           cap, sh, p.spin_limit, only_if);
+        launch_leaves((const unsigned*)&sh->fail);
+        launch_chain((const unsigned*)&sh->fail);
+        return VD_OK;
     };
     vd_time_begin(ctx);
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_nodes, 0, sizeof(Node) * (2 * (size_t)n + 1), ctx->stream));   // TlasNode::default()
-    hipLaunchKernelGGL((tlas_leaves_kernel<Node>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_inst, n, d_meshes,
-                       n_mesh, d_nodes, sb, slot_node, (unsigned)cap, 0, (const unsigned*)nullptr);
-    if (indexed) {
-        IxEntry* entries = reinterpret_cast<IxEntry*>(base + off_ent);
-        unsigned* slot_ent = reinterpret_cast<unsigned*>(base + off_map);
-        unsigned* keys[4];
-        for (int k = 0; k < 4; ++k) keys[k] = reinterpret_cast<unsigned*>(base + off_sort + k * sort_stride);
-        IxCtl* ctl = reinterpret_cast<IxCtl*>(base + off_ctl);
-        const unsigned n_slices = E / kIxSlice, n_super = (n_slices + kIxSuper - 1u) / kIxSuper;
-        const int chain_in_lds_ix = ctx->option(VD_OPT_TLAS_CHAIN_LDS, 1) != 0 && (size_t)phase2 * 28 <= 120000 ? 1 : 0;
-        hipLaunchKernelGGL(tlas_index_kernel, dim3(1), dim3(kSortThreads), 0, ctx->stream, sb, (unsigned)cap, n, E, keys[0], keys[1], keys[2], keys[3],
-                           entries, slot_ent, ctl);
-        constexpr unsigned waves = 2 * kIxGroup;          // kIxGroup waves answer the chain's question, as many the speculative one
-        // (+ room for the slot arrays of the plain scans the build ends with: they take the corner tables' place)
-        const size_t lds_chain = chain_in_lds_ix ? ((sizeof(IxShared) + 15) & ~(size_t)15) + (size_t)((phase2 + 8u + 3u) & ~3u) * 28 : 0;
-        const size_t lds = std::max(ix_lds_bytes(n_slices, n_super, kIxGroup, waves), lds_chain);
-        constexpr int which = std::is_same<Node, VdTlasNode>::value ? 0 : 1;
-        if (!ctx->tlas_ix_lds_opt_in[which]) {            // per context (= per device): up to 160 KB of dynamic LDS
-            constexpr unsigned max_slices = kIxMaxInstances / kIxSlice;
-            VD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tlas_build_indexed_kernel<Node, kIxGroup>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)ix_lds_bytes(max_slices, max_slices / kIxSuper, kIxGroup, waves)));
-            ctx->tlas_ix_lds_opt_in[which] = true;
-        }
-        hipLaunchKernelGGL((tlas_build_indexed_kernel<Node, kIxGroup>), dim3(1), dim3(64 * waves), lds, ctx->stream, d_nodes, n, entries, slot_ent, E,
-                           sb, slot_node, (unsigned)cap, ctl, phase2, refresh, ctx->option(VD_OPT_TLAS_PROFILE, 0) ? 1 : 0, chain_in_lds_ix);
-        // Decided on the device: leaf coordinates the fast arithmetic cannot order (NaN, inf, |x| >= 1e18), or boxes that
-        // defeat the pruning (all union areas tie).  The indexed kernel then returned early and left the slot arrays as the
-        // leaves kernel wrote them; the plain chain runs instead - on 16 workgroups where that pays, with ITS redo behind it.
-        if (groups <= 1u) {
-            launch_chain((const unsigned*)&ctl->fallback);
-        } else {
-            VD_HIP_CHECK(ctx, hipMemsetAsync(sh, 0, sizeof(MwShared), ctx->stream));
-            hipLaunchKernelGGL((tlas_build_mw_kernel<Node>), dim3(groups * 8u), dim3(kMwThreads), 0, ctx->stream, d_nodes, n, sb, slot_node,
-                               (unsigned)cap, sh, spin_limit, (const unsigned*)&ctl->fallback);
-            hipLaunchKernelGGL((tlas_leaves_kernel<Node>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_inst, n, d_meshes,
-                               n_mesh, d_nodes, sb, slot_node, (unsigned)cap, 0, (const unsigned*)&sh->fail);
-            launch_chain((const unsigned*)&sh->fail);
-        }
-    } else if (groups <= 1u) {
-        launch_chain((const unsigned*)nullptr);
-    } else {
-        VD_HIP_CHECK(ctx, hipMemsetAsync(sh, 0, sizeof(MwShared), ctx->stream));
-        hipLaunchKernelGGL((tlas_build_mw_kernel<Node>), dim3(groups * 8u), dim3(kMwThreads), 0, ctx->stream, d_nodes, n, sb, slot_node,
-                           (unsigned)cap, sh, spin_limit, (const unsigned*)nullptr);
-        // If the workgroups did not hear from each other in time (not co-resident: spin limit) they set sh->fail and
-        // leave; the two launches below then redo the build on one workgroup, and return at once otherwise - decided
-        // on the device, so the call stays asynchronous.  Every node a build writes is written again by the redo.
-        hipLaunchKernelGGL((tlas_leaves_kernel<Node>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_inst, n, d_meshes,
-                           n_mesh, d_nodes, sb, slot_node, (unsigned)cap, 0, (const unsigned*)&sh->fail);
-        launch_chain((const unsigned*)&sh->fail);
-    }
+    launch_leaves(nullptr);
+    const unsigned* only_if = nullptr;      // the plain chain runs unconditionally - or when the indexed build says so
+    if (p.indexed && (rc = launch_indexed_build<Node>(ctx, p, n, d_nodes, base, &only_if))) return rc;
+    if ((rc = launch_plain(only_if))) return rc;
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
@@ -1614,27 +1628,28 @@ int check_args(VdCtx* ctx, const void* inst, uint32_t n, const void* meshes, uin
     return VD_OK;
 }
 
-// host-pointer wrapper: stage instances + meshes in, nodes out
-template <typename Node, typename Fn>
-int tlas_host(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, Node* nodes,
-              bool upload_nodes, Fn fn) {
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t nb = sizeof(Node) * (2 * (size_t)n + 1);
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)n * sizeof(VdInstance));
+// Every vd_tlas_* entry point: one of the three builders (exact agglomerative build, refit, LBVH) over narrow or wide nodes,
+// through device pointers or host pointers.  A _dev form forgets what the trace fan-out found over the top level at this
+// address (vd_trace*: what the last walk over it found no longer holds); a host form has no device top level to forget - its
+// nodes live in the staging arena for the length of the call.  HOST: instances, meshes and - for a refit - the nodes staged in,
+// the nodes out.
+enum TlasOp { kExact, kRefit, kLbvh };
+template <typename Node, TlasOp OP, bool HOST>
+int tlas_entry(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, Node* nodes) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, std::is_same<Node, VdTlasNodeWide>::value, OP == kLbvh);
     if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, (size_t)n_mesh * sizeof(VdMeshInfo) + 16);
-    if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, nb);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->stage_in, inst, (size_t)n * sizeof(VdInstance), hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->stage_aux, meshes, (size_t)n_mesh * sizeof(VdMeshInfo), hipMemcpyHostToDevice, ctx->stream));
-    if (upload_nodes) VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->stage_out, nodes, nb, hipMemcpyHostToDevice, ctx->stream));
-    rc = fn(reinterpret_cast<const VdInstance*>(ctx->stage_in), reinterpret_cast<const VdMeshInfo*>(ctx->stage_aux),
-            reinterpret_cast<Node*>(ctx->stage_out));
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(nodes, ctx->stage_out, nb, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    constexpr auto run = OP == kExact ? tlas_build_impl<Node> : OP == kRefit ? tlas_refit_impl<Node> : tlas_lbvh_impl<Node>;
+    if constexpr (!HOST) {
+        ctx->fan_forget(nodes);
+        return run(ctx, inst, n, meshes, n_mesh, nodes);
+    } else {
+        VdBlob b[3] = {{inst, (size_t)n * sizeof(VdInstance), 256, nullptr}, {meshes, (size_t)n_mesh * sizeof(VdMeshInfo), 256, nullptr},
+                       {OP == kRefit ? nodes : nullptr, sizeof(Node) * (2 * (size_t)n + 1), 256, nullptr}};
+        if ((rc = vd_stage_blobs(ctx, b, 3))) return rc;
+        rc = run(ctx, static_cast<const VdInstance*>(b[0].dev), n, static_cast<const VdMeshInfo*>(b[1].dev), n_mesh, static_cast<Node*>(b[2].dev));
+        return rc ? rc : vd_fetch_blob(ctx, nodes, &b[2]);
+    }
 }
 
 }  // namespace
@@ -1655,91 +1670,38 @@ int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlas
 
 extern "C" {
 
-int vd_tlas_build_lbvh_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                           VdTlasNode* d_nodes) {
-    VdDeviceGuard vd_guard_(ctx);
-    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, false, true);
-    if (!rc) ctx->fan_forget(d_nodes);
-    return rc ? rc : tlas_lbvh_impl<VdTlasNode>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+int vd_tlas_build_lbvh_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNode* d_nodes) {
+    return tlas_entry<VdTlasNode, kLbvh, false>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
 }
-int vd_tlas_build_lbvh_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                                VdTlasNodeWide* d_nodes) {
-    VdDeviceGuard vd_guard_(ctx);
-    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, true, true);
-    if (!rc) ctx->fan_forget(d_nodes);
-    return rc ? rc : tlas_lbvh_impl<VdTlasNodeWide>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+int vd_tlas_build_lbvh_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNodeWide* d_nodes) {
+    return tlas_entry<VdTlasNodeWide, kLbvh, false>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
 }
 int vd_tlas_build_lbvh(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNode* nodes) {
-    VdDeviceGuard vd_guard_(ctx);
-    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, false, true);
-    if (rc) return rc;
-    return tlas_host<VdTlasNode>(ctx, inst, n, meshes, n_mesh, nodes, false, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNode* dn) {
-        return tlas_lbvh_impl<VdTlasNode>(ctx, di, n, dm, n_mesh, dn);
-    });
+    return tlas_entry<VdTlasNode, kLbvh, true>(ctx, inst, n, meshes, n_mesh, nodes);
 }
-int vd_tlas_build_lbvh_wide(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh,
-                            VdTlasNodeWide* nodes) {
-    VdDeviceGuard vd_guard_(ctx);
-    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, true, true);
-    if (rc) return rc;
-    return tlas_host<VdTlasNodeWide>(ctx, inst, n, meshes, n_mesh, nodes, false, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNodeWide* dn) {
-        return tlas_lbvh_impl<VdTlasNodeWide>(ctx, di, n, dm, n_mesh, dn);
-    });
+int vd_tlas_build_lbvh_wide(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNodeWide* nodes) {
+    return tlas_entry<VdTlasNodeWide, kLbvh, true>(ctx, inst, n, meshes, n_mesh, nodes);
 }
-
-int vd_tlas_build_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                      VdTlasNode* d_nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, false);
-    if (!rc) ctx->fan_forget(d_nodes);     // vd_trace*: what the last walk over this top level found no longer holds
-    return rc ? rc : tlas_build_impl<VdTlasNode>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+int vd_tlas_build_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNode* d_nodes) {
+    return tlas_entry<VdTlasNode, kExact, false>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
 }
-int vd_tlas_build_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                           VdTlasNodeWide* d_nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, true);
-    if (!rc) ctx->fan_forget(d_nodes);     // vd_trace*: what the last walk over this top level found no longer holds
-    return rc ? rc : tlas_build_impl<VdTlasNodeWide>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+int vd_tlas_build_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNodeWide* d_nodes) {
+    return tlas_entry<VdTlasNodeWide, kExact, false>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
 }
-int vd_tlas_refit_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                      VdTlasNode* d_nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, false);
-    if (!rc) ctx->fan_forget(d_nodes);     // vd_trace*: what the last walk over this top level found no longer holds
-    return rc ? rc : tlas_refit_impl<VdTlasNode>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+int vd_tlas_refit_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNode* d_nodes) {
+    return tlas_entry<VdTlasNode, kRefit, false>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
 }
-int vd_tlas_refit_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                           VdTlasNodeWide* d_nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, d_inst, n, d_meshes, n_mesh, d_nodes, true);
-    if (!rc) ctx->fan_forget(d_nodes);     // vd_trace*: what the last walk over this top level found no longer holds
-    return rc ? rc : tlas_refit_impl<VdTlasNodeWide>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
+int vd_tlas_refit_wide_dev(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh, VdTlasNodeWide* d_nodes) {
+    return tlas_entry<VdTlasNodeWide, kRefit, false>(ctx, d_inst, n, d_meshes, n_mesh, d_nodes);
 }
-
 int vd_tlas_build(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNode* nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, false);
-    if (rc) return rc;
-    return tlas_host<VdTlasNode>(ctx, inst, n, meshes, n_mesh, nodes, false, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNode* dn) {
-        return tlas_build_impl<VdTlasNode>(ctx, di, n, dm, n_mesh, dn);
-    });
+    return tlas_entry<VdTlasNode, kExact, true>(ctx, inst, n, meshes, n_mesh, nodes);
 }
-int vd_tlas_build_wide(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh,
-                       VdTlasNodeWide* nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, true);
-    if (rc) return rc;
-    return tlas_host<VdTlasNodeWide>(ctx, inst, n, meshes, n_mesh, nodes, false, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNodeWide* dn) {
-        return tlas_build_impl<VdTlasNodeWide>(ctx, di, n, dm, n_mesh, dn);
-    });
+int vd_tlas_build_wide(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNodeWide* nodes) {
+    return tlas_entry<VdTlasNodeWide, kExact, true>(ctx, inst, n, meshes, n_mesh, nodes);
 }
 int vd_tlas_refit(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo* meshes, uint32_t n_mesh, VdTlasNode* nodes) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, false);
-    if (rc) return rc;
-    return tlas_host<VdTlasNode>(ctx, inst, n, meshes, n_mesh, nodes, true, [&](const VdInstance* di, const VdMeshInfo* dm, VdTlasNode* dn) {
-        return tlas_refit_impl<VdTlasNode>(ctx, di, n, dm, n_mesh, dn);
-    });
+    return tlas_entry<VdTlasNode, kRefit, true>(ctx, inst, n, meshes, n_mesh, nodes);
 }
 
 }  // extern "C"

@@ -1052,19 +1052,26 @@ __global__ void tight_root_kernel(VdTlasNode* nodes, unsigned n) {
 // WIDE: the scene's top level is VdTlasNodeWide (vd_trace_wide*).  Same call, except that the records are one table of
 // n_tlas_nodes x 64 B that needs no fill (records_wide_kernel), in an arena of its own (ctx->trace_wide) so that the narrow
 // calls' scratch does not grow with a wide scene's node count, and the wide instantiations of the kernels walk.
-template <bool WIDE = false>
-int launch_trace(VdCtx* ctx, const std::conditional_t<WIDE, VdTraceSceneWide, VdTraceScene>* sc, const float* d_tris, const VdRay* d_rays,
-                 uint32_t n_rays, VdHit* d_out, uint32_t* d_any = nullptr) {
-    void** arena = WIDE ? &ctx->trace_wide : &ctx->scratch;
-    size_t* arena_bytes = WIDE ? &ctx->trace_wide_bytes : &ctx->scratch_bytes;
-    // idle waves keep drawing from the ray counter after the last ray: leave it room below 2^32
-    if (n_rays > 0xf0000000u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: more than 0xf0000000 rays in one call");
-    // scratch: [256 B flags and counters][TLAS child pairs, 64 B x 65 536][entry records, 64 B x 65 536][mesh records][de-indexed triangles][fan-out]
-    // (pairs and entry records for all 65 536 indices a 16-bit child field can name: a stray index reads a poisoned slot, not beyond)
-    const size_t pair_bytes = (size_t)64 * (WIDE ? sc->n_tlas_nodes : kTlasSlots), irec_bytes = WIDE ? 0 : (size_t)64 * kTlasSlots,
-                 owner_bytes = WIDE ? 0 : (size_t)4 * kTlasSlots;
+template <bool WIDE> using SceneOf = std::conditional_t<WIDE, VdTraceSceneWide, VdTraceScene>;
+
+// What one trace call will do, decided before anything is launched (as pass1_plan does in cull.hip).  The call's arena:
+// [256 B flags and counters][TLAS child pairs, 64 B x 65 536][entry records, 64 B x 65 536][pair owners][mesh records][de-indexed triangles][fan-out]
+// (pairs and entry records for all 65 536 indices a 16-bit child field can name: a stray index reads a poisoned slot, not
+// beyond; WIDE: one table of 64 B per node and no owners), the fan-out as [256 B control words][best: 8 B per ray][jobs: 48 B x cap].
+struct TracePlan {
+    size_t pair_bytes, irec_bytes, owner_bytes, tris_at, tris_bytes, fan_at, best_bytes, total;
+    bool auto_prep;                        // the call de-indexes the leaves itself, into [tris_at, tris_at + tris_bytes)
+    unsigned waves, phases, fan_cap;       // the persistent grid, launches of the call (1: no fan-out), job slots
+    unsigned yield, ovf_words;             // Scene::yield; words of the overflow bitmap
+};
+template <bool WIDE>
+TracePlan trace_plan(VdCtx* ctx, const SceneOf<WIDE>* sc, bool prepared, uint32_t n_rays) {
+    TracePlan p;
+    p.pair_bytes = (size_t)64 * (WIDE ? sc->n_tlas_nodes : kTlasSlots);
+    p.irec_bytes = WIDE ? 0 : (size_t)64 * kTlasSlots;
+    p.owner_bytes = WIDE ? 0 : (size_t)4 * kTlasSlots;
     const size_t mrec_bytes = (size_t)128 * sc->n_meshes;
-    const size_t tris_at = 256 + pair_bytes + irec_bytes + owner_bytes + ((mrec_bytes + 255) & ~(size_t)255);
+    p.tris_at = 256 + p.pair_bytes + p.irec_bytes + p.owner_bytes + ((mrec_bytes + 255) & ~(size_t)255);
     // A call that was not given prepared leaves de-indexes them itself when that is cheap next to the walk (one pass over the
     // index buffer, 36 B per triangle into the scratch: 5 us for the stress scene's 131 k triangles, 20 us for the harness
     // scene's 1.2 M) - the plain vd_trace_dev then walks at the prepared rate.  Not for few rays over a big scene,
@@ -1073,170 +1080,227 @@ int launch_trace(VdCtx* ctx, const std::conditional_t<WIDE, VdTraceSceneWide, Vd
     // 16 Mi (576 MB), 0 turns it off.  vd_trace_prepare_dev is the explicit form without a limit.
     const size_t n_tri = sc->n_indices / 3u;
     const long long auto_opt = ctx->option(VD_OPT_TRACE_AUTO_PREPARE, 1);
-    const bool auto_prep = !d_tris && auto_opt != 0 && n_tri > 0 && sc->n_vertices > 0 && sc->n_meshes <= 65535u &&
-                           n_tri <= ((size_t)1 << (auto_opt >= 2 ? 24 : 21)) && (size_t)n_rays * 8u >= n_tri;
-    const size_t tris_bytes = auto_prep ? (((size_t)36 * n_tri + 64 + 255) & ~(size_t)255) : 0;
-    const size_t fan_at = tris_at + tris_bytes;
-    // fan-out (kFan*): calls with at least one ray per lane of the grid, scenes with enough instances for
-    // a ray to be long.  [256 B control words][best: 8 B per ray][jobs: 48 B x cap]
-    const unsigned waves = (unsigned)ctx->num_cus * (unsigned)std::min<long long>(kWavesPerCu, std::max<long long>(1, ctx->option(VD_OPT_TRACE_WAVES, kWavesPerCu)));
-    unsigned phases = (unsigned)std::min<long long>(4, std::max<long long>(1, ctx->option(VD_OPT_TRACE_FAN, kFanPhases)));
-    if ((size_t)n_rays < (size_t)waves * 64u || sc->n_instances < 64u) phases = 1u;
+    p.auto_prep = !prepared && auto_opt != 0 && n_tri > 0 && sc->n_vertices > 0 && sc->n_meshes <= 65535u &&
+                  n_tri <= ((size_t)1 << (auto_opt >= 2 ? 24 : 21)) && (size_t)n_rays * 8u >= n_tri;
+    p.tris_bytes = p.auto_prep ? (((size_t)36 * n_tri + 64 + 255) & ~(size_t)255) : 0;
+    p.fan_at = p.tris_at + p.tris_bytes;
+    // fan-out (kFan*): calls with at least one ray per lane of the grid, scenes with enough instances for a ray to be long.
+    p.waves = (unsigned)ctx->num_cus * (unsigned)std::min<long long>(kWavesPerCu, std::max<long long>(1, ctx->option(VD_OPT_TRACE_WAVES, kWavesPerCu)));
+    p.phases = (unsigned)std::min<long long>(4, std::max<long long>(1, ctx->option(VD_OPT_TRACE_FAN, kFanPhases)));
+    if ((size_t)n_rays < (size_t)p.waves * 64u || sc->n_instances < 64u) p.phases = 1u;
     // The fan-out's kernels cost ~15 % where no ray lives long enough to fan out (more code, spilled registers, launches that find
-    // nothing to do): a call remembers how many jobs it made, and while the last call over the same top level made fewer than one
-    // per 64 rays the next 15 calls over it run as one launch with the plain kernels; then the fan-out is tried again.
+    // nothing to do): a call remembers how many jobs it made (trace_flags), and while the last call over the same top level made fewer
+    // than one per 64 rays the next 15 calls over it run as one launch with the plain kernels; then the fan-out is tried again.
     const bool fan_default = ctx->option(VD_OPT_TRACE_FAN, -1) < 0;
-    const bool fan_same_scene = ctx->fan_tlas == sc->tlas_nodes && ctx->fan_nodes == sc->n_tlas_nodes && ctx->fan_inst == sc->n_instances;
-    if (phases > 1u && fan_default && fan_same_scene && ctx->fan_idle_calls != 0u) { phases = 1u; --ctx->fan_idle_calls; }
-    unsigned fan_cap = (unsigned)std::min<size_t>((size_t)1 << 21, (size_t)n_rays * 2u);
-    if (ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1) >= 0) fan_cap = (unsigned)std::min<long long>(fan_cap, ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1));      // tests: a list that fills up
-    const size_t best_bytes = ((size_t)n_rays * 8u + 255) & ~(size_t)255;
-    const size_t fan_bytes = phases > 1u ? 256 + best_bytes + (size_t)fan_cap * sizeof(FanJob) : 0;
-    int rc = vd_ensure(ctx, arena, arena_bytes, fan_at + fan_bytes);
+    if (p.phases > 1u && fan_default && ctx->fan_rest(sc->tlas_nodes, sc->n_tlas_nodes, sc->n_instances)) p.phases = 1u;
+    p.fan_cap = (unsigned)std::min<size_t>((size_t)1 << 21, (size_t)n_rays * 2u);
+    if (ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1) >= 0) p.fan_cap = (unsigned)std::min<long long>(p.fan_cap, ctx->option(VD_OPT_TRACE_FAN_SLOTS, -1));      // tests: a list that fills up
+    p.best_bytes = ((size_t)n_rays * 8u + 255) & ~(size_t)255;
+    p.total = p.fan_at + (p.phases > 1u ? 256 + p.best_bytes + (size_t)p.fan_cap * sizeof(FanJob) : 0);
+    p.yield = (unsigned)std::max<long long>(1, ctx->option(VD_OPT_TRACE_YIELD, kYieldDefault));
+    p.ovf_words = (n_rays + 31u) / 32u;
+    return p;
+}
+// the fan-out's part of the arena (nothing behind these pointers when plan.phases == 1)
+struct FanMem { unsigned* ctl; unsigned long long* best; FanJob* jobs; };      // ctl: [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
+FanMem fan_mem(const TracePlan& p, char* arena) {
+    char* const at = arena + p.fan_at;
+    return {reinterpret_cast<unsigned*>(at), reinterpret_cast<unsigned long long*>(at + 256), reinterpret_cast<FanJob*>(at + 256 + p.best_bytes)};
+}
+
+// The overflow bitmap, one bit per ray: "ran out of its 128 stack entries" (trace_deep_pass).  All zero between calls: zeroed
+// when (re)allocated and again after a call that set any (or left early), so a call that overflows nowhere pays nothing for
+// it.  A call marks it dirty here and clean (ctx->trace_ovf_dirty = false) when it has ended with every bit zero again.
+int ovf_acquire(VdCtx* ctx, unsigned ovf_words, unsigned** d_ovf) {
+    const size_t before = ctx->trace_ovf_bytes;      // the size, not the pointer: a grown buffer may come back at the address just freed
+    const int rc = vd_ensure(ctx, &ctx->trace_ovf, &ctx->trace_ovf_bytes, (size_t)ovf_words * 4u + 4u);
     if (rc) return rc;
-    char* const scratch = reinterpret_cast<char*>(*arena);
-    // one bit per ray: "ran out of its 128 stack entries" (second pass below).  All zero between calls: zeroed when (re)allocated
-    // and again after a call that set any, so a call that overflows nowhere pays nothing for it.
-    const unsigned ovf_words = (n_rays + 31u) / 32u;
-    {
-        const size_t before = ctx->trace_ovf_bytes;      // the size, not the pointer: a grown buffer may come back at the address just freed
-        rc = vd_ensure(ctx, &ctx->trace_ovf, &ctx->trace_ovf_bytes, (size_t)ovf_words * 4u + 4u);
-        if (rc) return rc;
-        if (ctx->trace_ovf_bytes != before || ctx->trace_ovf_dirty) VD_HIP_CHECK(ctx, hipMemsetAsync(ctx->trace_ovf, 0, ctx->trace_ovf_bytes, ctx->stream));
-        ctx->trace_ovf_dirty = true;       // until this call has ended cleanly
-    }
-    unsigned* d_ovf = reinterpret_cast<unsigned*>(ctx->trace_ovf);
-    vd_time_begin(ctx);
-    unsigned* d_flag = reinterpret_cast<unsigned*>(scratch);
-#ifdef VD_TUNING
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 256, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag + 16, 0xff, 8, ctx->stream));
-#else
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 64, ctx->stream));
-#endif
-    unsigned* fan_ctl = reinterpret_cast<unsigned*>(scratch + fan_at);      // [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
-    unsigned long long* fan_best = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(fan_ctl) + 256);
-    FanJob* fan_jobs = reinterpret_cast<FanJob*>(reinterpret_cast<char*>(fan_best) + best_bytes);
-    if (phases > 1u) {
-        VD_HIP_CHECK(ctx, hipMemsetAsync(fan_ctl, 0, 256, ctx->stream));
-        if (!d_any) VD_HIP_CHECK(ctx, hipMemsetAsync(fan_best, 0xff, best_bytes, ctx->stream));
-    }
-    float4* d_pair = reinterpret_cast<float4*>(scratch + 256);
-    float4* d_rec = reinterpret_cast<float4*>(reinterpret_cast<char*>(d_pair) + pair_bytes);
-    unsigned* d_owner = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_rec) + irec_bytes);
-    float4* d_mrec = reinterpret_cast<float4*>(reinterpret_cast<char*>(d_owner) + owner_bytes);
-    if (WIDE) d_rec = d_pair;      // one table: a node is a leaf or an interior node
-    const unsigned yield = (unsigned)std::max<long long>(1, ctx->option(VD_OPT_TRACE_YIELD, kYieldDefault));
+    if (ctx->trace_ovf_bytes != before || ctx->trace_ovf_dirty) VD_HIP_CHECK(ctx, hipMemsetAsync(ctx->trace_ovf, 0, ctx->trace_ovf_bytes, ctx->stream));
+    ctx->trace_ovf_dirty = true;       // until this call has ended cleanly
+    *d_ovf = reinterpret_cast<unsigned*>(ctx->trace_ovf);
+    return VD_OK;
+}
+
+// The per-call records of the scene, behind the arena's first 256 bytes.  Narrow: every slot poisoned, then the pair owners,
+// then pairs, entry records and mesh records.  WIDE: one table - a node is a leaf or an interior node - that needs no fill.
+struct TraceTables { float4* pair; float4* rec; float4* mrec; };
+template <bool WIDE>
+int launch_records(VdCtx* ctx, const SceneOf<WIDE>* sc, const TracePlan& p, char* arena, TraceTables* t) {
+    t->pair = reinterpret_cast<float4*>(arena + 256);
+    t->rec = WIDE ? t->pair : reinterpret_cast<float4*>(arena + 256 + p.pair_bytes);
+    unsigned* d_owner = reinterpret_cast<unsigned*>(arena + 256 + p.pair_bytes + p.irec_bytes);
+    t->mrec = reinterpret_cast<float4*>(arena + 256 + p.pair_bytes + p.irec_bytes + p.owner_bytes);
     if constexpr (WIDE) {
         const unsigned items = std::max(sc->n_tlas_nodes, sc->n_meshes);
         hipLaunchKernelGGL(records_wide_kernel, dim3(vd_blocks(ctx, items, 256u, 64u)), dim3(256), 0, ctx->stream, sc->tlas_nodes, sc->n_tlas_nodes,
-                           sc->instances, sc->n_instances, sc->meshes, sc->n_meshes, sc->bvh_nodes, sc->n_bvh_nodes, d_pair, d_mrec);
+                           sc->instances, sc->n_instances, sc->meshes, sc->n_meshes, sc->bvh_nodes, sc->n_bvh_nodes, t->pair, t->mrec);
     } else {
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_pair, 0xff, pair_bytes + irec_bytes + owner_bytes, ctx->stream));      // no pair slot carries a tag or has an owner yet, every entry record says "bad"
-    const unsigned n_rec = std::min(sc->n_tlas_nodes, kTlasSlots);      // nodes past 65 535 cannot be named by a 16-bit child field
-    hipLaunchKernelGGL(pair_owner_kernel, dim3((n_rec + 255u) / 256u), dim3(256), 0, ctx->stream, sc->tlas_nodes, n_rec, d_owner);
-    hipLaunchKernelGGL(records_kernel, dim3((std::max(n_rec, sc->n_meshes) + 255u) / 256u), dim3(256), 0, ctx->stream, sc->tlas_nodes,
-                       n_rec, sc->instances, sc->n_instances, sc->meshes, sc->n_meshes, sc->bvh_nodes, sc->n_bvh_nodes, d_rec, d_pair, d_mrec, d_owner);
+        VD_HIP_CHECK(ctx, hipMemsetAsync(t->pair, 0xff, p.pair_bytes + p.irec_bytes + p.owner_bytes, ctx->stream));      // no pair slot carries a tag or has an owner yet, every entry record says "bad"
+        const unsigned n_rec = std::min(sc->n_tlas_nodes, kTlasSlots);      // nodes past 65 535 cannot be named by a 16-bit child field
+        hipLaunchKernelGGL(pair_owner_kernel, dim3((n_rec + 255u) / 256u), dim3(256), 0, ctx->stream, sc->tlas_nodes, n_rec, d_owner);
+        hipLaunchKernelGGL(records_kernel, dim3((std::max(n_rec, sc->n_meshes) + 255u) / 256u), dim3(256), 0, ctx->stream, sc->tlas_nodes,
+                           n_rec, sc->instances, sc->n_instances, sc->meshes, sc->n_meshes, sc->bvh_nodes, sc->n_bvh_nodes, t->rec, t->pair, t->mrec, d_owner);
     }
-    const unsigned* gate = nullptr;
-    if (auto_prep) {
-        float* t = reinterpret_cast<float*>(scratch + tris_at);
-        hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, sc->n_meshes), dim3(256), 0, ctx->stream, sc->meshes, sc->vertices, sc->indices, sc->n_indices,
-                           sc->n_vertices, t, d_flag + 2);
-        d_tris = t; gate = d_flag + 2;        // non-zero: some mesh's index range cannot be de-indexed - the indexed kernel takes the call
-    }
-    const VdTlasNode* tlas_arg = reinterpret_cast<const VdTlasNode*>(sc->tlas_nodes);      // WIDE: the kernels cast it back (tl_instance)
-    Scene s{tlas_arg, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, d_tris, d_rec, d_pair, d_mrec, yield, d_ovf};
-    // two run-time booleans -> the template arguments of a launch: f(std::integral_constant<bool, a>{}, std::integral_constant<bool, b>{})
-    auto with_bools = [](bool x, bool y, auto&& f) {
-        using T = std::integral_constant<bool, true>; using F = std::integral_constant<bool, false>;
-        if (x) { if (y) f(T{}, T{}); else f(T{}, F{}); }
-        else { if (y) f(F{}, T{}); else f(F{}, F{}); }
-    };
-    const SceneArgs a{tlas_arg, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, yield, d_rec, d_pair, d_mrec, d_ovf};
-    // fan-out: launch 0 hands out the rays; launch p >= 1 the jobs appended before it started (fan_snapshot_kernel);
-    // every launch but the last may append; fan_resolve_kernel writes the records of the rays that were fanned out
-    for (unsigned ph = 0; ph < phases; ++ph) {
+    return VD_OK;
+}
+
+// The first pass takes the scene as plain kernel arguments: the Scene the host built, field by field (the kernels put it
+// together again, with the triangles their own argument).
+SceneArgs scene_args(const Scene& s) {
+    return {s.tlas, s.inst, s.meshes, s.bvh, s.verts, s.indices, s.n_meshes, s.yield, s.irec, s.tpair, s.mrec, s.ovf_bits};
+}
+// two run-time booleans -> the template arguments of a launch: f(std::integral_constant<bool, a>{}, std::integral_constant<bool, b>{})
+template <typename F> void with_bools(bool x, bool y, F&& f) {
+    using T = std::integral_constant<bool, true>; using N = std::integral_constant<bool, false>;
+    if (x) { if (y) f(T{}, T{}); else f(T{}, N{}); }
+    else { if (y) f(N{}, T{}); else f(N{}, N{}); }
+}
+
+// What a walk reads and writes besides the scene; flag: the arena's first words - [0] 1 = some ray overflowed, 2 / 4 = refusals, [1] the ray counter, [2] the gate
+struct TraceIo { const VdRay* rays; uint32_t n_rays; VdHit* out; uint32_t* any; unsigned* flag; };
+
+// The first pass.  fan-out: launch 0 hands out the rays; launch p >= 1 the jobs appended before it started (fan_snapshot_kernel);
+// every launch but the last may append; fan_resolve_kernel writes the records of the rays that were fanned out.
+// gate (s.tris de-indexed by this call): non-zero = some mesh's index range cannot be de-indexed - the indexed kernel takes the call.
+template <bool WIDE>
+void launch_first_pass(VdCtx* ctx, const TracePlan& p, const Scene& s, const unsigned* gate, const TraceIo& io, const FanMem& fm) {
+    const SceneArgs a = scene_args(s);
+    const float* d_tris = s.tris;
+    for (unsigned ph = 0; ph < p.phases; ++ph) {
         Fan fan = {};
-        if (phases > 1u) {
-            fan.jobs = fan_jobs; fan.append = fan_ctl; fan.cap = fan_cap; fan.best = fan_best; fan.level = ph;
-            fan.below = ph + 1u < phases ? kFanBelow : 0u;
-            if (ph) { fan.begin = fan_ctl + 8 + (ph - 1); fan.end = fan_ctl + 8 + ph; }
+        if (p.phases > 1u) {
+            fan.jobs = fm.jobs; fan.append = fm.ctl; fan.cap = p.fan_cap; fan.best = fm.best; fan.level = ph;
+            fan.below = ph + 1u < p.phases ? kFanBelow : 0u;
+            if (ph) { fan.begin = fm.ctl + 8 + (ph - 1); fan.end = fm.ctl + 8 + ph; }
         }
-        if (ph) hipLaunchKernelGGL(fan_snapshot_kernel, dim3(1), dim3(64), 0, ctx->stream, fan_ctl, fan_cap, fan_ctl + 8 + ph);
-        unsigned* next = ph == 0 ? d_flag + 1 : fan_ctl + ph;
-        with_bools(d_any != nullptr, phases > 1u, [&](auto any, auto fanned) {
+        if (ph) hipLaunchKernelGGL(fan_snapshot_kernel, dim3(1), dim3(64), 0, ctx->stream, fm.ctl, p.fan_cap, fm.ctl + 8 + ph);
+        unsigned* next = ph == 0 ? io.flag + 1 : fm.ctl + ph;
+        with_bools(io.any != nullptr, p.phases > 1u, [&](auto any, auto fanned) {
             constexpr bool A = decltype(any)::value, F = decltype(fanned)::value;
             if constexpr (WIDE) {
-                if (d_tris) hipLaunchKernelGGL((trace_wide_kernel<A, true, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any, d_flag,
+                if (d_tris) hipLaunchKernelGGL((trace_wide_kernel<A, true, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any, io.flag,
                                                next, d_tris, gate, fan);
-                if (!d_tris || gate) hipLaunchKernelGGL((trace_wide_kernel<A, false, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any,
-                                                        d_flag, next, d_tris, gate, fan);
+                if (!d_tris || gate) hipLaunchKernelGGL((trace_wide_kernel<A, false, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any,
+                                                        io.flag, next, d_tris, gate, fan);
                 return;
             }
-            if (d_tris) hipLaunchKernelGGL((trace_single_prep_kernel<A, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any, d_flag,
+            if (d_tris) hipLaunchKernelGGL((trace_single_prep_kernel<A, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any, io.flag,
                                            next, d_tris, gate, fan);
-            if (!d_tris || gate) hipLaunchKernelGGL((trace_single_kernel<A, F>), dim3(waves), dim3(64), 0, ctx->stream, a, d_rays, n_rays, d_out, d_any,
-                                                    d_flag, next, gate, fan);
+            if (!d_tris || gate) hipLaunchKernelGGL((trace_single_kernel<A, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any,
+                                                    io.flag, next, gate, fan);
         });
     }
-    if (phases > 1u && !d_any)
-        hipLaunchKernelGGL(fan_resolve_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(256), 0, ctx->stream, fan_jobs, fan_ctl, fan_cap, fan_best, d_out);
-    vd_time_end(ctx);
+    if (p.phases > 1u && !io.any)
+        hipLaunchKernelGGL(fan_resolve_kernel, dim3((unsigned)ctx->num_cus * 4u), dim3(256), 0, ctx->stream, fm.jobs, fm.ctl, p.fan_cap, fm.best, io.out);
+}
+
+// After the first pass: the flag word, the jobs the fan-out made and the gate come back into host_pinned[0..2] (blocks), the
+// context remembers what the fan-out found, and a scene the walk could not make sense of is refused.
+template <bool WIDE>
+int trace_flags(VdCtx* ctx, const TracePlan& p, const SceneOf<WIDE>* sc, const TraceIo& io, const FanMem& fm) {
     VD_HIP_CHECK(ctx, hipGetLastError());
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (phases > 1u) VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned + 1, fan_ctl, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned + 2, d_flag + 2, 4, hipMemcpyDeviceToHost, ctx->stream));      // the gate: which of the two kernels walked
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, io.flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (p.phases > 1u) VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned + 1, fm.ctl, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned + 2, io.flag + 2, 4, hipMemcpyDeviceToHost, ctx->stream));      // the gate: which of the two kernels walked
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (phases > 1u) {
-        ctx->fan_tlas = sc->tlas_nodes; ctx->fan_nodes = sc->n_tlas_nodes; ctx->fan_inst = sc->n_instances;
-        ctx->fan_idle_calls = ctx->host_pinned[1] < n_rays / 64u ? 15u : 0u;
-    }
+    if (p.phases > 1u) ctx->fan_remember(sc->tlas_nodes, sc->n_tlas_nodes, sc->n_instances, ctx->host_pinned[1] < io.n_rays / 64u);
     if (ctx->host_pinned[0] & 4u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: a TLAS leaf's instance, its mesh's root or the root's children lie outside the scene's buffers");
     if (ctx->host_pinned[0] & 2u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: BVH leaf with more than 3 triangles (BvhBuilder never makes one: blas.rs:108)");
-    if (ctx->host_pinned[0] & 1u) {
-        // Some rays needed more than the 128 entries a lane holds (the reference's own 24-entry stack is unchecked,
-        // shaders/utils/stack.wgsl:1-20: it has no answer there at all).  They are walked again, from their start, with the entries
-        // beyond 128 in a slab of global memory - same visits, same arithmetic, so the records are the ones an unbounded stack gives
-        // (tests/test_gpu_trace_deep.py holds them against the oracle through the first four sizes).  Entries per lane grow 1 Ki -> 4 Ki -> ...
-        // until nothing overflows; the slab is waves x 64 lanes x entries x 4 B under a 256 MB budget (fewer waves as it deepens),
-        // and a stack cannot hold more entries than the scene has nodes.
-        const bool prep_walked = d_tris && (!gate || ctx->host_pinned[2] == 0u);
-        const size_t node_bound = (size_t)sc->n_tlas_nodes + (size_t)sc->n_bvh_nodes + 2u;
-        const size_t list_bytes = ((size_t)n_rays * 4u + 255) & ~(size_t)255;
-        const size_t budget = (size_t)256 << 20;
-        for (size_t cap = 1024;; cap *= 4) {
-            const size_t per_wave = cap * 64u * 4u;
-            if (per_wave > ((size_t)2 << 30)) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_trace: a ray's traversal stack needs more than 128 + 4 Mi entries");
-            const unsigned waves_d = (unsigned)std::max<size_t>(1, std::min<size_t>(waves, budget / per_wave));
-            rc = vd_ensure(ctx, &ctx->trace_deep, &ctx->trace_deep_bytes, 256 + list_bytes + (size_t)waves_d * per_wave);
-            if (rc) return rc;
-            unsigned* ctl = reinterpret_cast<unsigned*>(ctx->trace_deep);                 // [0] listed rays, [1] supply counter
-            unsigned* list = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctl) + 256);
-            VD_HIP_CHECK(ctx, hipMemsetAsync(ctl, 0, 256, ctx->stream));
-            VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-            hipLaunchKernelGGL(ovf_list_kernel, dim3((ovf_words + 255u) / 256u), dim3(256), 0, ctx->stream, d_ovf, ovf_words, n_rays, list, ctl);
-            Scene sd = s;
-            sd.ovf_bits = nullptr;
-            sd.deep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(list) + list_bytes);
-            sd.deep_cap = (unsigned)cap;
-            with_bools(d_any != nullptr, prep_walked, [&](auto any, auto prep) {
-                constexpr bool A = decltype(any)::value, P = decltype(prep)::value;
-                if constexpr (WIDE) hipLaunchKernelGGL((trace_deep_wide_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays, list, ctl, d_out,
-                                                       d_any, d_flag, ctl + 1);
-                else hipLaunchKernelGGL((trace_deep_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, d_rays, list, ctl, d_out, d_any, d_flag, ctl + 1);
-            });
-            vd_time_end(ctx);                                                              // vd_last_gpu_ms covers the second pass too
-            VD_HIP_CHECK(ctx, hipGetLastError());
-            VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-            VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->host_pinned[0] & 6u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: the scene's buffers are inconsistent (bad leaf or entry met by the second pass)");
-            if (!(ctx->host_pinned[0] & 1u)) break;
-            if (cap >= node_bound) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_trace: traversal stack deeper than the scene has nodes (cyclic node arrays?)");
-        }
-        VD_HIP_CHECK(ctx, hipMemsetAsync(d_ovf, 0, (size_t)ovf_words * 4u, ctx->stream));
+    return VD_OK;
+}
+
+// The second pass.  Some rays needed more than the 128 entries a lane holds (the reference's own 24-entry stack is unchecked,
+// shaders/utils/stack.wgsl:1-20: it has no answer there at all).  They are walked again, from their start, with the entries
+// beyond 128 in a slab of global memory - same visits, same arithmetic, so the records are the ones an unbounded stack gives
+// (tests/test_gpu_trace_deep.py holds them against the oracle through the first four sizes).  Entries per lane grow 1 Ki -> 4 Ki -> ...
+// until nothing overflows; the slab is waves x 64 lanes x entries x 4 B under a 256 MB budget (fewer waves as it deepens),
+// and a stack cannot hold more entries than the scene has nodes (node_bound).
+// The largest cap that can run is 4 Mi entries per lane: cap goes 1 Ki, 4 Ki, ..., 1 Mi, 4 Mi, 16 Mi, a wave's part of the slab is
+// cap x 256 B, and the limit of 2 GiB per wave passes 4 Mi (1 GiB, by then one wave: the budget only ever lowers the wave
+// count to 1) and stops 16 Mi (4 GiB) - 8 Mi, where the limit itself lies, is not a step.  A ray that overflows 128 + 4 Mi
+// entries is therefore what the message below says.
+template <bool WIDE>
+int trace_deep_pass(VdCtx* ctx, const TracePlan& p, const Scene& s, bool prep_walked, size_t node_bound, const TraceIo& io) {
+    const size_t list_bytes = ((size_t)io.n_rays * 4u + 255) & ~(size_t)255;
+    const size_t budget = (size_t)256 << 20;
+    for (size_t cap = 1024;; cap *= 4) {
+        const size_t per_wave = cap * 64u * 4u;
+        if (per_wave > ((size_t)2 << 30)) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_trace: a ray's traversal stack needs more than 128 + 4 Mi entries");
+        const unsigned waves_d = (unsigned)std::max<size_t>(1, std::min<size_t>(p.waves, budget / per_wave));
+        const int rc = vd_ensure(ctx, &ctx->trace_deep, &ctx->trace_deep_bytes, 256 + list_bytes + (size_t)waves_d * per_wave);
+        if (rc) return rc;
+        unsigned* ctl = reinterpret_cast<unsigned*>(ctx->trace_deep);                 // [0] listed rays, [1] supply counter
+        unsigned* list = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ctl) + 256);
+        VD_HIP_CHECK(ctx, hipMemsetAsync(ctl, 0, 256, ctx->stream));
+        VD_HIP_CHECK(ctx, hipMemsetAsync(io.flag, 0, 4, ctx->stream));
+        hipLaunchKernelGGL(ovf_list_kernel, dim3((p.ovf_words + 255u) / 256u), dim3(256), 0, ctx->stream, s.ovf_bits, p.ovf_words, io.n_rays, list, ctl);
+        Scene sd = s;
+        sd.ovf_bits = nullptr;
+        sd.deep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(list) + list_bytes);
+        sd.deep_cap = (unsigned)cap;
+        with_bools(io.any != nullptr, prep_walked, [&](auto any, auto prep) {
+            constexpr bool A = decltype(any)::value, P = decltype(prep)::value;
+            if constexpr (WIDE) hipLaunchKernelGGL((trace_deep_wide_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, io.rays, list, ctl, io.out,
+                                                   io.any, io.flag, ctl + 1);
+            else hipLaunchKernelGGL((trace_deep_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, io.rays, list, ctl, io.out, io.any, io.flag, ctl + 1);
+        });
+        vd_time_end(ctx);                                                              // vd_last_gpu_ms covers the second pass too
+        VD_HIP_CHECK(ctx, hipGetLastError());
+        VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, io.flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+        VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->host_pinned[0] & 6u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: the scene's buffers are inconsistent (bad leaf or entry met by the second pass)");
+        if (!(ctx->host_pinned[0] & 1u)) break;
+        if (cap >= node_bound) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_trace: traversal stack deeper than the scene has nodes (cyclic node arrays?)");
     }
-    ctx->trace_ovf_dirty = false;
+    VD_HIP_CHECK(ctx, hipMemsetAsync(s.ovf_bits, 0, (size_t)p.ovf_words * 4u, ctx->stream));      // all zero between calls (ovf_acquire)
+    return VD_OK;
+}
+
+// One trace call: plan, arena and bitmap, the flag words, the records, the leaves when the call de-indexes them itself, the
+// first pass, its flags, and the second pass for the rays that overflowed.  Blocks.
+template <bool WIDE = false>
+int launch_trace(VdCtx* ctx, const SceneOf<WIDE>* sc, const float* d_tris, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out, uint32_t* d_any = nullptr) {
+    // idle waves keep drawing from the ray counter after the last ray: leave it room below 2^32
+    if (n_rays > 0xf0000000u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: more than 0xf0000000 rays in one call");
+    const TracePlan p = trace_plan<WIDE>(ctx, sc, d_tris != nullptr, n_rays);
+    int rc = vd_ensure(ctx, WIDE ? &ctx->trace_wide : &ctx->scratch, WIDE ? &ctx->trace_wide_bytes : &ctx->scratch_bytes, p.total);
+    if (rc) return rc;
+    char* const arena = reinterpret_cast<char*>(WIDE ? ctx->trace_wide : ctx->scratch);
+    unsigned* d_ovf = nullptr;
+    if ((rc = ovf_acquire(ctx, p.ovf_words, &d_ovf))) return rc;
+    vd_time_begin(ctx);
+    const TraceIo io{d_rays, n_rays, d_out, d_any, reinterpret_cast<unsigned*>(arena)};
+#ifdef VD_TUNING
+    VD_HIP_CHECK(ctx, hipMemsetAsync(io.flag, 0, 256, ctx->stream));
+    VD_HIP_CHECK(ctx, hipMemsetAsync(io.flag + 16, 0xff, 8, ctx->stream));
+#else
+    VD_HIP_CHECK(ctx, hipMemsetAsync(io.flag, 0, 64, ctx->stream));
+#endif
+    const FanMem fm = fan_mem(p, arena);
+    if (p.phases > 1u) {
+        VD_HIP_CHECK(ctx, hipMemsetAsync(fm.ctl, 0, 256, ctx->stream));
+        if (!d_any) VD_HIP_CHECK(ctx, hipMemsetAsync(fm.best, 0xff, p.best_bytes, ctx->stream));
+    }
+    TraceTables t;
+    if ((rc = launch_records<WIDE>(ctx, sc, p, arena, &t))) return rc;
+    const unsigned* gate = nullptr;
+    if (p.auto_prep) {
+        float* tris = reinterpret_cast<float*>(arena + p.tris_at);
+        hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, sc->n_meshes), dim3(256), 0, ctx->stream, sc->meshes, sc->vertices, sc->indices, sc->n_indices,
+                           sc->n_vertices, tris, io.flag + 2);
+        d_tris = tris; gate = io.flag + 2;
+    }
+    const VdTlasNode* tlas_arg = reinterpret_cast<const VdTlasNode*>(sc->tlas_nodes);      // WIDE: the kernels cast it back (tl_instance)
+    const Scene s{tlas_arg, sc->instances, sc->meshes, sc->bvh_nodes, sc->vertices, sc->indices, sc->n_meshes, d_tris, t.rec, t.pair, t.mrec, p.yield, d_ovf};
+    launch_first_pass<WIDE>(ctx, p, s, gate, io, fm);
+    vd_time_end(ctx);
+    if ((rc = trace_flags<WIDE>(ctx, p, sc, io, fm))) return rc;
+    if (ctx->host_pinned[0] & 1u) {      // some rays ran out of their 128 entries
+        const bool prep_walked = d_tris && (!gate || ctx->host_pinned[2] == 0u);
+        rc = trace_deep_pass<WIDE>(ctx, p, s, prep_walked, (size_t)sc->n_tlas_nodes + (size_t)sc->n_bvh_nodes + 2u, io);
+        if (rc) return rc;
+    }
+    ctx->trace_ovf_dirty = false;      // every bit is zero again
     return VD_OK;
 }
 
@@ -1267,49 +1331,111 @@ int build_tight_tlas(VdCtx* ctx, VdTraceAccel* a) {
     return VD_OK;
 }
 
+// de-index every mesh's leaves into `tris`; gridDim.y carries the mesh: 65 535 per launch
+void launch_prepare_tris(VdCtx* ctx, const VdTraceScene& s, float* tris, unsigned* err) {
+    for (unsigned m0 = 0; m0 < s.n_meshes; m0 += 65535u)
+        hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, std::min(s.n_meshes - m0, 65535u)), dim3(256), 0, ctx->stream, s.meshes + m0,
+                           s.vertices, s.indices, s.n_indices, s.n_vertices, tris, err);
+}
+
+// everything a VdTraceAccel owns, and the handle itself - when the stream no longer uses any of it
+void accel_free(VdCtx* ctx, VdTraceAccel* a) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (a->tris) (void)hipFree(a->tris);
+    if (a->tight) (void)hipFree(a->tight);
+    if (a->boxes) (void)hipFree(a->boxes);
+    if (a->lbvh) (void)hipFree(a->lbvh);
+    delete a;
+}
+
+int fail_named(VdCtx* ctx, const char* name, const char* text) {
+    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, text);
+    return VD_ERR_INVALID_ARG;
+}
 template <typename S> bool scene_ok(const S* s) {
     return s && s->tlas_nodes && s->instances && s->meshes && s->bvh_nodes && s->vertices && s->indices && s->n_meshes &&
            s->n_tlas_nodes && s->n_instances;
 }
-// what every vd_trace_wide* entry point checks before anything is launched
-int wide_scene_check(VdCtx* ctx, const VdTraceSceneWide* s) {
-    if (!scene_ok(s)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: incomplete scene");
-    if (s->n_tlas_nodes > 2u * VD_TLAS_WIDE_MAX_INSTANCES + 1u)
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: more than 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1 top-level nodes");
-    return VD_OK;
-}
 
 // host-pointer form of a trace call: the six buffers and the rays staged in, the records out
 template <bool WIDE>
-int trace_host(VdCtx* ctx, const std::conditional_t<WIDE, VdTraceSceneWide, VdTraceScene>* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
+int trace_host(VdCtx* ctx, const SceneOf<WIDE>* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
     using Node = std::conditional_t<WIDE, VdTlasNodeWide, VdTlasNode>;
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    // one staging arena, sub-allocated at 256-B boundaries
-    const size_t sz[8] = {(size_t)scene->n_tlas_nodes * sizeof(Node), (size_t)scene->n_instances * sizeof(VdInstance),
-                          (size_t)scene->n_meshes * sizeof(VdMeshInfo), (size_t)scene->n_bvh_nodes * sizeof(VdBvhNode),
-                          (size_t)scene->n_vertices * 12, (size_t)scene->n_indices * 4, (size_t)n_rays * sizeof(VdRay),
-                          (size_t)n_rays * sizeof(VdHit)};
-    const void* src[7] = {scene->tlas_nodes, scene->instances, scene->meshes, scene->bvh_nodes, scene->vertices, scene->indices, rays};
-    size_t off[8], total = 0;
-    for (int k = 0; k < 8; ++k) { off[k] = total; total += (sz[k] + 255) & ~(size_t)255; }
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, total);
+    enum { kNodes, kInst, kMeshes, kBvh, kVerts, kIdx, kRays, kOut, kBlobs };
+    VdBlob b[kBlobs] = {{scene->tlas_nodes, (size_t)scene->n_tlas_nodes * sizeof(Node), 256, nullptr},
+                        {scene->instances, (size_t)scene->n_instances * sizeof(VdInstance), 256, nullptr},
+                        {scene->meshes, (size_t)scene->n_meshes * sizeof(VdMeshInfo), 256, nullptr},
+                        {scene->bvh_nodes, (size_t)scene->n_bvh_nodes * sizeof(VdBvhNode), 256, nullptr},
+                        {scene->vertices, (size_t)scene->n_vertices * 12, 256, nullptr},
+                        {scene->indices, (size_t)scene->n_indices * 4, 256, nullptr},
+                        {rays, (size_t)n_rays * sizeof(VdRay), 256, nullptr},
+                        {nullptr, (size_t)n_rays * sizeof(VdHit), 256, nullptr}};
+    int rc = vd_stage_blobs(ctx, b, kBlobs);
     if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->stage_in);
-    for (int k = 0; k < 7; ++k)
-        if (sz[k]) VD_HIP_CHECK(ctx, hipMemcpyAsync(base + off[k], src[k], sz[k], hipMemcpyHostToDevice, ctx->stream));
     auto d = *scene;
-    d.tlas_nodes = reinterpret_cast<const Node*>(base + off[0]);
-    d.instances = reinterpret_cast<const VdInstance*>(base + off[1]);
-    d.meshes = reinterpret_cast<const VdMeshInfo*>(base + off[2]);
-    d.bvh_nodes = reinterpret_cast<const VdBvhNode*>(base + off[3]);
-    d.vertices = reinterpret_cast<const float*>(base + off[4]);
-    d.indices = reinterpret_cast<const uint32_t*>(base + off[5]);
-    VdHit* d_out = reinterpret_cast<VdHit*>(base + off[7]);
-    rc = launch_trace<WIDE>(ctx, &d, nullptr, reinterpret_cast<const VdRay*>(base + off[6]), n_rays, d_out);
+    d.tlas_nodes = static_cast<const Node*>(b[kNodes].dev);
+    d.instances = static_cast<const VdInstance*>(b[kInst].dev);
+    d.meshes = static_cast<const VdMeshInfo*>(b[kMeshes].dev);
+    d.bvh_nodes = static_cast<const VdBvhNode*>(b[kBvh].dev);
+    d.vertices = static_cast<const float*>(b[kVerts].dev);
+    d.indices = static_cast<const uint32_t*>(b[kIdx].dev);
+    rc = launch_trace<WIDE>(ctx, &d, nullptr, static_cast<const VdRay*>(b[kRays].dev), n_rays, static_cast<VdHit*>(b[kOut].dev));
+    return rc ? rc : vd_fetch_blob(ctx, out, &b[kOut]);
+}
+
+// What every vd_trace* walker does: the device guard, the context, the scene (`name`: no_scene when it is missing or incomplete -
+// every wide form words that as vd_trace_wide does, and refuses more nodes than the wide layout is specified for), nothing to
+// do without rays, rays and a place for the result (`name`: null rays/out), and the call - staged when the pointers are the host's.
+// Exactly one of out / any is the result; tris: the prepared leaves of vd_trace_*prepared_dev.
+template <bool WIDE, bool HOST = false>
+int trace_entry(VdCtx* ctx, const char* name, const char* no_scene, const SceneOf<WIDE>* sc, const float* tris, const VdRay* rays, uint32_t n_rays,
+                VdHit* out, uint32_t* any) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (!scene_ok(sc)) return fail_named(ctx, WIDE ? "vd_trace_wide" : name, no_scene);
+    if (WIDE && sc->n_tlas_nodes > 2u * VD_TLAS_WIDE_MAX_INSTANCES + 1u)
+        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: more than 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1 top-level nodes");
+    if (n_rays == 0) return VD_OK;
+    if (!rays || (!out && !any)) return fail_named(ctx, name, "null rays/out");
+    if constexpr (HOST) return trace_host<WIDE>(ctx, sc, rays, n_rays, out);
+    else return launch_trace<WIDE>(ctx, sc, tris, rays, n_rays, out, any);
+}
+
+// vd_traverse_iter* / vd_traverse*: one mesh, one ray per lane; `recursive` picks the walk (traverse_rec_kernel, from t0) and
+// `host` the form: the mesh and the rays staged in (n_vert vertices, n_tri triangles), the distances out.
+int traverse_entry(VdCtx* ctx, bool recursive, bool host, float t0, const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, uint32_t n_vert,
+                   const uint32_t* indices, uint32_t n_tri, const VdRay* rays, uint32_t n_rays, float* out_dist) {
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    const char* name = host ? "vd_traverse[_iter]" : recursive ? "vd_traverse" : "vd_traverse_iter";
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (!nodes || n_nodes == 0 || !verts_xyz || !indices) return fail_named(ctx, name, "incomplete mesh");
+    if (n_rays == 0) return VD_OK;
+    if (!rays || !out_dist) return fail_named(ctx, name, "null rays/out");
+    VdBlob b[5] = {{nodes, (size_t)n_nodes * sizeof(VdBvhNode), 256, nullptr}, {verts_xyz, (size_t)n_vert * 12, 256, nullptr},
+                   {indices, (size_t)n_tri * 12, 256, nullptr}, {rays, (size_t)n_rays * sizeof(VdRay), 256, nullptr},
+                   {nullptr, (size_t)n_rays * 4, 256, nullptr}};
+    int rc = host ? vd_stage_blobs(ctx, b, 5) : VD_OK;
     if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, sz[7], hipMemcpyDeviceToHost, ctx->stream));
+    const VdBvhNode* d_nodes = host ? static_cast<const VdBvhNode*>(b[0].dev) : nodes;
+    const float* d_verts = host ? static_cast<const float*>(b[1].dev) : verts_xyz;
+    const uint32_t* d_indices = host ? static_cast<const uint32_t*>(b[2].dev) : indices;
+    const VdRay* d_rays = host ? static_cast<const VdRay*>(b[3].dev) : rays;
+    float* d_out = host ? static_cast<float*>(b[4].dev) : out_dist;
+    if ((rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, 256))) return rc;
+    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
+    vd_time_begin(ctx);
+    VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
+    if (recursive) hipLaunchKernelGGL(traverse_rec_kernel, dim3((n_rays + 63u) / 64u), dim3(64), 0, ctx->stream, d_nodes, d_verts, d_indices, d_rays,
+                                      n_rays, t0, d_out, d_flag);
+    else hipLaunchKernelGGL(traverse_iter_kernel, dim3((n_rays + 63u) / 64u), dim3(64), 0, ctx->stream, d_nodes, d_verts, d_indices, d_rays,
+                            n_rays, d_out, d_flag);
+    vd_time_end(ctx);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    if (ctx->host_pinned[0]) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, recursive ? "vd_traverse: traversal stack (128 pending right children per ray) exceeded"
+                                                                           : "vd_traverse_iter: traversal stack (128 entries per ray) exceeded");
+    return host ? vd_fetch_blob(ctx, out_dist, &b[4]) : VD_OK;
 }
 
 }  // namespace
@@ -1337,22 +1463,30 @@ int vd_debug_trace_counters(VdCtx* ctx, uint64_t* out /*[11]*/) {
 }
 #endif
 
+// The walkers (trace_entry): what differs is the name in the messages, the node type, whose pointers these are, and closest hit / any hit.
 int vd_trace_dev(VdCtx* ctx, const VdTraceScene* d_scene, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!scene_ok(d_scene)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: incomplete scene");
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: null rays/out");
-    return launch_trace(ctx, d_scene, nullptr, d_rays, n_rays, d_out);
+    return trace_entry<false>(ctx, "vd_trace", "incomplete scene", d_scene, nullptr, d_rays, n_rays, d_out, nullptr);
 }
-
 int vd_trace_any_dev(VdCtx* ctx, const VdTraceScene* d_scene, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!scene_ok(d_scene)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_any: incomplete scene");
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out_hit) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_any: null rays/out");
-    return launch_trace(ctx, d_scene, nullptr, d_rays, n_rays, nullptr, d_out_hit);
+    return trace_entry<false>(ctx, "vd_trace_any", "incomplete scene", d_scene, nullptr, d_rays, n_rays, nullptr, d_out_hit);
+}
+int vd_trace_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
+    return trace_entry<false>(ctx, "vd_trace_prepared", "null accel", accel ? &accel->scene : nullptr, accel ? accel->tris : nullptr, d_rays, n_rays, d_out, nullptr);
+}
+int vd_trace_any_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
+    return trace_entry<false>(ctx, "vd_trace_any_prepared", "null accel", accel ? &accel->scene : nullptr, accel ? accel->tris : nullptr, d_rays, n_rays, nullptr, d_out_hit);
+}
+int vd_trace(VdCtx* ctx, const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
+    return trace_entry<false, true>(ctx, "vd_trace", "incomplete scene", scene, nullptr, rays, n_rays, out, nullptr);
+}
+int vd_trace_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
+    return trace_entry<true>(ctx, "vd_trace_wide", "incomplete scene", d_scene, nullptr, d_rays, n_rays, d_out, nullptr);
+}
+int vd_trace_any_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
+    return trace_entry<true>(ctx, "vd_trace_any_wide", "incomplete scene", d_scene, nullptr, d_rays, n_rays, nullptr, d_out_hit);
+}
+int vd_trace_wide(VdCtx* ctx, const VdTraceSceneWide* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
+    return trace_entry<true, true>(ctx, "vd_trace_wide", "incomplete scene", scene, nullptr, rays, n_rays, out, nullptr);
 }
 
 int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel** out) {
@@ -1364,19 +1498,17 @@ int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel**
     if (!a) return VD_ERR_OOM;
     a->scene = *d_scene;
     const size_t n_tri = d_scene->n_indices / 3u;
-    if (hipMalloc(reinterpret_cast<void**>(&a->tris), 36 * n_tri + 64) != hipSuccess) { delete a; VD_FAIL(ctx, VD_ERR_OOM, "vd_trace_prepare: triangle array"); }
+    if (hipMalloc(reinterpret_cast<void**>(&a->tris), 36 * n_tri + 64) != hipSuccess) { a->tris = nullptr; accel_free(ctx, a); VD_FAIL(ctx, VD_ERR_OOM, "vd_trace_prepare: triangle array"); }
     int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, 256);
-    if (rc) { (void)hipFree(a->tris); delete a; return rc; }
+    if (rc) { accel_free(ctx, a); return rc; }
     unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
     (void)hipMemsetAsync(d_flag, 0, 4, ctx->stream);
     (void)hipMemsetAsync(a->tris, 0, 36 * n_tri + 64, ctx->stream);      // index ranges no mesh covers
-    for (unsigned m0 = 0; m0 < d_scene->n_meshes; m0 += 65535u)      // gridDim.y carries the mesh: 65 535 per launch
-        hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, std::min(d_scene->n_meshes - m0, 65535u)), dim3(256), 0, ctx->stream, d_scene->meshes + m0,
-                           d_scene->vertices, d_scene->indices, d_scene->n_indices, d_scene->n_vertices, a->tris, d_flag);
+    launch_prepare_tris(ctx, *d_scene, a->tris, d_flag);
     hipError_t e = hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess || ctx->host_pinned[0]) {
-        (void)hipFree(a->tris); delete a;
+        accel_free(ctx, a);
         if (e != hipSuccess) VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
         VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_prepare: a mesh's index range or a vertex index lies outside the scene's buffers");
     }
@@ -1390,13 +1522,9 @@ int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel**
                     hipMalloc(reinterpret_cast<void**>(&a->tight), sizeof(VdTlasNode) * (2 * (size_t)n + 1)) == hipSuccess &&
                     (a->tight_mode != 2u || hipMalloc(reinterpret_cast<void**>(&a->lbvh), lbvh_bytes) == hipSuccess);
         if (good) good = hipMemsetAsync(a->tight, 0, sizeof(VdTlasNode) * (2 * (size_t)n + 1), ctx->stream) == hipSuccess;      // slots a builder leaves unused read as leaves nobody reaches
-        int rc_t = good ? build_tight_tlas(ctx, a) : VD_ERR_OOM;
+        const int rc_t = good ? build_tight_tlas(ctx, a) : VD_ERR_OOM;
         if (rc_t) {
-            (void)hipStreamSynchronize(ctx->stream);
-            if (a->boxes) (void)hipFree(a->boxes);
-            if (a->lbvh) (void)hipFree(a->lbvh);
-            if (a->tight) (void)hipFree(a->tight);
-            (void)hipFree(a->tris); delete a;
+            accel_free(ctx, a);
             if (rc_t == VD_ERR_OOM) VD_FAIL(ctx, VD_ERR_OOM, "vd_trace_prepare: the private top level (VD_OPT_TRACE_TIGHT_TLAS) could not be allocated");
             return rc_t;
         }
@@ -1429,9 +1557,7 @@ int vd_trace_accel_update_geometry_dev(VdCtx* ctx, VdTraceAccel* accel) {
     if (!ctx || !accel) return VD_ERR_INVALID_ARG;
     const VdTraceScene& s = accel->scene;
     unsigned* d_ignored = reinterpret_cast<unsigned*>(accel->tris + 9 * (size_t)(s.n_indices / 3u));      // the array's slack: prepare validated, nobody reads this word
-    for (unsigned m0 = 0; m0 < s.n_meshes; m0 += 65535u)
-        hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, std::min(s.n_meshes - m0, 65535u)), dim3(256), 0, ctx->stream, s.meshes + m0,
-                           s.vertices, s.indices, s.n_indices, s.n_vertices, accel->tris, d_ignored);
+    launch_prepare_tris(ctx, s, accel->tris, d_ignored);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
@@ -1439,32 +1565,9 @@ int vd_trace_accel_update_geometry_dev(VdCtx* ctx, VdTraceAccel* accel) {
 int vd_trace_release(VdCtx* ctx, VdTraceAccel* accel) {
     VdDeviceGuard vd_guard_(ctx);
     if (!ctx || !accel) return VD_ERR_INVALID_ARG;
-    (void)hipStreamSynchronize(ctx->stream);
     if (accel->tight) ctx->fan_forget(accel->tight);
-    if (accel->tris) (void)hipFree(accel->tris);
-    if (accel->tight) (void)hipFree(accel->tight);
-    if (accel->boxes) (void)hipFree(accel->boxes);
-    if (accel->lbvh) (void)hipFree(accel->lbvh);
-    delete accel;
+    accel_free(ctx, accel);
     return VD_OK;
-}
-
-int vd_trace_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
-    VdDeviceGuard vd_guard_(ctx);
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!accel) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_prepared: null accel");
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_prepared: null rays/out");
-    return launch_trace(ctx, &accel->scene, accel->tris, d_rays, n_rays, d_out);
-}
-
-int vd_trace_any_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
-    VdDeviceGuard vd_guard_(ctx);
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!accel) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_any_prepared: null accel");
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out_hit) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_any_prepared: null rays/out");
-    return launch_trace(ctx, &accel->scene, accel->tris, d_rays, n_rays, nullptr, d_out_hit);
 }
 
 int vd_shadow_rays_dev(VdCtx* ctx, const float* d_positions, const float* d_normals, uint32_t n_points, const float* light_position,
@@ -1494,139 +1597,34 @@ int vd_primary_rays_dev(VdCtx* ctx, const VdCameraUniform* camera, uint32_t widt
     return VD_OK;
 }
 
-int vd_traverse_iter_dev(VdCtx* ctx, const VdBvhNode* d_nodes, uint32_t n_nodes, const float* d_verts_xyz, const uint32_t* d_indices,
-                         const VdRay* d_rays, uint32_t n_rays, float* d_out_dist) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!d_nodes || n_nodes == 0 || !d_verts_xyz || !d_indices) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_traverse_iter: incomplete mesh");
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out_dist) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_traverse_iter: null rays/out");
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, 256);
-    if (rc) return rc;
-    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
-    vd_time_begin(ctx);
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(traverse_iter_kernel, dim3((n_rays + 63u) / 64u), dim3(64), 0, ctx->stream, d_nodes, d_verts_xyz, d_indices, d_rays,
-                       n_rays, d_out_dist, d_flag);
-    vd_time_end(ctx);
-    VD_HIP_CHECK(ctx, hipGetLastError());
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->host_pinned[0]) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_traverse_iter: traversal stack (128 entries per ray) exceeded");
-    return VD_OK;
-}
-
-int vd_traverse_dev(VdCtx* ctx, const VdBvhNode* d_nodes, uint32_t n_nodes, const float* d_verts_xyz, const uint32_t* d_indices,
-                    const VdRay* d_rays, uint32_t n_rays, float t0, float* d_out_dist) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!d_nodes || n_nodes == 0 || !d_verts_xyz || !d_indices) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_traverse: incomplete mesh");
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out_dist) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_traverse: null rays/out");
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, 256);
-    if (rc) return rc;
-    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
-    vd_time_begin(ctx);
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(traverse_rec_kernel, dim3((n_rays + 63u) / 64u), dim3(64), 0, ctx->stream, d_nodes, d_verts_xyz, d_indices, d_rays,
-                       n_rays, t0, d_out_dist, d_flag);
-    vd_time_end(ctx);
-    VD_HIP_CHECK(ctx, hipGetLastError());
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->host_pinned[0]) VD_FAIL(ctx, VD_ERR_STACK_OVERFLOW, "vd_traverse: traversal stack (128 pending right children per ray) exceeded");
-    return VD_OK;
-}
-
-int vd_trace(VdCtx* ctx, const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!scene_ok(scene)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: incomplete scene");
-    if (n_rays == 0) return VD_OK;
-    if (!rays || !out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace: null rays/out");
-    return trace_host<false>(ctx, scene, rays, n_rays, out);
-}
-
-int vd_trace_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
-    VdDeviceGuard vd_guard_(ctx);
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (const int rc = wide_scene_check(ctx, d_scene)) return rc;
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: null rays/out");
-    return launch_trace<true>(ctx, d_scene, nullptr, d_rays, n_rays, d_out);
-}
-
-int vd_trace_any_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
-    VdDeviceGuard vd_guard_(ctx);
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (const int rc = wide_scene_check(ctx, d_scene)) return rc;
-    if (n_rays == 0) return VD_OK;
-    if (!d_rays || !d_out_hit) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_any_wide: null rays/out");
-    return launch_trace<true>(ctx, d_scene, nullptr, d_rays, n_rays, nullptr, d_out_hit);
-}
-
-int vd_trace_wide(VdCtx* ctx, const VdTraceSceneWide* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
-    VdDeviceGuard vd_guard_(ctx);
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (const int rc = wide_scene_check(ctx, scene)) return rc;
-    if (n_rays == 0) return VD_OK;
-    if (!rays || !out) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_wide: null rays/out");
-    return trace_host<true>(ctx, scene, rays, n_rays, out);
-}
-
 int vd_primary_rays(VdCtx* ctx, const VdCameraUniform* camera, uint32_t width, uint32_t height, VdRay* rays) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
     const uint64_t n = (uint64_t)width * height;
     if (n && !rays) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_primary_rays: null rays");
-    int rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, (size_t)n * sizeof(VdRay));
+    VdBlob b = {nullptr, (size_t)n * sizeof(VdRay), 256, nullptr};
+    int rc = vd_stage_blobs(ctx, &b, 1);
     if (rc) return rc;
-    rc = vd_primary_rays_dev(ctx, camera, width, height, reinterpret_cast<VdRay*>(ctx->stage_out));
+    rc = vd_primary_rays_dev(ctx, camera, width, height, static_cast<VdRay*>(b.dev));
     if (rc || n == 0) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(rays, ctx->stage_out, (size_t)n * sizeof(VdRay), hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    return vd_fetch_blob(ctx, rays, &b);
 }
 
-static int traverse_host(VdCtx* ctx, bool recursive, float t0, const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, uint32_t n_vert,
-                         const uint32_t* indices, uint32_t n_tri, const VdRay* rays, uint32_t n_rays, float* out_dist) {
-    if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!nodes || n_nodes == 0 || !verts_xyz || !indices) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_traverse[_iter]: incomplete mesh");
-    if (n_rays == 0) return VD_OK;
-    if (!rays || !out_dist) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_traverse[_iter]: null rays/out");
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t sz[5] = {(size_t)n_nodes * sizeof(VdBvhNode), (size_t)n_vert * 12, (size_t)n_tri * 12, (size_t)n_rays * sizeof(VdRay),
-                          (size_t)n_rays * 4};
-    const void* src[4] = {nodes, verts_xyz, indices, rays};
-    size_t off[5], total = 0;
-    for (int k = 0; k < 5; ++k) { off[k] = total; total += (sz[k] + 255) & ~(size_t)255; }
-    int rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, total);
-    if (rc) return rc;
-    char* base = reinterpret_cast<char*>(ctx->stage_in);
-    for (int k = 0; k < 4; ++k)
-        if (sz[k]) VD_HIP_CHECK(ctx, hipMemcpyAsync(base + off[k], src[k], sz[k], hipMemcpyHostToDevice, ctx->stream));
-    float* d_out = reinterpret_cast<float*>(base + off[4]);
-    const VdBvhNode* dn = reinterpret_cast<const VdBvhNode*>(base + off[0]);
-    const float* dv = reinterpret_cast<const float*>(base + off[1]);
-    const uint32_t* di = reinterpret_cast<const uint32_t*>(base + off[2]);
-    const VdRay* dr = reinterpret_cast<const VdRay*>(base + off[3]);
-    rc = recursive ? vd_traverse_dev(ctx, dn, n_nodes, dv, di, dr, n_rays, t0, d_out) : vd_traverse_iter_dev(ctx, dn, n_nodes, dv, di, dr, n_rays, d_out);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(out_dist, d_out, sz[4], hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+int vd_traverse_iter_dev(VdCtx* ctx, const VdBvhNode* d_nodes, uint32_t n_nodes, const float* d_verts_xyz, const uint32_t* d_indices,
+                         const VdRay* d_rays, uint32_t n_rays, float* d_out_dist) {
+    return traverse_entry(ctx, false, false, 0.0f, d_nodes, n_nodes, d_verts_xyz, 0, d_indices, 0, d_rays, n_rays, d_out_dist);
 }
-
+int vd_traverse_dev(VdCtx* ctx, const VdBvhNode* d_nodes, uint32_t n_nodes, const float* d_verts_xyz, const uint32_t* d_indices,
+                    const VdRay* d_rays, uint32_t n_rays, float t0, float* d_out_dist) {
+    return traverse_entry(ctx, true, false, t0, d_nodes, n_nodes, d_verts_xyz, 0, d_indices, 0, d_rays, n_rays, d_out_dist);
+}
 int vd_traverse_iter(VdCtx* ctx, const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, uint32_t n_vert,
                      const uint32_t* indices, uint32_t n_tri, const VdRay* rays, uint32_t n_rays, float* out_dist) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    return traverse_host(ctx, false, 0.0f, nodes, n_nodes, verts_xyz, n_vert, indices, n_tri, rays, n_rays, out_dist);
+    return traverse_entry(ctx, false, true, 0.0f, nodes, n_nodes, verts_xyz, n_vert, indices, n_tri, rays, n_rays, out_dist);
 }
-
 int vd_traverse(VdCtx* ctx, const VdBvhNode* nodes, uint32_t n_nodes, const float* verts_xyz, uint32_t n_vert,
                 const uint32_t* indices, uint32_t n_tri, const VdRay* rays, uint32_t n_rays, float t0, float* out_dist) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    return traverse_host(ctx, true, t0, nodes, n_nodes, verts_xyz, n_vert, indices, n_tri, rays, n_rays, out_dist);
+    return traverse_entry(ctx, true, true, t0, nodes, n_nodes, verts_xyz, n_vert, indices, n_tri, rays, n_rays, out_dist);
 }
 
 }  // extern "C"

@@ -45,6 +45,10 @@ struct VdCtx {
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene
     void fan_forget(const void* tlas) { if (tlas == fan_tlas) { fan_tlas = nullptr; fan_idle_calls = 0; } }   // the top level at this address was rebuilt / refitted / released
+    // A call that would fan out asks first: true = the last call over this very top level made too few jobs, run as one launch
+    // (one of the 15 such calls is used up).  fan_remember: what a call that did fan out found.
+    bool fan_rest(const void* tlas, unsigned nodes, unsigned inst) { const bool rest = tlas == fan_tlas && nodes == fan_nodes && inst == fan_inst && fan_idle_calls != 0u; if (rest) --fan_idle_calls; return rest; }
+    void fan_remember(const void* tlas, unsigned nodes, unsigned inst, bool few_jobs) { fan_tlas = tlas; fan_nodes = nodes; fan_inst = inst; fan_idle_calls = few_jobs ? 15u : 0u; }
     unsigned refit_n = 0;                                         // instance count the arena's layout was last used with
     unsigned long long scan_launches = 0;
     void* dbg_ptr = nullptr; unsigned dbg_count = 0; void* dbg_ptr2 = nullptr;   // tuning hooks
@@ -153,6 +157,12 @@ extern "C" __attribute__((visibility("hidden"))) int vd_stage(VdCtx* ctx, const 
                                                               unsigned n_blobs, size_t out_bytes, VdStaged* s);
 extern "C" __attribute__((visibility("hidden"))) int vd_fetch_lists(VdCtx* ctx, const char* name, bool scan, const VdStaged* s, uint32_t n_views, uint32_t n_inst,
                                                                     int pad_tail, VdDrawIndexedIndirect* out, uint64_t out_stride, uint32_t* out_counts);
+
+// ctx.hip: the staged round trip of the host-pointer forms that are not draw lists (vd_trace*, vd_traverse*, vd_primary_rays,
+// vd_tlas_*).  vd_stage_blobs drains the stream, sizes ONE arena in ctx->stage_in, places every blob at its alignment (*dev) and
+// uploads those that have a host pointer - one without is room for a result; vd_fetch_blob copies a blob back and drains again.
+extern "C" __attribute__((visibility("hidden"))) int vd_stage_blobs(VdCtx* ctx, VdBlob* blobs, unsigned n_blobs);
+extern "C" __attribute__((visibility("hidden"))) int vd_fetch_blob(VdCtx* ctx, void* host, const VdBlob* blob);
 
 // Calls f with a value of the mesh-id type of that width - unsigned char, unsigned short or unsigned: the one place
 // where an id width (1, 2 or 4 bytes; checked by the caller) picks a kernel instantiation.
