@@ -244,7 +244,9 @@ typedef enum VdOption {
                                      agglomerative builder of tlas.rs:56-105 (best tree; the sequential chain: 35 ms for
                                      2 000 instances); 2: an LBVH built on all CUs (~0.1 ms, <= 32 767 instances) - the form
                                      for scenes that move.  The private top level is a snapshot of the instances:
-                                     vd_trace_accel_update_dev rebuilds it after they moved.                       */
+                                     vd_trace_accel_update_dev rebuilds it after they moved, vd_trace_accel_refit_dev
+                                     refits it.  vd_trace_prepare_wide_dev: 1 and 2 both select the LBVH, over
+                                     VdTlasNodeWide, for 2 .. VD_TLAS_WIDE_MAX_INSTANCES instances.                */
     VD_OPT_COUNT_ = 32
 } VdOption;
 int         vd_ctx_set_option(VdCtx* ctx, int option /* VdOption */, int64_t value);
@@ -693,8 +695,8 @@ int vd_trace_dev(VdCtx* ctx, const VdTraceScene* d_scene /* struct on host, poin
  * before anything is launched, for n_tlas_nodes > 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1.  Total like the narrow call (second
  * pass over a global-memory stack, same limits), same fan-out rule, same per-call de-indexing of the leaves.  Every call
  * first writes one 64-byte record per top-level node - 48 B read, 64 B written, nothing filled: 235 MB at 2 Mi nodes - into an arena of the
- * context that only wide calls use, so narrow and wide calls may alternate.  Prepared (VdTraceAccel) wide scenes and
- * VD_OPT_TRACE_TIGHT_TLAS for them do not exist.                                                                       */
+ * context that only wide calls use, so narrow and wide calls may alternate.  vd_trace_prepare_wide_dev (below) makes a
+ * prepared wide scene (VdTraceAccel), with VD_OPT_TRACE_TIGHT_TLAS a private tight top level for it.                   */
 typedef struct VdTraceSceneWide {
     const VdTlasNodeWide* tlas_nodes; uint32_t n_tlas_nodes;
     const VdInstance* instances;    uint32_t n_instances;
@@ -734,7 +736,8 @@ int vd_trace_accel_info(const VdTraceAccel* accel, VdTraceAccelInfo* out);
 /* Rebuilds the private top level of a prepared scene from the scene's instance buffer as it is NOW (the instances moved:
  * shaders/compute_update.wgsl:10-28).  The triangles are not touched.  Blocks (it reads back whether every instance still
  * qualifies; if one does not, the walk goes back to the scene's own top level until an update finds all qualifying again).
- * A no-op for a scene prepared without VD_OPT_TRACE_TIGHT_TLAS: that one walks the host's top level, which the host refits.  */
+ * A no-op for a scene prepared without VD_OPT_TRACE_TIGHT_TLAS: that one walks the host's top level, which the host refits.
+ * The cheap form that keeps the tree is vd_trace_accel_refit_dev (below).                                                    */
 int vd_trace_accel_update_dev(VdCtx* ctx, VdTraceAccel* accel);
 /* Re-runs the de-indexing of vd_trace_prepare_dev into the accel's existing triangle array, from the scene's vertex buffer
  * as it is NOW (a mesh deformed).  Enqueues only: no validation and no read-back - indices and meshes have not changed and
@@ -743,6 +746,47 @@ int vd_trace_accel_update_geometry_dev(VdCtx* ctx, VdTraceAccel* accel);
 int vd_trace_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out);
 int vd_trace_any_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays,
                               uint32_t* d_out_hit);
+
+/* The prepared form of a WIDE scene: ONE handle type - the VdTraceAccel this returns is what vd_trace_prepared_dev,
+ * vd_trace_any_prepared_dev, vd_trace_accel_update_dev, vd_trace_accel_refit_dev, vd_trace_accel_update_geometry_dev and
+ * vd_trace_release take, and they dispatch on the handle (one made by vd_trace_prepare_dev behaves as it always did).
+ * Validates as vd_trace_prepare_dev does and BLOCKS: index ranges are checked; VD_ERR_INVALID_ARG for an incomplete scene and
+ * for n_tlas_nodes > 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1; VD_ERR_OOM with nothing left allocated.  All leaves are de-indexed,
+ * 36 B per triangle, whatever their number (the per-call de-indexing of vd_trace_wide_dev stops at 2 Mi / 16 Mi triangles).
+ * Owns: the triangle copy and, when it has one, the private top level and its work memory; the six scene buffers stay the
+ * caller's and must outlive the handle (the accel keeps the pointers, not the data).
+ * VD_OPT_TRACE_TIGHT_TLAS == 0: the accel walks the scene's own wide nodes, read through the scene's pointers by every call -
+ * they may change freely - and the records are those of vd_trace_wide_dev bit for bit.
+ * VD_OPT_TRACE_TIGHT_TLAS != 0 and 2 <= n_instances <= VD_TLAS_WIDE_MAX_INSTANCES (else ignored, silently, as the narrow call
+ * does): the accel owns a private VdTlasNodeWide top level over the tight boxes of VD_OPT_TRACE_TIGHT_TLAS - same rule, same
+ * padding, same test of inv_transform and of finiteness - built by the LBVH builder for BOTH option values (the agglomerative
+ * chain takes seconds at these sizes): tight_tlas reports 2 and 2n nodes are walked.  One instance that does not qualify and
+ * the accel walks the scene's own top level (tight_fallback_instances counts them) until an update or a refit finds every
+ * instance qualifying again.  Same guarantee as the narrow option: hit flags are the scene's own, distances within 1e-5, which
+ * of two triangles at the same distance is reported may differ.
+ * Memory held with a private top level of n instances: (2n + 1) * 48 B of nodes + 24n B of boxes + the LBVH's work memory
+ * (~36n B: two key and two value arrays, links, arrival words, the sort's table) + 36 B per triangle; the first
+ * vd_trace_accel_refit_dev adds 20 B per node of links and arrival words.
+ * A tight accel is a SNAPSHOT of the instances: after they moved it must be updated or refitted before it is traced.          */
+int vd_trace_prepare_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, VdTraceAccel** out);
+/* Refits the private top level of a prepared scene - narrow (either builder) or wide - to the scene's instance buffer as it is
+ * NOW: new tight boxes into the leaves of the tree as it stands, then the boxes bottom-up; the TOPOLOGY is kept, so the
+ * tree gets worse as the instances drift from where they were when it was built - refit per frame, vd_trace_accel_update_dev
+ * (the rebuild) when the walk has slowed down.  0.03 - 0.25 ms where a rebuild takes 8.6 ms (LBVH, 1 Mi instances) or 182 ms
+ * (agglomerative, 32 768).  BLOCKS like the update (it reads back whether every instance still qualifies; the decline rule
+ * and the way back are the update's).  The links and arrival words of the refit live in the accel (allocated by the first
+ * refit), not in the context: the caller's own vd_tlas_refit_dev at another n disturbs nothing.  VdTraceAccelInfoWide::
+ * refits_since_build counts refits; an update resets it.  An agglomerative tree that was BUILT while some instance did not
+ * qualify is rebuilt instead (its chain may have dropped a cluster).  A no-op returning VD_OK without a private top level.   */
+int vd_trace_accel_refit_dev(VdCtx* ctx, VdTraceAccel* accel);
+/* vd_trace_accel_info for a handle made by vd_trace_prepare_wide_dev.  Each of the two answers VD_ERR_INVALID_ARG for a handle
+ * of the other kind, with a message that names the other function (vd_last_error of the context that prepared the handle).  */
+typedef struct VdTraceAccelInfoWide {
+    uint32_t tight_tlas /* 0: the scene's own top level is walked; 2: the private LBVH */, n_tlas_nodes, tight_fallback_instances, refits_since_build;
+    uint64_t triangle_bytes;
+    const VdTlasNodeWide* d_tlas_nodes;
+} VdTraceAccelInfoWide;
+int vd_trace_accel_info_wide(const VdTraceAccel* accel, VdTraceAccelInfoWide* out);
 
 /* Occlusion query: d_out_hit[i] = traverse_tlas(ray i).hit, which is all the
  * reference's shadow pass reads (src/bin/raytraced_shadows.wgsl:97-102).  Same walk as vd_trace

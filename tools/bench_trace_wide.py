@@ -10,6 +10,16 @@
       (synth.instances defaults), and the per-call record cost there: a call of 64 rays that look away from the scene - they miss
       the root's box, so the call is its records and its launches.
 
+Prepared wide scenes and the accel refit (results: profiles/trace_wide_prepared.md):
+
+  (p) the scenes of (c) under (a) the plain vd_trace_wide_dev over the LBVH of the reference's boxes - the baseline, twice per
+      repetition: the difference of the two is the spread -, (b) the prepared accel with VD_OPT_TRACE_TIGHT_TLAS off and (c) the
+      prepared accel with its private tight top level; closest hit and any hit.  --big-reps: repetitions at --big (a baseline call
+      there takes seconds);
+  (d) vd_trace_accel_update_dev (rebuild) against vd_trace_accel_refit_dev on those accels, and at 32 768 instances on narrow accels
+      of both builders;
+  (e) the stress scene of (b): narrow tight (both builders) against wide tight over the same instances.
+
 Device events (torch, on the context's stream), warm-up, medians of --reps (>= 30) with the compared forms alternating inside each
 repetition.  One JSON line per measurement on stdout; --out FILE keeps them."""
 import argparse
@@ -54,7 +64,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--exact-reps", type=int, default=5, help="repetitions of the exact builds (hundreds of ms each)")
     ap.add_argument("--big", type=int, default=1 << 20, help="the largest instance count of (a) and (c)")
-    ap.add_argument("--legs", default="abc", help="which of (a), (b), (c) to run; r = of (c) only the per-call records")
+    ap.add_argument("--big-reps", type=int, default=30, help="repetitions of (p) at --big instances")
+    ap.add_argument("--legs", default="abc", help="which of (a), (b), (c), (p), (d), (e) to run; r = of (c) only the per-call records")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     ctx = Context(0)
@@ -93,6 +104,12 @@ def main():
         leg_b(ctx, args, emit)
     if "c" in args.legs or "r" in args.legs:
         leg_c(ctx, args, emit, records_only="c" not in args.legs)
+    if "p" in args.legs or "d" in args.legs:
+        leg_p(ctx, args, emit)
+    if "d" in args.legs:
+        leg_d_narrow(ctx, args, emit)
+    if "e" in args.legs:
+        leg_e(ctx, args, emit)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
@@ -179,6 +196,125 @@ def leg_c(ctx, args, emit, records_only=False):
                  min_ms=round(lo, 4), max_ms=round(hi, 4), Mrays_per_s=None if "64" in k else round(len(rays_c) / med / 1e3, 1),
                  hit_share=hit_share, reps=args.reps)
         del ds, d_i, d_w
+    ctx.set_option("trace.fan", None)
+
+
+def prepare(ctx, ds, tight):
+    ctx.set_option("trace.tight_tlas", tight)
+    acc = ctx.trace_prepare(ds)
+    ctx.set_option("trace.tight_tlas", None)
+    return acc
+
+
+def leg_p(ctx, args, emit):
+    """(p) and the wide half of (d): the scenes of leg_c."""
+    n_rays = 1 << 20
+    d_h = [ctx.empty(n_rays * 16) for _ in range(3)]
+    d_a = [torch.zeros(n_rays, dtype=torch.int32, device="cuda") for _ in range(3)]
+    ctx.set_option("trace.fan", 3)
+    sv, si = synth.knot_mesh(64, 16)
+    nodes_s, idx_s = ctx.bvh_build(sv, si)
+    infos_s = np.zeros(1, dtype=abi.MESH_INFO)
+    infos_s[0]["min"], infos_s[0]["max"] = synth.mesh_bounds(sv)
+    infos_s[0]["index_count"] = len(idx_s)
+    d_ms = ctx.upload(infos_s)
+    rays_c = synth.primary_rays(synth.camera_uniform(eye=(0, 2.5, 1500), pitch_deg=0), 1024, 1024)
+    d_rc = ctx.upload(rays_c)
+    for n in sorted({65536, args.big}):
+        inst = synth.instances(n, n_mesh=1, seed=synth.SEED_BASE + 9)          # the bench cloud's placement: the defaults
+        d_i = ctx.upload(inst)
+        d_w = ctx.empty((2 * n + 1) * 48)
+        ctx.tlas_build_lbvh_dev(d_i, n, d_ms, 1, d_w, wide=True)
+        torch.cuda.synchronize()
+        wide = d_w.cpu().numpy()[: (2 * n + 1) * 48].view(abi.TLAS_NODE_WIDE)
+        ds = ctx.device_scene((wide, inst, infos_s, nodes_s, sv, idx_s))
+        exact, tight = prepare(ctx, ds, 0), prepare(ctx, ds, 2)
+        info = tight.info()
+        assert info["tight_tlas"] == 2 and info["n_tlas_nodes"] == 2 * n, info
+        reps = args.reps if n <= 65536 else args.big_reps
+        if "p" in args.legs:
+            res = alternate({"a_plain_closest": lambda: ctx.trace_wide_dev(ds, d_rc, n_rays, d_h[0]),
+                             "b_prepared_exact_closest": lambda: ctx.trace_prepared_dev(exact, d_rc, n_rays, d_h[1]),
+                             "c_prepared_tight_closest": lambda: ctx.trace_prepared_dev(tight, d_rc, n_rays, d_h[2]),
+                             "a_plain_closest_again": lambda: ctx.trace_wide_dev(ds, d_rc, n_rays, d_h[0]),
+                             "a_plain_any": lambda: ctx.trace_any_wide_dev(ds, d_rc, n_rays, d_a[0]),
+                             "b_prepared_exact_any": lambda: ctx.trace_any_prepared_dev(exact, d_rc, n_rays, d_a[1]),
+                             "c_prepared_tight_any": lambda: ctx.trace_any_prepared_dev(tight, d_rc, n_rays, d_a[2]),
+                             "a_plain_any_again": lambda: ctx.trace_any_wide_dev(ds, d_rc, n_rays, d_a[0])}, reps, min(args.warmup, reps))
+            torch.cuda.synchronize()
+            h = [x.cpu().numpy()[: n_rays * 16].view(abi.HIT) for x in d_h]
+            hit = h[0]["hit"] == 1
+            check = {"b_same_bytes_as_a": h[0].tobytes() == h[1].tobytes() and bool((d_a[0] == d_a[1]).all().item()),
+                     "c_same_hit_flags": bool((h[0]["hit"] == h[2]["hit"]).all()) and bool((d_a[0] == d_a[2]).all().item()),
+                     "c_dist_not_bit_equal": int((h[0]["dist"][hit].view(np.uint32) != h[2]["dist"][hit].view(np.uint32)).sum()),
+                     "hit_share": round(float(hit.mean()), 3)}
+            for k, (med, lo, hi) in res.items():
+                emit(leg="p", n_instances=n, form=k, n_rays=n_rays, median_ms=round(med, 4), min_ms=round(lo, 4), max_ms=round(hi, 4),
+                     Mrays_per_s=round(n_rays / med / 1e3, 2), reps=reps, **check)
+        if "d" in args.legs:
+            res = alternate({"update_rebuild": tight.update, "refit": tight.refit, "refit_again": tight.refit}, args.reps, args.warmup)
+            for k, (med, lo, hi) in res.items():
+                emit(leg="d", accel="wide lbvh", n_instances=n, form=k, median_ms=round(med, 4), min_ms=round(lo, 4), max_ms=round(hi, 4), reps=args.reps)
+        exact.close(); tight.close()
+        del ds, d_i, d_w
+    ctx.set_option("trace.fan", None)
+
+
+def leg_d_narrow(ctx, args, emit):
+    """(d) at 32 768 instances (32 767 for the LBVH: 2n must fit 16 bits) on narrow accels of both builders."""
+    sv, si = synth.knot_mesh(64, 16)
+    nodes_s, idx_s = ctx.bvh_build(sv, si)
+    infos_s = np.zeros(1, dtype=abi.MESH_INFO)
+    infos_s[0]["min"], infos_s[0]["max"] = synth.mesh_bounds(sv)
+    infos_s[0]["index_count"] = len(idx_s)
+    for mode, n in ((1, 32768), (2, 32767)):
+        inst = synth.instances(n, n_mesh=1, seed=synth.SEED_BASE + 9)
+        tl = ctx.tlas_build_lbvh(inst, infos_s)                                 # the scene's own top level is not what is measured
+        ds = ctx.device_scene((tl, inst, infos_s, nodes_s, sv, idx_s))
+        acc = prepare(ctx, ds, mode)
+        assert acc.info()["tight_tlas"] == mode, acc.info()
+        reps = args.exact_reps if mode == 1 else args.reps
+        res = alternate({"update_rebuild": acc.update, "refit": acc.refit, "refit_again": acc.refit}, reps, 1 if mode == 1 else args.warmup)
+        for k, (med, lo, hi) in res.items():
+            emit(leg="d", accel="narrow agglomerative" if mode == 1 else "narrow lbvh", n_instances=n, form=k, median_ms=round(med, 4),
+                 min_ms=round(lo, 4), max_ms=round(hi, 4), reps=reps)
+        acc.close()
+
+
+def leg_e(ctx, args, emit):
+    """(e) the stress scene: narrow tight (agglomerative, LBVH) against wide tight (LBVH) over the same instances."""
+    tv, ti = synth.knot_mesh(512, 128)
+    nodes_b, idx_b = ctx.bvh_build(tv, ti)
+    infos = np.zeros(1, dtype=abi.MESH_INFO)
+    infos[0]["min"], infos[0]["max"] = synth.mesh_bounds(tv)
+    infos[0]["index_count"] = len(idx_b)
+    inst_t = synth.instances(2000, n_mesh=1, seed=synth.SEED_BASE + 8, extent=120.0, scale_range=(0.5, 2.0))
+    tl = ctx.tlas_build(inst_t, infos)
+    rays = synth.primary_rays(synth.camera_uniform(eye=(0, 2.5, 90), pitch_deg=0), 1024, 1024)
+    n_rays = len(rays)
+    d_rays = ctx.upload(rays)
+    ds_n = ctx.device_scene((tl, inst_t, infos, nodes_b, tv, idx_b))
+    ds_w = ctx.device_scene((widen(tl), inst_t, infos, nodes_b, tv, idx_b))
+    accs = {"narrow_agglomerative": prepare(ctx, ds_n, 1), "narrow_lbvh": prepare(ctx, ds_n, 2), "wide_lbvh": prepare(ctx, ds_w, 2),
+            "narrow_exact": prepare(ctx, ds_n, 0)}
+    d_h = {k: ctx.empty(n_rays * 16) for k in accs}
+    d_a = {k: torch.zeros(n_rays, dtype=torch.int32, device="cuda") for k in accs}
+    ctx.set_option("trace.fan", 3)
+    forms = {}
+    for k, acc in accs.items():
+        forms[k + "_closest"] = (lambda acc=acc, k=k: ctx.trace_prepared_dev(acc, d_rays, n_rays, d_h[k]))
+    forms["narrow_lbvh_closest_again"] = lambda: ctx.trace_prepared_dev(accs["narrow_lbvh"], d_rays, n_rays, d_h["narrow_lbvh"])
+    for k, acc in accs.items():
+        forms[k + "_any"] = (lambda acc=acc, k=k: ctx.trace_any_prepared_dev(acc, d_rays, n_rays, d_a[k]))
+    forms["narrow_lbvh_any_again"] = lambda: ctx.trace_any_prepared_dev(accs["narrow_lbvh"], d_rays, n_rays, d_a["narrow_lbvh"])
+    res = alternate(forms, args.reps, args.warmup)
+    torch.cuda.synchronize()
+    same = d_h["narrow_lbvh"].cpu().numpy()[: n_rays * 16].tobytes() == d_h["wide_lbvh"].cpu().numpy()[: n_rays * 16].tobytes()
+    for k, (med, lo, hi) in res.items():
+        emit(leg="e", scene="stress: 2000 instances x 131k-triangle knot", form=k, n_rays=n_rays, median_ms=round(med, 4), min_ms=round(lo, 4),
+             max_ms=round(hi, 4), Mrays_per_s=round(n_rays / med / 1e3, 1), reps=args.reps, same_bytes_narrow_lbvh_vs_wide_lbvh=same)
+    for acc in accs.values():
+        acc.close()
     ctx.set_option("trace.fan", None)
 
 

@@ -135,6 +135,12 @@ class TraceAccelInfo(C.Structure):
                 ("triangle_bytes", C.c_uint64), ("d_tlas_nodes", C.c_void_p)]
 
 
+class TraceAccelInfoWide(C.Structure):
+    """VdTraceAccelInfoWide (include/voidin_abi.h): the info of an accel made by vd_trace_prepare_wide_dev."""
+    _fields_ = [("tight_tlas", C.c_uint32), ("n_tlas_nodes", C.c_uint32), ("tight_fallback_instances", C.c_uint32), ("refits_since_build", C.c_uint32),
+                ("triangle_bytes", C.c_uint64), ("d_tlas_nodes", C.c_void_p)]
+
+
 class BvhBatchItem(C.Structure):
     """VdBvhBatchItem (include/voidin_abi.h, "Batched BLAS build")."""
     _fields_ = [("verts_xyz", C.c_void_p), ("indices_inout", C.c_void_p), ("out_nodes", C.c_void_p),
@@ -220,9 +226,12 @@ PROTOTYPES = {
     "vd_host_callback_async": (_I, [_P, C.CFUNCTYPE(None, C.c_void_p), _P]),
     "vd_trace_any_dev": (_I, [_P, C.POINTER(TraceScene), _P, _U, _P]),
     "vd_trace_prepare_dev": (_I, [_P, C.POINTER(TraceScene), C.POINTER(_P)]),
+    "vd_trace_prepare_wide_dev": (_I, [_P, C.POINTER(TraceSceneWide), C.POINTER(_P)]),
     "vd_trace_release": (_I, [_P, _P]),
     "vd_trace_accel_info": (_I, [_P, _P]),
+    "vd_trace_accel_info_wide": (_I, [_P, _P]),
     "vd_trace_accel_update_dev": (_I, [_P, _P]),
+    "vd_trace_accel_refit_dev": (_I, [_P, _P]),
     "vd_trace_accel_update_geometry_dev": (_I, [_P, _P]),
     "vd_trace_prepared_dev": (_I, [_P, _P, _P, _U, _P]),
     "vd_trace_any_prepared_dev": (_I, [_P, _P, _P, _U, _P]),

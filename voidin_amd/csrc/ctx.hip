@@ -142,7 +142,7 @@ int vd_ctx_destroy(VdCtx* ctx) {
     if (ctx->expand_state) (void)hipFree(ctx->expand_state);
     if (ctx->trace_ovf) (void)hipFree(ctx->trace_ovf);
     if (ctx->trace_deep) (void)hipFree(ctx->trace_deep);
-    if (ctx->refit_state) (void)hipFree(ctx->refit_state);
+    if (ctx->refit.state) (void)hipFree(ctx->refit.state);
     if (ctx->trace_wide) (void)hipFree(ctx->trace_wide);
     if (ctx->lbvh_state) (void)hipFree(ctx->lbvh_state);
     if (ctx->stage_in) (void)hipFree(ctx->stage_in);

@@ -1591,21 +1591,21 @@ int tlas_build_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMe
 
 template <typename Node>
 int tlas_refit_impl(VdCtx* ctx, const VdInstance* d_inst, uint32_t n, const VdMeshInfo* d_meshes, uint32_t n_mesh,
-                    Node* d_nodes) {
+                    Node* d_nodes, VdRefitArena* ar) {
     const size_t total = 2 * (size_t)n + 1;
     const size_t need = 256 + total * 16 + total * 4;
     // The arrival words sit behind the link records, so their offset depends on n: after refits at n1 a refit at another
     // n in the same arena would read old arrival words (values up to 4 / 6 = plausible small epochs) as link records.
     // A change of n therefore starts the arena over, like a reallocation or an epoch wrap does.
-    if (need > ctx->refit_state_bytes || !ctx->refit_state || ctx->refit_epoch == 0xffffffffu || n != ctx->refit_n) {
-        int rc = vd_ensure(ctx, &ctx->refit_state, &ctx->refit_state_bytes, need);
+    if (need > ar->bytes || !ar->state || ar->epoch == 0xffffffffu || n != ar->n) {
+        int rc = vd_ensure(ctx, &ar->state, &ar->bytes, need);
         if (rc) return rc;
-        VD_HIP_CHECK(ctx, hipMemsetAsync(ctx->refit_state, 0, ctx->refit_state_bytes, ctx->stream));   // epoch 0 = never written
-        ctx->refit_epoch = 0u;
-        ctx->refit_n = n;
+        VD_HIP_CHECK(ctx, hipMemsetAsync(ar->state, 0, ar->bytes, ctx->stream));   // epoch 0 = never written
+        ar->epoch = 0u;
+        ar->n = n;
     }
-    const unsigned epoch = ++ctx->refit_epoch;
-    char* base = reinterpret_cast<char*>(ctx->refit_state);
+    const unsigned epoch = ++ar->epoch;
+    char* base = reinterpret_cast<char*>(ar->state);
     RefitRoot* root = reinterpret_cast<RefitRoot*>(base);
     uint4* parent = reinterpret_cast<uint4*>(base + 256);                      // {parent, sibling, epoch} per node
     unsigned* arrivals = reinterpret_cast<unsigned*>(parent + total);
@@ -1639,7 +1639,11 @@ int tlas_entry(VdCtx* ctx, const VdInstance* inst, uint32_t n, const VdMeshInfo*
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     int rc = check_args(ctx, inst, n, meshes, n_mesh, nodes, std::is_same<Node, VdTlasNodeWide>::value, OP == kLbvh);
     if (rc) return rc;
-    constexpr auto run = OP == kExact ? tlas_build_impl<Node> : OP == kRefit ? tlas_refit_impl<Node> : tlas_lbvh_impl<Node>;
+    auto run = [](VdCtx* c, const VdInstance* d_inst, uint32_t count, const VdMeshInfo* d_meshes, uint32_t count_mesh, Node* d_nodes) {
+        if constexpr (OP == kExact) return tlas_build_impl<Node>(c, d_inst, count, d_meshes, count_mesh, d_nodes);
+        else if constexpr (OP == kRefit) return tlas_refit_impl<Node>(c, d_inst, count, d_meshes, count_mesh, d_nodes, &c->refit);
+        else return tlas_lbvh_impl<Node>(c, d_inst, count, d_meshes, count_mesh, d_nodes);
+    };
     if constexpr (!HOST) {
         ctx->fan_forget(nodes);
         return run(ctx, inst, n, meshes, n_mesh, nodes);
@@ -1666,6 +1670,18 @@ size_t vd_lbvh_work_bytes(uint32_t n) {
 int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes, void* work) {
     if (!ctx || !d_boxes || !d_nodes || !work || n == 0 || n > VD_TLAS_MAX_INSTANCES) return VD_ERR_INVALID_ARG;
     return lbvh_from_boxes<VdTlasNode>(ctx, d_boxes, n, d_nodes, work);
+}
+
+int vd_tlas_lbvh_from_boxes_wide(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNodeWide* d_nodes, void* work) {
+    if (!ctx || !d_boxes || !d_nodes || !work || n == 0 || n > VD_TLAS_WIDE_MAX_INSTANCES) return VD_ERR_INVALID_ARG;
+    return lbvh_from_boxes<VdTlasNodeWide>(ctx, d_boxes, n, d_nodes, work);
+}
+// internal (vd_common.hpp): tlas_refit_impl with n_mesh == 0 - leaf_box then reads ready boxes
+int vd_tlas_refit_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* d_nodes, bool wide, VdRefitArena* arena) {
+    if (!ctx || !d_boxes || !d_nodes || !arena || n == 0 || n > (wide ? VD_TLAS_WIDE_MAX_INSTANCES : VD_TLAS_MAX_INSTANCES)) return VD_ERR_INVALID_ARG;
+    const VdInstance* as_inst = reinterpret_cast<const VdInstance*>(d_boxes);
+    return wide ? tlas_refit_impl<VdTlasNodeWide>(ctx, as_inst, n, nullptr, 0u, static_cast<VdTlasNodeWide*>(d_nodes), arena)
+                : tlas_refit_impl<VdTlasNode>(ctx, as_inst, n, nullptr, 0u, static_cast<VdTlasNode*>(d_nodes), arena);
 }
 
 extern "C" {

@@ -13,20 +13,32 @@
 #include "vd_common.hpp"
 
 #include <algorithm>
+#include <cstddef>
 #include <new>
 #include <type_traits>
 
 // vd_trace_prepare_dev: per-scene data derived once from the six trace buffers.  The triangle copy follows the scene's
 // vertex buffer through vd_trace_accel_update_geometry_dev (a mesh deformed: same indices and meshes, new positions), which
 // re-runs the de-indexing into the same array without validating or reading anything back.
+// vd_trace_prepare_wide_dev makes the same handle over a VdTraceSceneWide (`wide`): the two scene structs differ in the node type
+// their first pointer names and in nothing else, so the accel keeps one copy, typed by `wide` (accel_scene<WIDE>), and its node
+// pointers as void*.
 struct VdTraceAccel {
-    VdTraceScene scene; float* tris = nullptr;
+    union { VdTraceScene scene; VdTraceSceneWide wscene; };
+    bool wide = false; float* tris = nullptr;
     // private top level (VD_OPT_TRACE_TIGHT_TLAS): its nodes, which builder made it (1 agglomerative, 2 LBVH), the scene's own top
     // level (what the walk goes back to when an update finds an instance that does not qualify), work memory of the builders
-    VdTlasNode* tight = nullptr; unsigned tight_mode = 0, tight_fallbacks = 0;
-    const VdTlasNode* user_tlas = nullptr; unsigned user_n_nodes = 0;
+    void* tight = nullptr; unsigned tight_mode = 0, tight_fallbacks = 0;
+    const void* user_tlas = nullptr; unsigned user_n_nodes = 0;
     float* boxes = nullptr; unsigned* lbvh = nullptr;
+    // vd_trace_accel_refit_dev: its links and arrival words (allocated by the first refit), refits since the tree was built, and
+    // how many instances did not qualify when it was BUILT (the agglomerative chain drops a cluster it finds no partner for)
+    VdRefitArena refit; unsigned refits = 0, built_fallbacks = 0;
+    VdCtx* owner = nullptr;      // the context that prepared it: where the info calls, which take none, leave their message
+    VdTraceAccel() : scene{} {}
 };
+static_assert(sizeof(VdTraceScene) == sizeof(VdTraceSceneWide) && offsetof(VdTraceScene, instances) == offsetof(VdTraceSceneWide, instances) &&
+              offsetof(VdTraceScene, n_indices) == offsetof(VdTraceSceneWide, n_indices), "one layout, two node types");
 
 namespace {
 
@@ -978,12 +990,10 @@ __global__ __launch_bounds__(256) void prepare_tris_kernel(const VdMeshInfo* __r
 // whose inverse is stale lie outside its box, so whether the reference finds them depends on its visit order, and a
 // top level with non-finite boxes may have dropped clusters (tlas.rs:87-105 finds no partner for a NaN area) that only
 // the reference's own build reproduces.
-__global__ __launch_bounds__(256) void tight_boxes_kernel(const VdInstance* __restrict__ inst, unsigned n_inst, const VdMeshInfo* __restrict__ meshes,
-                                                          unsigned n_meshes, const VdBvhNode* __restrict__ bvh, unsigned n_bvh,
-                                                          const VdTlasNode* __restrict__ scene_tlas, unsigned n_scene_nodes,
-                                                          float* __restrict__ boxes, unsigned* __restrict__ n_fallback) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_inst) return;
+
+// One instance's tight box, or false (mn / mx then hold nothing): the rule above, for both node types.
+__device__ __forceinline__ bool tight_box(const VdInstance* __restrict__ inst, unsigned i, const VdMeshInfo* __restrict__ meshes, unsigned n_meshes,
+                                          const VdBvhNode* __restrict__ bvh, unsigned n_bvh, float (&mn)[3], float (&mx)[3]) {
     const float* T = inst[i].transform;
     const float* V = inst[i].inv_transform;
     const VdMeshInfo m = meshes[min(inst[i].mesh, n_meshes - 1u)];
@@ -999,7 +1009,7 @@ __global__ __launch_bounds__(256) void tight_boxes_kernel(const VdInstance* __re
             worst = fmaxf(worst, e);
         }
     ok = ok && worst <= 1e-3f;                 // false for NaN too
-    float mn[3] = {3e38f, 3e38f, 3e38f}, mx[3] = {-3e38f, -3e38f, -3e38f};
+    for (int k = 0; k < 3; ++k) { mn[k] = 3e38f; mx[k] = -3e38f; }
     float dev[3] = {0.0f, 0.0f, 0.0f};
     if (ok) {
         const VdBvhNode root = bvh[m.bvh_index];
@@ -1026,9 +1036,25 @@ __global__ __launch_bounds__(256) void tight_boxes_kernel(const VdInstance* __re
             const float pad = (2e-5f * big + 1e-30f) + 1.01f * dev[k];        // rounding of ray-in versus corners-out + the inverse's own error
             mn[k] -= pad; mx[k] += pad;
         }
-    } else {
+    }
+    return ok;
+}
+// A scene's own leaf of instance i sits at i + 1 in every top level a vd_tlas_* builder of the narrow layout made: an instance
+// that does not qualify keeps that box.  A WIDE scene's leaves may sit anywhere (voidin_abi.h), so there - and wherever node
+// i + 1 is not that leaf - the box is everything; it is never walked (one such instance makes the accel decline).
+template <typename Node>
+__global__ __launch_bounds__(256) void tight_boxes_kernel(const VdInstance* __restrict__ inst, unsigned n_inst, const VdMeshInfo* __restrict__ meshes,
+                                                          unsigned n_meshes, const VdBvhNode* __restrict__ bvh, unsigned n_bvh,
+                                                          const Node* __restrict__ scene_tlas, unsigned n_scene_nodes,
+                                                          float* __restrict__ boxes, unsigned* __restrict__ n_fallback) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_inst) return;
+    float mn[3], mx[3];
+    if (!tight_box(inst, i, meshes, n_meshes, bvh, n_bvh, mn, mx)) {
         atomicAdd(n_fallback, 1u);
-        const bool own_leaf = i + 1u < n_scene_nodes && scene_tlas[i + 1u].left_right == 0u && scene_tlas[i + 1u].instance_idx == i;
+        bool own_leaf = false;
+        if constexpr (std::is_same<Node, VdTlasNode>::value)
+            own_leaf = i + 1u < n_scene_nodes && scene_tlas[i + 1u].left_right == 0u && scene_tlas[i + 1u].instance_idx == i;
         for (int k = 0; k < 3; ++k) {
             mn[k] = own_leaf ? scene_tlas[i + 1u].min[k] : -1e30f;
             mx[k] = own_leaf ? scene_tlas[i + 1u].max[k] : 1e30f;
@@ -1304,35 +1330,78 @@ int launch_trace(VdCtx* ctx, const SceneOf<WIDE>* sc, const float* d_tris, const
     return VD_OK;
 }
 
-// The private top level of a prepared scene (VD_OPT_TRACE_TIGHT_TLAS: 1 = agglomerative, 2 = LBVH), from the scene's instances as
-// they are now.  Blocks (it reads back how many instances did not qualify); with any, the scene's own top level is walked.
-int build_tight_tlas(VdCtx* ctx, VdTraceAccel* a) {
-    const unsigned n = a->scene.n_instances;
-    hipStream_t st = ctx->stream;
-    unsigned* d_fb = reinterpret_cast<unsigned*>(a->boxes + 6 * (size_t)n);
-    VD_HIP_CHECK(ctx, hipMemsetAsync(d_fb, 0, 4, st));
-    hipLaunchKernelGGL(tight_boxes_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a->scene.instances, n, a->scene.meshes, a->scene.n_meshes,
-                       a->scene.bvh_nodes, a->scene.n_bvh_nodes, a->user_tlas, a->user_n_nodes, a->boxes, d_fb);
-    if (a->tight_mode == 2u) {
-        const int rc = vd_tlas_lbvh_from_boxes(ctx, a->boxes, n, a->tight, a->lbvh);
-        if (rc) return rc;
-    } else {
-        const int rc = vd_tlas_build_from_boxes(ctx, a->boxes, n, a->tight);
-        if (rc) return rc;
-        hipLaunchKernelGGL(tight_root_kernel, dim3(1), dim3(64), 0, st, a->tight, n);
-    }
+// the accel's copy of the scene, as the type its `wide` says
+template <bool WIDE> SceneOf<WIDE>& accel_scene(VdTraceAccel* a) { if constexpr (WIDE) return a->wscene; else return a->scene; }
+template <bool WIDE> const SceneOf<WIDE>& accel_scene(const VdTraceAccel* a) { if constexpr (WIDE) return a->wscene; else return a->scene; }
+
+// New tight boxes from the scene's instances as they are now into a->boxes, the fallback count zeroed before them.
+template <bool WIDE>
+int launch_tight_boxes(VdCtx* ctx, VdTraceAccel* a, unsigned** d_fb) {
+    using Node = std::conditional_t<WIDE, VdTlasNodeWide, VdTlasNode>;
+    const SceneOf<WIDE>& sc = accel_scene<WIDE>(a);
+    const unsigned n = sc.n_instances;
+    *d_fb = reinterpret_cast<unsigned*>(a->boxes + 6 * (size_t)n);
+    VD_HIP_CHECK(ctx, hipMemsetAsync(*d_fb, 0, 4, ctx->stream));
+    hipLaunchKernelGGL((tight_boxes_kernel<Node>), dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, sc.instances, n, sc.meshes, sc.n_meshes,
+                       sc.bvh_nodes, sc.n_bvh_nodes, static_cast<const Node*>(a->user_tlas), a->user_n_nodes, a->boxes, *d_fb);
+    return VD_OK;
+}
+// ... and what follows the build or the refit behind them: the count comes back (blocks), and the accel walks its private top
+// level when every instance qualified, the scene's own otherwise.
+template <bool WIDE>
+int adopt_tight_tlas(VdCtx* ctx, VdTraceAccel* a, const unsigned* d_fb) {
+    using Node = std::conditional_t<WIDE, VdTlasNodeWide, VdTlasNode>;
+    SceneOf<WIDE>& sc = accel_scene<WIDE>(a);
     VD_HIP_CHECK(ctx, hipGetLastError());
     unsigned h_fallback = 0;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_fallback, d_fb, 4, hipMemcpyDeviceToHost, st));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_fallback, d_fb, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     a->tight_fallbacks = h_fallback;
-    if (h_fallback) { a->scene.tlas_nodes = a->user_tlas; a->scene.n_tlas_nodes = a->user_n_nodes; }      // declined: the reference's visit order is the only exact one here
-    else { a->scene.tlas_nodes = a->tight; a->scene.n_tlas_nodes = a->tight_mode == 2u ? 2u * n : 2u * n + 1u; }
+    if (h_fallback) { sc.tlas_nodes = static_cast<const Node*>(a->user_tlas); sc.n_tlas_nodes = a->user_n_nodes; }      // declined: the reference's visit order is the only exact one here
+    else { sc.tlas_nodes = static_cast<const Node*>(a->tight); sc.n_tlas_nodes = a->tight_mode == 2u ? 2u * sc.n_instances : 2u * sc.n_instances + 1u; }
+    return VD_OK;
+}
+
+// The private top level of a prepared scene (VD_OPT_TRACE_TIGHT_TLAS: 1 = agglomerative, 2 = LBVH; WIDE: always the LBVH), from the
+// scene's instances as they are now.  Blocks (it reads back how many instances did not qualify); with any, the scene's own top level is walked.
+template <bool WIDE>
+int build_tight_tlas(VdCtx* ctx, VdTraceAccel* a) {
+    const unsigned n = accel_scene<WIDE>(a).n_instances;
+    unsigned* d_fb = nullptr;
+    int rc = launch_tight_boxes<WIDE>(ctx, a, &d_fb);
+    if (rc) return rc;
+    if constexpr (WIDE) {
+        if ((rc = vd_tlas_lbvh_from_boxes_wide(ctx, a->boxes, n, static_cast<VdTlasNodeWide*>(a->tight), a->lbvh))) return rc;
+    } else if (a->tight_mode == 2u) {
+        if ((rc = vd_tlas_lbvh_from_boxes(ctx, a->boxes, n, static_cast<VdTlasNode*>(a->tight), a->lbvh))) return rc;
+    } else {
+        if ((rc = vd_tlas_build_from_boxes(ctx, a->boxes, n, static_cast<VdTlasNode*>(a->tight)))) return rc;
+        hipLaunchKernelGGL(tight_root_kernel, dim3(1), dim3(64), 0, ctx->stream, static_cast<VdTlasNode*>(a->tight), n);
+    }
+    if ((rc = adopt_tight_tlas<WIDE>(ctx, a, d_fb))) return rc;
+    a->refits = 0u;
+    a->built_fallbacks = a->tight_fallbacks;
+    return VD_OK;
+}
+
+// vd_trace_accel_refit_dev: new tight boxes into the leaves of the private tree as it stands, boxes bottom-up, same topology.
+// A tree the AGGLOMERATIVE builder made while an instance did not qualify is rebuilt instead: that instance's box may have been
+// everything, and the chain drops a cluster whose unions all reach 1e30 (tlas.hip, refit) - its tree cannot carry the scene.
+template <bool WIDE>
+int refit_tight_tlas(VdCtx* ctx, VdTraceAccel* a) {
+    if (a->tight_mode == 1u && a->built_fallbacks) return build_tight_tlas<WIDE>(ctx, a);
+    unsigned* d_fb = nullptr;
+    int rc = launch_tight_boxes<WIDE>(ctx, a, &d_fb);
+    if (rc) return rc;
+    if ((rc = vd_tlas_refit_from_boxes(ctx, a->boxes, accel_scene<WIDE>(a).n_instances, a->tight, WIDE, &a->refit))) return rc;
+    if ((rc = adopt_tight_tlas<WIDE>(ctx, a, d_fb))) return rc;
+    ++a->refits;
     return VD_OK;
 }
 
 // de-index every mesh's leaves into `tris`; gridDim.y carries the mesh: 65 535 per launch
-void launch_prepare_tris(VdCtx* ctx, const VdTraceScene& s, float* tris, unsigned* err) {
+template <typename S>
+void launch_prepare_tris(VdCtx* ctx, const S& s, float* tris, unsigned* err) {
     for (unsigned m0 = 0; m0 < s.n_meshes; m0 += 65535u)
         hipLaunchKernelGGL(prepare_tris_kernel, dim3(256, std::min(s.n_meshes - m0, 65535u)), dim3(256), 0, ctx->stream, s.meshes + m0,
                            s.vertices, s.indices, s.n_indices, s.n_vertices, tris, err);
@@ -1345,6 +1414,7 @@ void accel_free(VdCtx* ctx, VdTraceAccel* a) {
     if (a->tight) (void)hipFree(a->tight);
     if (a->boxes) (void)hipFree(a->boxes);
     if (a->lbvh) (void)hipFree(a->lbvh);
+    if (a->refit.state) (void)hipFree(a->refit.state);
     delete a;
 }
 
@@ -1355,6 +1425,61 @@ int fail_named(VdCtx* ctx, const char* name, const char* text) {
 template <typename S> bool scene_ok(const S* s) {
     return s && s->tlas_nodes && s->instances && s->meshes && s->bvh_nodes && s->vertices && s->indices && s->n_meshes &&
            s->n_tlas_nodes && s->n_instances;
+}
+
+// vd_trace_prepare_dev / vd_trace_prepare_wide_dev: validate, de-index every leaf (no triangle limit), and - with
+// VD_OPT_TRACE_TIGHT_TLAS and an instance count the builder takes - the private top level.  Blocks.  Nothing is left behind on failure.
+template <bool WIDE>
+int trace_prepare(VdCtx* ctx, const SceneOf<WIDE>* d_scene, VdTraceAccel** out) {
+    using Node = std::conditional_t<WIDE, VdTlasNodeWide, VdTlasNode>;
+    constexpr const char* name = WIDE ? "vd_trace_prepare_wide" : "vd_trace_prepare";
+    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
+    if (!ctx || !out) return VD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!scene_ok(d_scene) || d_scene->n_indices == 0u || d_scene->n_vertices == 0u) return fail_named(ctx, name, "incomplete scene");
+    if (WIDE && d_scene->n_tlas_nodes > 2u * VD_TLAS_WIDE_MAX_INSTANCES + 1u)
+        return fail_named(ctx, name, "more than 2 * VD_TLAS_WIDE_MAX_INSTANCES + 1 top-level nodes");
+    VdTraceAccel* a = new (std::nothrow) VdTraceAccel();
+    if (!a) return VD_ERR_OOM;
+    a->wide = WIDE; a->owner = ctx;
+    if constexpr (WIDE) a->wscene = *d_scene; else a->scene = *d_scene;
+    const size_t n_tri = d_scene->n_indices / 3u;
+    auto oom = [&](const char* what) { accel_free(ctx, a); snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what); return VD_ERR_OOM; };
+    if (hipMalloc(reinterpret_cast<void**>(&a->tris), 36 * n_tri + 64) != hipSuccess) { a->tris = nullptr; (void)hipGetLastError(); return oom("triangle array"); }
+    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, 256);
+    if (rc) { accel_free(ctx, a); return rc; }
+    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
+    (void)hipMemsetAsync(d_flag, 0, 4, ctx->stream);
+    (void)hipMemsetAsync(a->tris, 0, 36 * n_tri + 64, ctx->stream);      // index ranges no mesh covers
+    launch_prepare_tris(ctx, *d_scene, a->tris, d_flag);
+    hipError_t e = hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess || ctx->host_pinned[0]) {
+        accel_free(ctx, a);
+        if (e != hipSuccess) VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
+        return fail_named(ctx, name, "a mesh's index range or a vertex index lies outside the scene's buffers");
+    }
+    a->user_tlas = d_scene->tlas_nodes; a->user_n_nodes = d_scene->n_tlas_nodes;
+    const long long tight = ctx->option(VD_OPT_TRACE_TIGHT_TLAS, 0);
+    const unsigned n = d_scene->n_instances;
+    const unsigned n_max = WIDE ? VD_TLAS_WIDE_MAX_INSTANCES : (tight == 2 ? VD_TLAS_MAX_INSTANCES - 1u : VD_TLAS_MAX_INSTANCES);
+    if (tight != 0 && n >= 2u && n <= n_max) {
+        a->tight_mode = WIDE || tight == 2 ? 2u : 1u;      // wide: the agglomerative chain takes seconds at these sizes
+        const size_t lbvh_bytes = vd_lbvh_work_bytes(n);
+        bool good = hipMalloc(reinterpret_cast<void**>(&a->boxes), 24 * (size_t)n + 16) == hipSuccess &&       // (not in the context's scratch: the agglomerative builder lays that out for itself)
+                    hipMalloc(&a->tight, sizeof(Node) * (2 * (size_t)n + 1)) == hipSuccess &&
+                    (a->tight_mode != 2u || hipMalloc(reinterpret_cast<void**>(&a->lbvh), lbvh_bytes) == hipSuccess);
+        if (good) good = hipMemsetAsync(a->tight, 0, sizeof(Node) * (2 * (size_t)n + 1), ctx->stream) == hipSuccess;      // slots a builder leaves unused read as leaves nobody reaches
+        else (void)hipGetLastError();
+        const int rc_t = good ? build_tight_tlas<WIDE>(ctx, a) : VD_ERR_OOM;
+        if (rc_t) {
+            if (rc_t == VD_ERR_OOM) return oom("the private top level (VD_OPT_TRACE_TIGHT_TLAS) could not be allocated");
+            accel_free(ctx, a);
+            return rc_t;
+        }
+    }
+    *out = a;
+    return VD_OK;
 }
 
 // host-pointer form of a trace call: the six buffers and the rays staged in, the records out
@@ -1471,9 +1596,11 @@ int vd_trace_any_dev(VdCtx* ctx, const VdTraceScene* d_scene, const VdRay* d_ray
     return trace_entry<false>(ctx, "vd_trace_any", "incomplete scene", d_scene, nullptr, d_rays, n_rays, nullptr, d_out_hit);
 }
 int vd_trace_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, VdHit* d_out) {
+    if (accel && accel->wide) return trace_entry<true>(ctx, "vd_trace_prepared", "null accel", &accel->wscene, accel->tris, d_rays, n_rays, d_out, nullptr);
     return trace_entry<false>(ctx, "vd_trace_prepared", "null accel", accel ? &accel->scene : nullptr, accel ? accel->tris : nullptr, d_rays, n_rays, d_out, nullptr);
 }
 int vd_trace_any_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const VdRay* d_rays, uint32_t n_rays, uint32_t* d_out_hit) {
+    if (accel && accel->wide) return trace_entry<true>(ctx, "vd_trace_any_prepared", "null accel", &accel->wscene, accel->tris, d_rays, n_rays, nullptr, d_out_hit);
     return trace_entry<false>(ctx, "vd_trace_any_prepared", "null accel", accel ? &accel->scene : nullptr, accel ? accel->tris : nullptr, d_rays, n_rays, nullptr, d_out_hit);
 }
 int vd_trace(VdCtx* ctx, const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out) {
@@ -1489,52 +1616,12 @@ int vd_trace_wide(VdCtx* ctx, const VdTraceSceneWide* scene, const VdRay* rays, 
     return trace_entry<true, true>(ctx, "vd_trace_wide", "incomplete scene", scene, nullptr, rays, n_rays, out, nullptr);
 }
 
-int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel** out) {
-    VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
-    if (!ctx || !out) return VD_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!scene_ok(d_scene) || d_scene->n_indices == 0u || d_scene->n_vertices == 0u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_prepare: incomplete scene");
-    VdTraceAccel* a = new (std::nothrow) VdTraceAccel();
-    if (!a) return VD_ERR_OOM;
-    a->scene = *d_scene;
-    const size_t n_tri = d_scene->n_indices / 3u;
-    if (hipMalloc(reinterpret_cast<void**>(&a->tris), 36 * n_tri + 64) != hipSuccess) { a->tris = nullptr; accel_free(ctx, a); VD_FAIL(ctx, VD_ERR_OOM, "vd_trace_prepare: triangle array"); }
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, 256);
-    if (rc) { accel_free(ctx, a); return rc; }
-    unsigned* d_flag = reinterpret_cast<unsigned*>(ctx->scratch);
-    (void)hipMemsetAsync(d_flag, 0, 4, ctx->stream);
-    (void)hipMemsetAsync(a->tris, 0, 36 * n_tri + 64, ctx->stream);      // index ranges no mesh covers
-    launch_prepare_tris(ctx, *d_scene, a->tris, d_flag);
-    hipError_t e = hipMemcpyAsync(ctx->host_pinned, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess || ctx->host_pinned[0]) {
-        accel_free(ctx, a);
-        if (e != hipSuccess) VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
-        VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_trace_prepare: a mesh's index range or a vertex index lies outside the scene's buffers");
-    }
-    a->user_tlas = d_scene->tlas_nodes; a->user_n_nodes = d_scene->n_tlas_nodes;
-    const long long tight = ctx->option(VD_OPT_TRACE_TIGHT_TLAS, 0);
-    if (tight != 0 && d_scene->n_instances >= 2u && d_scene->n_instances <= (tight == 2 ? VD_TLAS_MAX_INSTANCES - 1u : VD_TLAS_MAX_INSTANCES)) {
-        const unsigned n = d_scene->n_instances;
-        a->tight_mode = tight == 2 ? 2u : 1u;
-        const size_t lbvh_bytes = vd_lbvh_work_bytes(n);
-        bool good = hipMalloc(reinterpret_cast<void**>(&a->boxes), 24 * (size_t)n + 16) == hipSuccess &&       // (not in the context's scratch: the agglomerative builder lays that out for itself)
-                    hipMalloc(reinterpret_cast<void**>(&a->tight), sizeof(VdTlasNode) * (2 * (size_t)n + 1)) == hipSuccess &&
-                    (a->tight_mode != 2u || hipMalloc(reinterpret_cast<void**>(&a->lbvh), lbvh_bytes) == hipSuccess);
-        if (good) good = hipMemsetAsync(a->tight, 0, sizeof(VdTlasNode) * (2 * (size_t)n + 1), ctx->stream) == hipSuccess;      // slots a builder leaves unused read as leaves nobody reaches
-        const int rc_t = good ? build_tight_tlas(ctx, a) : VD_ERR_OOM;
-        if (rc_t) {
-            accel_free(ctx, a);
-            if (rc_t == VD_ERR_OOM) VD_FAIL(ctx, VD_ERR_OOM, "vd_trace_prepare: the private top level (VD_OPT_TRACE_TIGHT_TLAS) could not be allocated");
-            return rc_t;
-        }
-    }
-    *out = a;
-    return VD_OK;
-}
+int vd_trace_prepare_dev(VdCtx* ctx, const VdTraceScene* d_scene, VdTraceAccel** out) { return trace_prepare<false>(ctx, d_scene, out); }
+int vd_trace_prepare_wide_dev(VdCtx* ctx, const VdTraceSceneWide* d_scene, VdTraceAccel** out) { return trace_prepare<true>(ctx, d_scene, out); }
 
 int vd_trace_accel_info(const VdTraceAccel* accel, VdTraceAccelInfo* out) {
     if (!accel || !out) return VD_ERR_INVALID_ARG;
+    if (accel->wide) VD_FAIL(accel->owner, VD_ERR_INVALID_ARG, "vd_trace_accel_info: the accel was made by vd_trace_prepare_wide_dev: use vd_trace_accel_info_wide");
     memset(out, 0, sizeof(*out));
     out->tight_tlas = (accel->tight && accel->scene.tlas_nodes == accel->tight) ? accel->tight_mode : 0u;
     out->n_tlas_nodes = accel->scene.n_tlas_nodes;
@@ -1543,21 +1630,42 @@ int vd_trace_accel_info(const VdTraceAccel* accel, VdTraceAccelInfo* out) {
     out->d_tlas_nodes = accel->scene.tlas_nodes;
     return VD_OK;
 }
+int vd_trace_accel_info_wide(const VdTraceAccel* accel, VdTraceAccelInfoWide* out) {
+    if (!accel || !out) return VD_ERR_INVALID_ARG;
+    if (!accel->wide) VD_FAIL(accel->owner, VD_ERR_INVALID_ARG, "vd_trace_accel_info_wide: the accel was made by vd_trace_prepare_dev: use vd_trace_accel_info");
+    memset(out, 0, sizeof(*out));
+    out->tight_tlas = (accel->tight && accel->wscene.tlas_nodes == accel->tight) ? accel->tight_mode : 0u;
+    out->n_tlas_nodes = accel->wscene.n_tlas_nodes;
+    out->tight_fallback_instances = accel->tight_fallbacks;
+    out->refits_since_build = accel->refits;
+    out->triangle_bytes = 36ull * (accel->wscene.n_indices / 3u);
+    out->d_tlas_nodes = accel->wscene.tlas_nodes;
+    return VD_OK;
+}
 
 int vd_trace_accel_update_dev(VdCtx* ctx, VdTraceAccel* accel) {
     VdDeviceGuard vd_guard_(ctx);
     if (!ctx || !accel) return VD_ERR_INVALID_ARG;
     if (!accel->tight) return VD_OK;          // the scene's own top level is walked: the host refits that one (vd_tlas_refit_dev)
     ctx->fan_forget(accel->tight);
-    return build_tight_tlas(ctx, accel);
+    return accel->wide ? build_tight_tlas<true>(ctx, accel) : build_tight_tlas<false>(ctx, accel);
+}
+
+int vd_trace_accel_refit_dev(VdCtx* ctx, VdTraceAccel* accel) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx || !accel) return VD_ERR_INVALID_ARG;
+    if (!accel->tight) return VD_OK;          // as above
+    ctx->fan_forget(accel->tight);
+    return accel->wide ? refit_tight_tlas<true>(ctx, accel) : refit_tight_tlas<false>(ctx, accel);
 }
 
 int vd_trace_accel_update_geometry_dev(VdCtx* ctx, VdTraceAccel* accel) {
     VdDeviceGuard vd_guard_(ctx);
     if (!ctx || !accel) return VD_ERR_INVALID_ARG;
-    const VdTraceScene& s = accel->scene;
-    unsigned* d_ignored = reinterpret_cast<unsigned*>(accel->tris + 9 * (size_t)(s.n_indices / 3u));      // the array's slack: prepare validated, nobody reads this word
-    launch_prepare_tris(ctx, s, accel->tris, d_ignored);
+    const uint32_t n_indices = accel->wide ? accel->wscene.n_indices : accel->scene.n_indices;
+    unsigned* d_ignored = reinterpret_cast<unsigned*>(accel->tris + 9 * (size_t)(n_indices / 3u));      // the array's slack: prepare validated, nobody reads this word
+    if (accel->wide) launch_prepare_tris(ctx, accel->wscene, accel->tris, d_ignored);
+    else launch_prepare_tris(ctx, accel->scene, accel->tris, d_ignored);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }

@@ -12,6 +12,15 @@
 
 #include "../../include/voidin_abi.h"
 
+// TLAS refit: epoch-tagged {parent, sibling} links + arrival words for ONE instance count at a time (tlas.hip: tlas_refit_impl).
+// The context has one for vd_tlas_refit*; a VdTraceAccel with a private top level has its own (vd_trace_accel_refit_dev), so
+// that the caller's own refits at another n do not start either arena over.
+struct VdRefitArena {
+    void* state = nullptr; size_t bytes = 0;
+    unsigned epoch = 0;                 // tag of the last refit launch (0 = the arena is freshly zeroed)
+    unsigned n = 0;                     // instance count the arena's layout was last used with
+};
+
 struct VdCtx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -40,8 +49,7 @@ struct VdCtx {
     void* trace_deep = nullptr;  size_t trace_deep_bytes = 0;     // traversal, second pass over those rays: their list + stack entries beyond 128 (allocated when first needed)
     void* trace_wide = nullptr;  size_t trace_wide_bytes = 0;     // vd_trace_wide*: the per-call records of a wide top level (64 B per node), mesh records, triangles, fan-out
     void* lbvh_state = nullptr;  size_t lbvh_state_bytes = 0;     // vd_tlas_build_lbvh*: leaf boxes, codes, the sort's tables, parent links, arrival words
-    void* refit_state = nullptr; size_t refit_state_bytes = 0;    // TLAS refit: epoch-tagged {parent, sibling} links + arrival words
-    unsigned refit_epoch = 0;                                     // tag of the last refit launch (0 = the arena is freshly zeroed)
+    VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene
     void fan_forget(const void* tlas) { if (tlas == fan_tlas) { fan_tlas = nullptr; fan_idle_calls = 0; } }   // the top level at this address was rebuilt / refitted / released
@@ -49,7 +57,6 @@ struct VdCtx {
     // (one of the 15 such calls is used up).  fan_remember: what a call that did fan out found.
     bool fan_rest(const void* tlas, unsigned nodes, unsigned inst) { const bool rest = tlas == fan_tlas && nodes == fan_nodes && inst == fan_inst && fan_idle_calls != 0u; if (rest) --fan_idle_calls; return rest; }
     void fan_remember(const void* tlas, unsigned nodes, unsigned inst, bool few_jobs) { fan_tlas = tlas; fan_nodes = nodes; fan_inst = inst; fan_idle_calls = few_jobs ? 15u : 0u; }
-    unsigned refit_n = 0;                                         // instance count the arena's layout was last used with
     unsigned long long scan_launches = 0;
     void* dbg_ptr = nullptr; unsigned dbg_count = 0; void* dbg_ptr2 = nullptr;   // tuning hooks
     void* stage_in = nullptr;    size_t stage_in_bytes = 0;    // host-pointer API staging
@@ -107,6 +114,12 @@ int vd_tlas_build_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTla
 // bytes of device memory, 256-byte aligned) as its work memory.  Enqueues only.  n <= 32 768.
 size_t vd_lbvh_work_bytes(uint32_t n);
 int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes, void* work);
+// ... and into 2n + 1 WIDE nodes: n <= VD_TLAS_WIDE_MAX_INSTANCES.
+int vd_tlas_lbvh_from_boxes_wide(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNodeWide* d_nodes, void* work);
+// tlas.hip: the refit (vd_tlas_refit*) of a top level whose leaves sit at 1..n, from ready leaf boxes (six floats per INSTANCE; leaf
+// j takes the box of its instance_idx): new leaf boxes, then bottom-up, topology kept.  `wide`: d_nodes is VdTlasNodeWide.  The links
+// and arrival words live in `arena` (grown when needed - then it drains the stream first).  Enqueues only otherwise.
+int vd_tlas_refit_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* d_nodes, bool wide, VdRefitArena* arena);
 // Look-back scan state for n_tiles tiles: *ticket = 64-bit {epoch | ticket} word, *states = granules.
 // Zeroed once when (re)allocated; the epoch tags make per-launch clearing unnecessary.
 int vd_scan_scratch(VdCtx* ctx, unsigned n_tiles, unsigned long long** ticket, unsigned long long** states, bool start_timer);

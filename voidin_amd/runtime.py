@@ -478,19 +478,30 @@ class Context:
         self._chk(self.lib.vd_trace_any_dev(self.h, C.byref(scene.struct), abi.ptr(d_rays), n_rays, abi.ptr(d_out_hit)))
 
     class TraceAccel:
-        """vd_trace_prepare_dev: per-scene de-indexed leaf triangles (include/voidin_abi.h); keeps the DeviceScene alive."""
+        """vd_trace_prepare_dev / vd_trace_prepare_wide_dev (by the DeviceScene's node type): per-scene de-indexed leaf triangles
+        and, with trace.tight_tlas, a private top level (include/voidin_abi.h); keeps the DeviceScene alive."""
 
         def __init__(self, ctx: "Context", scene: "Context.DeviceScene"):
-            self.ctx, self.scene = ctx, scene
+            self.ctx, self.scene, self.wide = ctx, scene, scene.wide
             h = C.c_void_p()
-            ctx._chk(ctx.lib.vd_trace_prepare_dev(ctx.h, C.byref(scene.struct), C.byref(h)))
+            prepare = ctx.lib.vd_trace_prepare_wide_dev if scene.wide else ctx.lib.vd_trace_prepare_dev
+            ctx._chk(prepare(ctx.h, C.byref(scene.struct), C.byref(h)))
             self.h = h
 
         def info(self) -> dict:
-            st = abi.TraceAccelInfo()
-            self.ctx._chk(self.ctx.lib.vd_trace_accel_info(self.h, C.byref(st)))
-            return {"tight_tlas": int(st.tight_tlas), "n_tlas_nodes": int(st.n_tlas_nodes), "tight_fallback_instances": int(st.tight_fallback_instances),
-                    "triangle_bytes": int(st.triangle_bytes), "d_tlas_nodes": st.d_tlas_nodes}
+            """vd_trace_accel_info, or vd_trace_accel_info_wide for a wide accel (then with "refits_since_build"); "wide" says which."""
+            st = abi.TraceAccelInfoWide() if self.wide else abi.TraceAccelInfo()
+            fn = self.ctx.lib.vd_trace_accel_info_wide if self.wide else self.ctx.lib.vd_trace_accel_info
+            self.ctx._chk(fn(self.h, C.byref(st)))
+            d = {"tight_tlas": int(st.tight_tlas), "n_tlas_nodes": int(st.n_tlas_nodes), "tight_fallback_instances": int(st.tight_fallback_instances),
+                 "triangle_bytes": int(st.triangle_bytes), "d_tlas_nodes": st.d_tlas_nodes, "wide": self.wide}
+            if self.wide:
+                d["refits_since_build"] = int(st.refits_since_build)
+            return d
+
+        def refit(self):
+            """vd_trace_accel_refit_dev: new tight boxes into the private top level as it stands, topology kept (blocks)."""
+            self.ctx._chk(self.ctx.lib.vd_trace_accel_refit_dev(self.ctx.h, self.h))
 
         def update(self):
             """vd_trace_accel_update_dev: rebuild the private top level from the instance buffer as it is now."""
