@@ -184,6 +184,18 @@ class BvhBuilder {
         bvh.nodes.resize(n_nodes);                                       // `self.nodes.truncate(new_node_index)`
         return bvh;
     }
+    // NEW (voidin_abi.h "LBVH bottom level"): an LBVH over the triangles in the same node layout and numbering - NOT the
+    // reference's tree - built in a fraction of the time: for a mesh whose triangles change every frame.  `indices` is
+    // rewritten in sorted code order.  Every consumer of a Bvh takes it (refit, traverse_iter, the trace entry points).
+    Bvh build_fast() {
+        Bvh bvh;
+        bvh.nodes.resize(2 * n_triangles_ > 2 ? 2 * n_triangles_ : 2);
+        uint32_t n_nodes = 0;
+        gpu_.check(vd_bvh_build_lbvh(gpu_.ctx(), &vertices_->x, (uint32_t)n_vertices_, &indices_->x, (uint32_t)n_triangles_,
+                                     bvh.nodes.data(), (uint32_t)bvh.nodes.size(), &n_nodes));
+        bvh.nodes.resize(n_nodes);
+        return bvh;
+    }
 
    private:
     const Gpu& gpu_;
@@ -252,18 +264,47 @@ class MeshPool {
         const uint32_t vertex_offset = (uint32_t)vertices.size();
         vertices.insert(vertices.end(), mesh.vertices, mesh.vertices + mesh.n_vertices);
         Bvh bvh = BvhBuilder(gpu_, mesh.vertices, mesh.n_vertices, reinterpret_cast<UVec3*>(mesh.indices), mesh.n_indices / 3).build();
-        const uint32_t bvh_index = (uint32_t)bvh_nodes.size();
-        bvh_nodes.insert(bvh_nodes.end(), bvh.nodes.begin(), bvh.nodes.end());
-        const uint32_t base_index = (uint32_t)indices.size();
-        indices.insert(indices.end(), mesh.indices, mesh.indices + mesh.n_indices);
-        MeshInfo info{};
-        calculate_bounds(mesh.vertices, mesh.n_vertices, info);
-        info.index_count = (uint32_t)mesh.n_indices;
-        info.base_index = base_index;
-        info.vertex_offset = (int32_t)vertex_offset;
-        info.bvh_index = bvh_index;
-        mesh_info_cpu.push_back(info);
-        return (uint32_t)mesh_info_cpu.size() - 1;     // MeshId
+        return append(mesh, vertex_offset, bvh, bvh.nodes.size());
+    }
+
+    // NEW (voidin_abi.h "LBVH bottom level"): `add` for a mesh that rebuild_fast will rebuild - the same bookkeeping with the LBVH
+    // builder, and the mesh keeps the full max(2, 2 T) node slots (zero nodes behind its tree), so a rebuild with another
+    // node count fits in place.
+    uint32_t add_fast(MeshRef mesh) {
+        const uint32_t vertex_offset = (uint32_t)vertices.size();
+        vertices.insert(vertices.end(), mesh.vertices, mesh.vertices + mesh.n_vertices);
+        const size_t n_tri = mesh.n_indices / 3;
+        Bvh bvh;
+        try {
+            bvh = BvhBuilder(gpu_, mesh.vertices, mesh.n_vertices, reinterpret_cast<UVec3*>(mesh.indices), n_tri).build_fast();
+        } catch (...) {
+            vertices.resize(vertex_offset);
+            throw;
+        }
+        return append(mesh, vertex_offset, bvh, 2 * n_tri > 2 ? 2 * n_tri : 2);
+    }
+
+    // NEW: the triangles of a mesh added with add_fast changed - same vertex count, same triangle count, other positions and
+    // other indices (fracture, re-triangulation, a streamed LOD of equal size).  The mesh's BLAS is rebuilt in place with the
+    // LBVH builder, the pool's positions and indices are replaced (the indices in sorted code order), MeshInfo.min / max are
+    // refreshed as update_vertices does; every other mesh, and every offset, stays as it is.
+    void rebuild_fast(uint32_t mesh_id, const Vec3* positions, size_t n_positions, const uint32_t* new_indices, size_t n_indices) {
+        if (mesh_id >= mesh_info_cpu.size()) throw Error(VD_ERR_INVALID_ARG, "MeshPool::rebuild_fast: no such mesh");
+        MeshInfo& info = mesh_info_cpu[mesh_id];
+        const bool last = mesh_id + 1 == mesh_info_cpu.size();
+        const size_t v0 = (size_t)info.vertex_offset, v1 = last ? vertices.size() : (size_t)mesh_info_cpu[mesh_id + 1].vertex_offset;
+        const size_t b0 = info.bvh_index, b1 = last ? bvh_nodes.size() : (size_t)mesh_info_cpu[mesh_id + 1].bvh_index;
+        const size_t n_tri = n_indices / 3, room = 2 * n_tri > 2 ? 2 * n_tri : 2;
+        if (n_positions != v1 - v0 || n_indices != info.index_count)
+            throw Error(VD_ERR_INVALID_ARG, "MeshPool::rebuild_fast: vertex or index count differs from the mesh's");
+        if (b1 - b0 < room) throw Error(VD_ERR_INVALID_ARG, "MeshPool::rebuild_fast: the mesh does not hold 2 T node slots (add it with add_fast)");
+        std::vector<uint32_t> idx(new_indices, new_indices + n_indices);
+        Bvh bvh = BvhBuilder(gpu_, positions, n_positions, reinterpret_cast<UVec3*>(idx.data()), n_tri).build_fast();
+        std::copy(bvh.nodes.begin(), bvh.nodes.end(), bvh_nodes.begin() + (std::ptrdiff_t)b0);
+        std::fill(bvh_nodes.begin() + (std::ptrdiff_t)(b0 + bvh.nodes.size()), bvh_nodes.begin() + (std::ptrdiff_t)b1, BvhNode{});
+        std::copy(idx.begin(), idx.end(), indices.begin() + (std::ptrdiff_t)info.base_index);
+        std::copy(positions, positions + n_positions, vertices.begin() + (std::ptrdiff_t)v0);
+        calculate_bounds(positions, n_positions, info);
     }
 
     // MeshPool::add for a whole scene: the same bookkeeping for every mesh, ONE batched BLAS build (vd_bvh_build_batch)
@@ -352,6 +393,23 @@ class MeshPool {
     }
 
    private:
+    // the bookkeeping of MeshPool::add behind the build: nodes (padded with zero nodes to `node_room`), indices, the MeshInfo row
+    uint32_t append(const MeshRef& mesh, uint32_t vertex_offset, const Bvh& bvh, size_t node_room) {
+        const uint32_t bvh_index = (uint32_t)bvh_nodes.size();
+        bvh_nodes.insert(bvh_nodes.end(), bvh.nodes.begin(), bvh.nodes.end());
+        bvh_nodes.resize(bvh_index + (node_room > bvh.nodes.size() ? node_room : bvh.nodes.size()));
+        const uint32_t base_index = (uint32_t)indices.size();
+        indices.insert(indices.end(), mesh.indices, mesh.indices + mesh.n_indices);
+        MeshInfo info{};
+        calculate_bounds(mesh.vertices, mesh.n_vertices, info);
+        info.index_count = (uint32_t)mesh.n_indices;
+        info.base_index = base_index;
+        info.vertex_offset = (int32_t)vertex_offset;
+        info.bvh_index = bvh_index;
+        mesh_info_cpu.push_back(info);
+        return (uint32_t)mesh_info_cpu.size() - 1;     // MeshId
+    }
+
     // calculate_bounds (mesh/mod.rs:22-27): fold from (+inf, -inf), into info.min / info.max
     static void calculate_bounds(const Vec3* positions, size_t n, MeshInfo& info) {
         float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};

@@ -512,6 +512,52 @@ int vd_bvh_build_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
                      uint32_t* d_indices_inout, uint32_t n_tri,
                      VdBvhNode* d_out_nodes, uint32_t node_cap, uint32_t* out_n_nodes /* host */);
 
+/* LBVH bottom level (NEW, NOT the reference's tree): a BLAS for a mesh whose TRIANGLES change every frame - fracture,
+ * procedural geometry, marching cubes, a streamed LOD, a cloth that tears - where vd_bvh_build's chain of dependent
+ * launches and host round trips is too dear and the refit below does not apply.  The array has the reference's BvhNode
+ * layout and node numbering, so every consumer of a BLAS takes it as it is: the WGSL traverse_bvh, vd_trace*,
+ * vd_trace_prepare*, vd_traverse_iter_dev, vd_bvh_refit_plan_dev.  The tree is a function of the input alone:
+ *   box       of a triangle: its three corners folded from (+1e30, -1e30) with the NaN-ignoring min / max of
+ *             calculate_bounds and the refit (tie rule -0 < +0).  A corner whose index is >= n_vert counts as a NaN
+ *             vertex: it is ignored, never read, and counted in n_bad_indices.
+ *   code      the key of vd_tlas_build_lbvh* applied to the triangle boxes: centre 0.5 * (min + max) in float32, 10 bits
+ *             per axis of the extent of the finite centres, x in the highest bit of each triple; a centre with a
+ *             non-finite coordinate gets 0x3fffffff.
+ *   order     stable sort by code (equal codes keep input order); indices_inout is rewritten in that order, whole triples.
+ *   topology  the binary radix tree (Karras 2012) over the 64-bit keys code << 32 | sorted position.  A radix-tree node
+ *             that covers <= 3 sorted positions is a LEAF with left_first = its first position and count = 1..3 (the
+ *             reference's `count <= 3`, blas.rs:106); its radix descendants are not emitted.
+ *   numbering the reference's (blas.rs:105-128): node 0 is the root, slot 1 the never-used all-zero node; an interior
+ *             node has count = 0 and its children at left_first and left_first + 1, a pair allocated when the node is
+ *             subdivided, before anything below it; then the whole left subtree, then the right.  So every child id is
+ *             greater than its parent's, n_nodes = 2 + 2 * (interior nodes) <= max(2, 2 * n_tri), and n_tri <= 3 gives
+ *             n_nodes = 2 with node 0 a leaf.
+ *   boxes     a leaf's is the union of its triangles' boxes, an interior node's the union of its children's:
+ *             vd_bvh_refit(lbvh(x), x) changes no byte.
+ * No byte of out_nodes past n_nodes is written.  The build is TOTAL: there is no VD_ERR_DEGENERATE - duplicate triangles,
+ * collinear centres, NaN and infinite vertices all give a valid tree.
+ *
+ * vd_bvh_build_lbvh_dev ONLY ENQUEUES on the context's stream: no host read-back, and no allocation once the context's
+ * grow-only work memory has reached the size of the largest n_tri (one warm-up call at that size), so it can be captured
+ * into a HIP graph and replayed.  d_result is DEVICE memory, written by the build.  VD_ERR_INVALID_ARG before anything is
+ * launched for: a null pointer, n_tri == 0, n_tri > VD_BVH_LBVH_MAX_TRIANGLES, node_cap < max(2, 2 * n_tri), a d_out_nodes
+ * that is not 16-byte aligned.
+ *   max_depth  edges on the longest path from node 0 to a leaf.  The WGSL traverse_bvh (bvh.wgsl:35-75) pushes the root, and
+ *              for every interior node it enters BOTH children before it pops one, so a ray that enters both children all
+ *              the way down the deepest path holds max_depth + 1 entries.  Its stack (stack.wgsl, STACK_LEN = 24) is
+ *              UNCHECKED: use the tree there only when max_depth <= 23.  An LBVH over real meshes passes that (24 for the
+ *              15 k-triangle helmet, profiles/blas_lbvh.md): build such a mesh with vd_bvh_build.  vd_trace*'s 128
+ *              entries (with its overflow pass behind them) hold any tree this build can make: 62 key bits bound
+ *              max_depth by 62.
+ * vd_bvh_build_lbvh: host pointers, synchronous: stage, build, copy back.  VD_ERR_INVALID_ARG when n_bad_indices != 0.
+ * Which builder for which mesh, and the trace rate through either tree: profiles/blas_lbvh.md.                        */
+#define VD_BVH_LBVH_MAX_TRIANGLES (1u << 24)
+typedef struct VdBvhLbvhResult { uint32_t n_nodes, n_bad_indices, max_depth, _pad; } VdBvhLbvhResult;
+int vd_bvh_build_lbvh_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert, uint32_t* d_indices_inout, uint32_t n_tri,
+                          VdBvhNode* d_out_nodes, uint32_t node_cap, VdBvhLbvhResult* d_result /* DEVICE */);
+int vd_bvh_build_lbvh(VdCtx* ctx, const float* verts_xyz, uint32_t n_vert, uint32_t* indices_inout, uint32_t n_tri,
+                      VdBvhNode* out_nodes, uint32_t node_cap, uint32_t* out_n_nodes);
+
 /* Batched BLAS build (NEW): K meshes in ONE build.  MeshPool::add builds one BLAS per mesh at load
  * (crates/pools/src/mesh/mod.rs:309-351: Sponza-class scenes are hundreds of small meshes) and a
  * single build has a fixed cost of launches and host round trips that dwarfs a 15 k-triangle mesh.

@@ -53,6 +53,8 @@ MAX_DIST = np.float32(1e30)
 CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run their split form from this many instances
 TLAS_MAX_INSTANCES = 32768
 TLAS_WIDE_MAX_INSTANCES = 1 << 24   # VD_TLAS_WIDE_MAX_INSTANCES: vd_tlas_build_lbvh_wide*, vd_trace_wide*
+BVH_LBVH_MAX_TRIANGLES = 1 << 24    # VD_BVH_LBVH_MAX_TRIANGLES: vd_bvh_build_lbvh*
+BVH_LBVH_RESULT = np.dtype([("n_nodes", "<u4"), ("n_bad_indices", "<u4"), ("max_depth", "<u4"), ("_pad", "<u4")])   # VdBvhLbvhResult
 MAX_VIEWS = 8             # VD_MAX_VIEWS: cameras per vd_cull_compact_views* call
 BATCH_MAX_MESHES = 4096   # VD_BATCH_MAX_MESHES: meshes per vd_cull_batch* / vd_batch_mask_dev call (one-digit counting sort)
 
@@ -193,6 +195,8 @@ PROTOTYPES = {
     "vd_cull_batch": (_I, [_P, _P, _P, _U, _P, _U, _P, _P, _P]),
     "vd_bvh_build": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
     "vd_bvh_build_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
+    "vd_bvh_build_lbvh_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
+    "vd_bvh_build_lbvh": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
     "vd_bvh_build_batch": (_I, [_P, _P, _U, _P, C.c_uint64, _U, _P]),
     "vd_bvh_build_batch_dev": (_I, [_P, _P, _U, _P, C.c_uint64, _U, _P]),
     "vd_bvh_refit_plan_dev": (_I, [_P, _P, _U, C.POINTER(_P)]),
@@ -276,9 +280,10 @@ class VoidinHipMissing(RuntimeError):
     pass
 
 
-def load(path: str | None = None) -> C.CDLL:
+def load(path: str | None = None, strict: bool = True) -> C.CDLL:
     """dlopen libvoidin_hip.so and bind every prototype.  Raises (never falls back) when the
-    library or any declared symbol is missing."""
+    library or any declared symbol is missing.  strict=False (A/B tools that load the library of an EARLIER commit, which
+    lacks the newer entry points): a missing symbol is left unbound - calling it is an AttributeError."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -296,6 +301,8 @@ def load(path: str | None = None) -> C.CDLL:
         pass
     lib = C.CDLL(p)
     for name, (res, args) in PROTOTYPES.items():
+        if not strict and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -145,6 +145,7 @@ int vd_ctx_destroy(VdCtx* ctx) {
     if (ctx->refit.state) (void)hipFree(ctx->refit.state);
     if (ctx->trace_wide) (void)hipFree(ctx->trace_wide);
     if (ctx->lbvh_state) (void)hipFree(ctx->lbvh_state);
+    if (ctx->blas_lbvh_state) (void)hipFree(ctx->blas_lbvh_state);
     if (ctx->stage_in) (void)hipFree(ctx->stage_in);
     if (ctx->stage_out) (void)hipFree(ctx->stage_out);
     if (ctx->stage_aux) (void)hipFree(ctx->stage_aux);

@@ -1215,7 +1215,7 @@ __global__ __launch_bounds__(256) void tlas_refit_up_kernel(Node* nodes, unsigne
 
 // Stable LSD radix sort of (key, value) pairs, 8 bits per pass, for the Morton codes of the LBVH top level
 // (lbvh_from_boxes below).  A UNIT is one wave's 1024 consecutive pairs; units are
-// independent: pass 1 counts a unit's digits, a single-workgroup scan turns the [digit][unit] table into start offsets,
+// independent: pass 1 counts a unit's digits, a scan (one workgroup; in parts by many for large tables) turns the [digit][unit] table into start offsets,
 // pass 2 re-reads the unit in order - 16 groups of 64 - and ranks every pair among the equal digits before it (8 ballots
 // give the lanes with the same digit; the unit's running offsets sit in LDS).
 constexpr unsigned kSortUnit = 1024;
@@ -1236,6 +1236,27 @@ __global__ __launch_bounds__(64 * kSortWaves) void rs_count_kernel(const unsigne
         for (unsigned d = lane; d < 256u; d += 64u) table[(size_t)d * n_units + unit] = s_h[wave][d];
     }
 }
+// Large tables (more than kScanSingle counters): a workgroup scans a PART of 1024 counters in place and leaves the part's total;
+// rs_scan_kernel below then scans the totals, and the scatter adds its part's offset when it reads the table.  (One workgroup over
+// the whole table took 0.38 ms a pass at 1 Mi elements, 18 % of a build.)  m is a multiple of 256; the table is 16-byte aligned.
+constexpr unsigned kScanPart = 1024, kScanSingle = 16384;
+__global__ __launch_bounds__(256) void rs_scan_part_kernel(unsigned* __restrict__ table, unsigned m, unsigned* __restrict__ totals) {
+    __shared__ unsigned s_wave[4];
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const unsigned at = blockIdx.x * kScanPart + 4u * tid;
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    if (at < m) c = *reinterpret_cast<const uint4*>(table + at);
+    const unsigned sum = c.x + c.y + c.z + c.w;
+    unsigned incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const unsigned t = __shfl_up(incl, off); if (lane >= (unsigned)off) incl += t; }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned run = incl - sum;
+    for (unsigned w = 0; w < wave; ++w) run += s_wave[w];
+    if (at < m) *reinterpret_cast<uint4*>(table + at) = make_uint4(run, run + c.x, run + c.x + c.y, run + c.x + c.y + c.z);
+    if (tid == 255u) totals[blockIdx.x] = run + sum;
+}
 // exclusive scan of `m` counters in place (single workgroup; thread t owns a contiguous range)
 __global__ __launch_bounds__(1024) void rs_scan_kernel(unsigned* __restrict__ table, unsigned m) {
     __shared__ unsigned s_wave[16];
@@ -1255,11 +1276,15 @@ __global__ __launch_bounds__(1024) void rs_scan_kernel(unsigned* __restrict__ ta
 }
 __global__ __launch_bounds__(64 * kSortWaves) void rs_scatter_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, unsigned n,
                                                                      unsigned shift, unsigned n_units, const unsigned* __restrict__ table,
+                                                                     const unsigned* __restrict__ part_offsets /* null: the table is scanned as a whole */,
                                                                      unsigned* __restrict__ keys_out, unsigned* __restrict__ vals_out) {
     __shared__ unsigned s_off[kSortWaves][256];
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
     if (unit >= n_units) return;
-    for (unsigned d = lane; d < 256u; d += 64u) s_off[wave][d] = table[(size_t)d * n_units + unit];
+    for (unsigned d = lane; d < 256u; d += 64u) {
+        const size_t at = (size_t)d * n_units + unit;
+        s_off[wave][d] = table[at] + (part_offsets ? part_offsets[at / kScanPart] : 0u);
+    }
     vd_wave_lds_sync();
     const unsigned b0 = unit * kSortUnit;
     for (unsigned g = 0; g < kSortUnit; g += 64u) {
@@ -1307,12 +1332,35 @@ __global__ __launch_bounds__(256) void lbvh_leaf_boxes_kernel(const VdInstance* 
 #pragma unroll
     for (int k = 0; k < 3; ++k) { boxes[6u * i + k] = b.mn[k]; boxes[6u * i + 3 + k] = b.mx[k]; }
 }
+// extent of the finite centres as integer min / max of the order-preserving image of the float bits.  Atomics on ONE address cost
+// about 11 ns per wave instruction whatever the lanes hold (1.1 ms of a build at 1 Mi elements with an atomic per element, and as
+// much with one per wave): a block folds kExtentPerBlock elements or more - grid stride, at most kExtentBlocks blocks - in
+// registers, across its waves' lanes and through LDS, and sends six.
+constexpr unsigned kExtentPerBlock = 2048, kExtentBlocks = 1024;
 __global__ __launch_bounds__(256) void lbvh_extent_kernel(const float* __restrict__ boxes, unsigned n, unsigned* __restrict__ ext /*[6]: min xyz, max xyz of the centres*/) {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    float c[3];
-    if (!lbvh_centre(boxes, i, c)) return;
-    for (int k = 0; k < 3; ++k) { atomicMin(ext + k, ord_of(c[k])); atomicMax(ext + 3 + k, ord_of(c[k])); }
+    __shared__ unsigned s_part[4][6];
+    unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};      // the neutral elements: what the words start from
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        float c[3];
+        if (!lbvh_centre(boxes, i, c)) continue;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], ord_of(c[k])); hi[k] = max(hi[k], ord_of(c[k])); }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], (unsigned)__shfl_xor((int)lo[k], off)); hi[k] = max(hi[k], (unsigned)__shfl_xor((int)hi[k], off)); }
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { s_part[threadIdx.x >> 6][k] = lo[k]; s_part[threadIdx.x >> 6][3 + k] = hi[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 6u) return;
+    const unsigned k = threadIdx.x;
+    unsigned r = s_part[0][k];
+    for (int w = 1; w < 4; ++w) r = k < 3u ? min(r, s_part[w][k]) : max(r, s_part[w][k]);
+    if (k < 3u) atomicMin(ext + k, r); else atomicMax(ext + k, r);      // (a block without a finite centre sends the neutral elements: no change)
 }
 __device__ __forceinline__ unsigned spread10(unsigned v) {
     v = (v | (v << 16)) & 0x030000ffu; v = (v | (v << 8)) & 0x0300f00fu; v = (v | (v << 4)) & 0x030c30c3u; v = (v | (v << 2)) & 0x09249249u;
@@ -1336,12 +1384,6 @@ __global__ __launch_bounds__(256) void lbvh_keys_kernel(const float* __restrict_
     keys[i] = key;
     vals[i] = i;
 }
-// length of the common prefix of the codes at sorted positions i and j (-1 outside the array); equal codes: their positions decide
-__device__ __forceinline__ int lbvh_delta(const unsigned* __restrict__ keys, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    const unsigned a = keys[i], b = keys[j];
-    return a != b ? __clz((int)(a ^ b)) : 32 + __clz((int)((unsigned)i ^ (unsigned)j));
-}
 template <typename Node> __device__ __forceinline__ Node lbvh_node(const Box& b, unsigned l, unsigned r, unsigned instance_idx) {
     Node nd;
 #pragma unroll
@@ -1364,22 +1406,9 @@ __global__ __launch_bounds__(256) void lbvh_tree_kernel(const unsigned* __restri
         if (N == 1) { nodes[0] = lf; nodes[2] = lbvh_node<Node>(b, 1u, 1u, 0xffffffffu); }      // one instance: node 0 is its leaf, node 2 the self-merge
     }
     if (i >= N - 1) return;
-    // Karras 2012: direction of the node's range, its other end, the split
-    const int d = lbvh_delta(keys, N, i, i + 1) - lbvh_delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = lbvh_delta(keys, N, i, i - d);
-    int lmax = 2;
-    while (lbvh_delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1) if (lbvh_delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = lbvh_delta(keys, N, i, j);
-    int sp = 0;
-    for (int t = (l + 1) >> 1; ; t = (t + 1) >> 1) {
-        if (lbvh_delta(keys, N, i, i + (sp + t) * d) > dnode) sp += t;
-        if (t == 1) break;
-    }
-    const int gamma = i + sp * d + min(d, 0);
-    const int lo = min(i, j), hi = max(i, j);
+    // Karras 2012: direction of the node's range, its other end, the split (vd_common.hpp)
+    int lo, hi, gamma;
+    vd_lbvh_range(keys, N, i, lo, hi, gamma);
     const unsigned self = i == 0 ? 2u * n - 1u : n + (unsigned)i;
     const unsigned left = lo == gamma ? 1u + (unsigned)gamma : n + (unsigned)gamma;            // gamma >= 1 when interior: the root is nobody's child
     const unsigned right = hi == gamma + 1 ? 2u + (unsigned)gamma : n + (unsigned)gamma + 1u;
@@ -1416,33 +1445,58 @@ __global__ __launch_bounds__(256) void lbvh_fit_kernel(unsigned n, Node* nodes, 
     }
 }
 
-// work memory of one build: two key and two value arrays, parent links and arrival words for 2n + 2 nodes, the extent, the sort's table
+// work memory of the codes and their sort: two key and two value arrays, the extent, the sort's table
 size_t lbvh_arr_bytes(uint32_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
-template <typename Node>
-int lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, Node* d_nodes, void* work) {
+size_t lbvh_sort_bytes(uint32_t n) {
+    const size_t n_units = (n + kSortUnit - 1u) / kSortUnit, m = 256 * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
+    return 4 * lbvh_arr_bytes(n) + ((4 * (8 + m + n_parts) + 255) & ~(size_t)255);
+}
+int lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, unsigned** keys, unsigned** vals) {
     hipStream_t st = ctx->stream;
     const unsigned n_units = (n + kSortUnit - 1u) / kSortUnit;
     const size_t arr = lbvh_arr_bytes(n);
     char* base = reinterpret_cast<char*>(work);
     unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
     unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
-    unsigned* parent = reinterpret_cast<unsigned*>(base + 4 * arr);                 // 2n + 2 words
-    unsigned* arrived = parent + 2 * (size_t)n + 2;                                 // 2n + 2 words
-    unsigned* ext = arrived + 2 * (size_t)n + 2;                                    // 8 words
+    unsigned* ext = reinterpret_cast<unsigned*>(base + 4 * arr);                    // 8 words
     unsigned* table = ext + 8;                                                      // 256 * n_units words
+    const unsigned m = 256u * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
+    unsigned* totals = table + m;                                                   // n_parts words: the offsets of the table's parts
+    const bool parts = m > kScanSingle;
     VD_HIP_CHECK(ctx, hipMemsetAsync(ext, 0xff, 12, st));
     VD_HIP_CHECK(ctx, hipMemsetAsync(ext + 3, 0, 12, st));
     const unsigned grid = (n + 255u) / 256u;
-    hipLaunchKernelGGL(lbvh_extent_kernel, dim3(grid), dim3(256), 0, st, d_boxes, n, ext);
+    const unsigned ext_grid = std::min((n + kExtentPerBlock - 1u) / kExtentPerBlock, kExtentBlocks);
+    hipLaunchKernelGGL(lbvh_extent_kernel, dim3(ext_grid), dim3(256), 0, st, d_boxes, n, ext);
     hipLaunchKernelGGL(lbvh_keys_kernel, dim3(grid), dim3(256), 0, st, d_boxes, n, ext, k[0], v[0]);
     const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
     for (int pass = 0; pass < 4; ++pass) {
         const int x = pass & 1, y = x ^ 1;
         hipLaunchKernelGGL(rs_count_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], n, 8u * pass, n_units, table);
-        hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, 256u * n_units);
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], n, 8u * pass, n_units, table, k[y], v[y]);
+        if (parts) {
+            hipLaunchKernelGGL(rs_scan_part_kernel, dim3(n_parts), dim3(256), 0, st, table, m, totals);
+            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, totals, n_parts);
+        } else {
+            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, m);
+        }
+        hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], n, 8u * pass, n_units, table,
+                           parts ? totals : (const unsigned*)nullptr, k[y], v[y]);
     }
-    hipLaunchKernelGGL((lbvh_tree_kernel<Node>), dim3(grid), dim3(256), 0, st, k[0], v[0], d_boxes, n, d_nodes, parent, arrived);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    *keys = k[0]; *vals = v[0];                                                     // four passes: back in the first pair
+    return VD_OK;
+}
+// work memory of one build: the sort's, then parent links and arrival words for 2n + 2 nodes
+template <typename Node>
+int lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, Node* d_nodes, void* work) {
+    hipStream_t st = ctx->stream;
+    unsigned *keys = nullptr, *vals = nullptr;
+    const int rc = lbvh_sort_boxes(ctx, d_boxes, n, work, &keys, &vals);
+    if (rc) return rc;
+    unsigned* parent = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(work) + lbvh_sort_bytes(n));      // 2n + 2 words
+    unsigned* arrived = parent + 2 * (size_t)n + 2;                                 // 2n + 2 words
+    const unsigned grid = (n + 255u) / 256u;
+    hipLaunchKernelGGL((lbvh_tree_kernel<Node>), dim3(grid), dim3(256), 0, st, keys, vals, d_boxes, n, d_nodes, parent, arrived);
     hipLaunchKernelGGL((lbvh_fit_kernel<Node>), dim3(grid), dim3(256), 0, st, n, d_nodes, parent, arrived);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
@@ -1665,7 +1719,14 @@ int vd_tlas_build_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTla
 }
 
 size_t vd_lbvh_work_bytes(uint32_t n) {
-    return 4 * lbvh_arr_bytes(n) + 4 * (4 * (size_t)n + 4 + 8 + 256 * (size_t)((n + kSortUnit - 1u) / kSortUnit)) + 256;
+    return lbvh_sort_bytes(n) + 4 * (4 * (size_t)n + 4) + 256;
+}
+size_t vd_lbvh_sort_bytes(uint32_t n) { return lbvh_sort_bytes(n); }
+int vd_lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, const unsigned** keys, const unsigned** vals) {
+    unsigned *k = nullptr, *v = nullptr;
+    const int rc = lbvh_sort_boxes(ctx, d_boxes, n, work, &k, &v);
+    *keys = k; *vals = v;
+    return rc;
 }
 int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes, void* work) {
     if (!ctx || !d_boxes || !d_nodes || !work || n == 0 || n > VD_TLAS_MAX_INSTANCES) return VD_ERR_INVALID_ARG;

@@ -49,6 +49,7 @@ struct VdCtx {
     void* trace_deep = nullptr;  size_t trace_deep_bytes = 0;     // traversal, second pass over those rays: their list + stack entries beyond 128 (allocated when first needed)
     void* trace_wide = nullptr;  size_t trace_wide_bytes = 0;     // vd_trace_wide*: the per-call records of a wide top level (64 B per node), mesh records, triangles, fan-out
     void* lbvh_state = nullptr;  size_t lbvh_state_bytes = 0;     // vd_tlas_build_lbvh*: leaf boxes, codes, the sort's tables, parent links, arrival words
+    void* blas_lbvh_state = nullptr; size_t blas_lbvh_state_bytes = 0;   // vd_bvh_build_lbvh*: triangle boxes, the index copy, the sort's work memory, the radix tree
     VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene
@@ -114,6 +115,11 @@ int vd_tlas_build_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTla
 // bytes of device memory, 256-byte aligned) as its work memory.  Enqueues only.  n <= 32 768.
 size_t vd_lbvh_work_bytes(uint32_t n);
 int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNode* d_nodes, void* work);
+// tlas.hip: the first half of that build for any box array (blas_lbvh.hip: triangle boxes) - the codes of the box centres and their
+// stable radix sort.  *keys / *vals = the sorted codes and, per sorted position, the index of its box; both lie inside `work`
+// (vd_lbvh_sort_bytes(n) bytes, 256-byte aligned).  Enqueues only.  n <= 2^24.
+size_t vd_lbvh_sort_bytes(uint32_t n);
+int vd_lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, const unsigned** keys, const unsigned** vals);
 // ... and into 2n + 1 WIDE nodes: n <= VD_TLAS_WIDE_MAX_INSTANCES.
 int vd_tlas_lbvh_from_boxes_wide(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNodeWide* d_nodes, void* work);
 // tlas.hip: the refit (vd_tlas_refit*) of a top level whose leaves sit at 1..n, from ready leaf boxes (six floats per INSTANCE; leaf
@@ -247,6 +253,34 @@ __device__ __forceinline__ void vd_wave_lds_sync() {
 
 typedef unsigned long long vd_u64;
 #define VD_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+// ---- Karras' binary radix tree over sorted 30-bit codes (tlas.hip: lbvh_tree_kernel, blas_lbvh.hip: blas_lbvh_tree_kernel) ----
+// length of the common prefix of the codes at sorted positions i and j (-1 outside the array); equal codes: their positions decide,
+// i.e. the keys are the 64-bit words code << 32 | sorted position
+__device__ __forceinline__ int vd_lbvh_delta(const unsigned* __restrict__ keys, int n, int i, int j) {
+    if (j < 0 || j >= n) return -1;
+    const unsigned a = keys[i], b = keys[j];
+    return a != b ? __clz((int)(a ^ b)) : 32 + __clz((int)((unsigned)i ^ (unsigned)j));
+}
+// Karras 2012 for interior node i of n - 1: the sorted positions [lo, hi] it covers and its split - the left child covers
+// [lo, gamma], the right one [gamma + 1, hi]; a child of one position is that leaf, any other is interior node gamma / gamma + 1.
+__device__ __forceinline__ void vd_lbvh_range(const unsigned* __restrict__ keys, int N, int i, int& lo, int& hi, int& gamma) {
+    const int d = vd_lbvh_delta(keys, N, i, i + 1) - vd_lbvh_delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = vd_lbvh_delta(keys, N, i, i - d);
+    int lmax = 2;
+    while (vd_lbvh_delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
+    int l = 0;
+    for (int t = lmax >> 1; t >= 1; t >>= 1) if (vd_lbvh_delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = vd_lbvh_delta(keys, N, i, j);
+    int sp = 0;
+    for (int t = (l + 1) >> 1; ; t = (t + 1) >> 1) {
+        if (vd_lbvh_delta(keys, N, i, i + (sp + t) * d) > dnode) sp += t;
+        if (t == 1) break;
+    }
+    gamma = i + sp * d + min(d, 0);
+    lo = min(i, j); hi = max(i, j);
+}
 
 // ---- single-pass ordered scan across workgroups ("decoupled look-back") ----------------
 // tile_state[t] is one naturally aligned 8-byte {epoch:30 | status:2 | value:32} granule written

@@ -282,6 +282,23 @@ class Context:
                                             abi.ptr(d_nodes), node_cap, C.addressof(n_nodes)))
         return n_nodes.value
 
+    def bvh_build_lbvh(self, verts, indices):
+        """vd_bvh_build_lbvh, host arrays: the LBVH bottom level (NOT the reference's tree; voidin_abi.h "LBVH bottom level")
+        -> (nodes, indices in sorted code order)."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        idx = np.array(indices, dtype=np.uint32).reshape(-1).copy()
+        n_tri = len(idx) // 3
+        nodes = np.zeros(max(2 * n_tri, 2), dtype=abi.BVH_NODE)
+        n_nodes = C.c_uint32(0)
+        self._chk(self.lib.vd_bvh_build_lbvh(self.h, verts.ctypes.data, len(verts), idx.ctypes.data, n_tri,
+                                             nodes.ctypes.data, len(nodes), C.addressof(n_nodes)))
+        return nodes[:n_nodes.value].copy(), idx
+
+    def bvh_build_lbvh_dev(self, d_verts, n_vert, d_indices, n_tri, d_nodes, node_cap, d_result):
+        """vd_bvh_build_lbvh_dev: enqueues only; d_result: 16 bytes of DEVICE memory for {n_nodes, n_bad_indices, max_depth, _pad}."""
+        self._chk(self.lib.vd_bvh_build_lbvh_dev(self.h, abi.ptr(d_verts), n_vert, abi.ptr(d_indices), n_tri,
+                                                 abi.ptr(d_nodes), node_cap, abi.ptr(d_result)))
+
     def bvh_build_batch(self, meshes, packed=True):
         """K meshes in ONE build (vd_bvh_build_batch; MeshPool::add for a whole scene, mesh/mod.rs:309-351).
         meshes: [(vertices (V,3) f32, indices (3T,) u32)].  packed: one shared node array, each mesh's nodes behind the
@@ -708,6 +725,12 @@ class BvhBuilder:
 
     def build(self) -> Bvh:
         nodes, idx = self.ctx.bvh_build(self.vertices, self.indices)
+        self.indices.reshape(-1)[:] = idx
+        return Bvh(nodes)
+
+    def build_fast(self) -> Bvh:
+        """NEW (not in the reference): the LBVH bottom level (vd_bvh_build_lbvh) - for a mesh that is rebuilt every frame."""
+        nodes, idx = self.ctx.bvh_build_lbvh(self.vertices, self.indices)
         self.indices.reshape(-1)[:] = idx
         return Bvh(nodes)
 
