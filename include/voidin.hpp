@@ -307,6 +307,85 @@ class MeshPool {
         calculate_bounds(positions, n_positions, info);
     }
 
+    // NEW (voidin_abi.h "Batched LBVH bottom level"): add_fast for MANY meshes - the shards of a fracture, the chunks of a volume -
+    // with ONE batched LBVH build (vd_bvh_build_lbvh_batch) instead of a build per mesh.  The pool afterwards is what add_fast
+    // of each mesh in turn gives; the meshes' index slices are permuted in place.  A failed batch (a bad index, an empty mesh)
+    // throws and leaves the pool as it was.  Returns the MeshId of the first mesh added (ids are consecutive).
+    uint32_t add_many_fast(const MeshRef* meshes, size_t n_meshes) {
+        const uint32_t first_id = (uint32_t)mesh_info_cpu.size();
+        if (n_meshes == 0) return first_id;
+        std::vector<VdBvhLbvhBatchItem> items(n_meshes);
+        std::vector<size_t> first(n_meshes + 1, 0);
+        for (size_t m = 0; m < n_meshes; ++m) first[m + 1] = first[m] + node_room(meshes[m].n_indices / 3);
+        std::vector<BvhNode> built(first[n_meshes], BvhNode{});          // zero nodes behind every tree, as add_fast leaves them
+        for (size_t m = 0; m < n_meshes; ++m)
+            items[m] = lbvh_item(meshes[m].vertices, meshes[m].n_vertices, meshes[m].indices, meshes[m].n_indices, built.data() + first[m]);
+        std::vector<VdBvhLbvhResult> results(n_meshes);
+        gpu_.check(vd_bvh_build_lbvh_batch(gpu_.ctx(), items.data(), (uint32_t)n_meshes, nullptr, results.data()));
+        for (size_t m = 0; m < n_meshes; ++m) {
+            const MeshRef& mesh = meshes[m];
+            MeshInfo info{};
+            calculate_bounds(mesh.vertices, mesh.n_vertices, info);
+            info.index_count = (uint32_t)mesh.n_indices;
+            info.base_index = (uint32_t)indices.size();
+            info.vertex_offset = (int32_t)vertices.size();
+            info.bvh_index = (uint32_t)(bvh_nodes.size() + first[m]);
+            vertices.insert(vertices.end(), mesh.vertices, mesh.vertices + mesh.n_vertices);
+            indices.insert(indices.end(), mesh.indices, mesh.indices + mesh.n_indices);
+            mesh_info_cpu.push_back(info);
+        }
+        bvh_nodes.insert(bvh_nodes.end(), built.begin(), built.end());
+        return first_id;
+    }
+
+    // NEW: rebuild_fast for a LIST of meshes (each added with add_fast / add_many_fast), one batched LBVH build.  The pool
+    // afterwards is what rebuild_fast of each in turn gives.  Every mesh is checked before anything is built, and a failed build
+    // throws before anything is replaced: the pool stays as it was.
+    struct MeshRebuild {
+        uint32_t mesh_id;
+        const Vec3* positions; size_t n_positions;
+        const uint32_t* indices; size_t n_indices;
+    };
+    void rebuild_many_fast(const MeshRebuild* meshes, size_t n_meshes) {
+        if (n_meshes == 0) return;
+        struct Span { size_t v0, b0, b1, first; };
+        std::vector<Span> spans(n_meshes);
+        size_t n_idx = 0, n_nodes = 0;
+        for (size_t m = 0; m < n_meshes; ++m) {
+            const MeshRebuild& r = meshes[m];
+            if (r.mesh_id >= mesh_info_cpu.size()) throw Error(VD_ERR_INVALID_ARG, "MeshPool::rebuild_many_fast: no such mesh");
+            const MeshInfo& info = mesh_info_cpu[r.mesh_id];
+            const bool last = r.mesh_id + 1 == mesh_info_cpu.size();
+            const size_t v0 = (size_t)info.vertex_offset, v1 = last ? vertices.size() : (size_t)mesh_info_cpu[r.mesh_id + 1].vertex_offset;
+            const size_t b0 = info.bvh_index, b1 = last ? bvh_nodes.size() : (size_t)mesh_info_cpu[r.mesh_id + 1].bvh_index;
+            if (r.n_positions != v1 - v0 || r.n_indices != info.index_count)
+                throw Error(VD_ERR_INVALID_ARG, "MeshPool::rebuild_many_fast: vertex or index count differs from the mesh's");
+            if (b1 - b0 < node_room(r.n_indices / 3))
+                throw Error(VD_ERR_INVALID_ARG, "MeshPool::rebuild_many_fast: the mesh does not hold 2 T node slots (add it with add_fast)");
+            spans[m] = Span{v0, b0, b1, n_nodes};
+            n_idx += r.n_indices; n_nodes += node_room(r.n_indices / 3);
+        }
+        std::vector<uint32_t> idx(n_idx);
+        std::vector<BvhNode> built(n_nodes, BvhNode{});
+        std::vector<VdBvhLbvhBatchItem> items(n_meshes);
+        std::vector<VdBvhLbvhResult> results(n_meshes);
+        for (size_t m = 0, at = 0; m < n_meshes; at += meshes[m].n_indices, ++m) {
+            std::copy(meshes[m].indices, meshes[m].indices + meshes[m].n_indices, idx.begin() + (std::ptrdiff_t)at);
+            items[m] = lbvh_item(meshes[m].positions, meshes[m].n_positions, idx.data() + at, meshes[m].n_indices, built.data() + spans[m].first);
+        }
+        gpu_.check(vd_bvh_build_lbvh_batch(gpu_.ctx(), items.data(), (uint32_t)n_meshes, nullptr, results.data()));
+        for (size_t m = 0, at = 0; m < n_meshes; at += meshes[m].n_indices, ++m) {
+            const MeshRebuild& r = meshes[m];
+            MeshInfo& info = mesh_info_cpu[r.mesh_id];
+            const size_t n = results[m].n_nodes;
+            std::copy(built.begin() + (std::ptrdiff_t)spans[m].first, built.begin() + (std::ptrdiff_t)(spans[m].first + n), bvh_nodes.begin() + (std::ptrdiff_t)spans[m].b0);
+            std::fill(bvh_nodes.begin() + (std::ptrdiff_t)(spans[m].b0 + n), bvh_nodes.begin() + (std::ptrdiff_t)spans[m].b1, BvhNode{});
+            std::copy(idx.begin() + (std::ptrdiff_t)at, idx.begin() + (std::ptrdiff_t)(at + r.n_indices), indices.begin() + (std::ptrdiff_t)info.base_index);
+            std::copy(r.positions, r.positions + r.n_positions, vertices.begin() + (std::ptrdiff_t)spans[m].v0);
+            calculate_bounds(r.positions, r.n_positions, info);
+        }
+    }
+
     // MeshPool::add for a whole scene: the same bookkeeping for every mesh, ONE batched BLAS build (vd_bvh_build_batch)
     // instead of a build per mesh - a load of hundreds of small meshes pays the builder's fixed cost once.  The meshes'
     // index slices are permuted in place, as `add` does.  Returns the MeshId of the first mesh added (ids are consecutive).
@@ -408,6 +487,17 @@ class MeshPool {
         info.bvh_index = bvh_index;
         mesh_info_cpu.push_back(info);
         return (uint32_t)mesh_info_cpu.size() - 1;     // MeshId
+    }
+
+    // the node slots a mesh of T triangles keeps for the LBVH builder, and its item of a batched LBVH build (host pointers)
+    static size_t node_room(size_t n_tri) { return 2 * n_tri > 2 ? 2 * n_tri : 2; }
+    static VdBvhLbvhBatchItem lbvh_item(const Vec3* positions, size_t n_positions, uint32_t* idx, size_t n_indices, BvhNode* nodes) {
+        VdBvhLbvhBatchItem it{};
+        it.verts_xyz = &positions->x; it.n_vert = (uint32_t)n_positions;
+        it.indices_inout = idx; it.tri_cap = (uint32_t)(n_indices / 3);
+        it.nodes = nodes; it.node_cap = (uint32_t)node_room(n_indices / 3);
+        it.mesh_info = nullptr;                            // the pool's rows take calculate_bounds below, as add_fast's do
+        return it;
     }
 
     // calculate_bounds (mesh/mod.rs:22-27): fold from (+inf, -inf), into info.min / info.max

@@ -558,6 +558,58 @@ int vd_bvh_build_lbvh_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
 int vd_bvh_build_lbvh(VdCtx* ctx, const float* verts_xyz, uint32_t n_vert, uint32_t* indices_inout, uint32_t n_tri,
                       VdBvhNode* out_nodes, uint32_t node_cap, uint32_t* out_n_nodes);
 
+/* Batched LBVH bottom level: MANY meshes rebuilt in one call, every mesh's triangle count read from DEVICE memory - the shards
+ * of a fracture, the chunks of a marching-cubes volume, streamed LODs - where a vd_bvh_build_lbvh_dev per mesh pays its chain
+ * of launches per mesh and needs the count on the host.  Plan once per layout (pointers and capacities), then one call per
+ * frame (the idiom of vd_bvh_refit_plan_dev below).
+ * DEFINITION.  For item m let T_m = min(d_n_tri[m], tri_cap_m): a count ABOVE THE CAPACITY IS READ AS THE CAPACITY; d_n_tri ==
+ * NULL means every tri_cap.  Then nodes[0 .. n_nodes), the first 3 * T_m indices and d_results[m] (all 16 bytes, _pad 0) are
+ * byte for byte what vd_bvh_build_lbvh_dev(verts_xyz, n_vert, indices_inout, T_m, nodes, node_cap, &d_results[m]) writes for
+ * that mesh alone - box, code (the extent is each mesh's own), order, topology, numbering and boxes as defined above, node
+ * ids and leaf positions mesh-local.  No byte of nodes past n_nodes and no index past 3 * T_m is written.
+ *   T_m == 0    is legal here (a shard can vanish): d_results[m] is all zero (n_nodes == 0) and no node is written; a consumer
+ *               skips such a mesh - it has no node 0.
+ *   mesh_info   optional.  Its min / max become what MeshPool::calculate_bounds gives over ALL n_vert vertices from
+ *               (+inf, -inf), NaN ignored - the definition and the device code of vd_bvh_refit_planned_dev - whatever T_m is; no
+ *               other field is touched.
+ * vd_bvh_lbvh_plan_dev           once per layout.  BLOCKS: validates, uploads the descriptor table and allocates ALL work memory
+ *                                inside the plan, sized by the capacities (each mesh's slots are rounded up to 256; about 110 B
+ *                                per slot).  The plan keeps the items' POINTERS, not their data.  VD_ERR_INVALID_ARG with
+ *                                items[m].status set (no plan is returned) for: a null verts_xyz / indices_inout / nodes;
+ *                                tri_cap == 0; node_cap < max(2, 2 * tri_cap); nodes not 16-byte aligned; the capacities, each
+ *                                rounded up to 256, adding up to more than VD_BVH_LBVH_MAX_TRIANGLES (the item that crosses
+ *                                it); and, without a status, n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS.  The items are judged
+ *                                before the context is looked at, so a null ctx with a bad item names that item too.
+ *                                n_items == 0 is VD_OK: a plan that does nothing.
+ * vd_bvh_build_lbvh_planned_dev  ONLY ENQUEUES on the context's stream: no host read, no allocation, nothing on the host that
+ *                                depends on the counts - it can be captured into a HIP graph and replayed after d_n_tri has
+ *                                changed.  The number of launches depends on the plan's capacities alone (19 or 23 kernels and no
+ *                                memset, one more kernel when an item carries a mesh_info), never on n_items or the counts.  A null
+ *                                plan or d_results is VD_ERR_INVALID_ARG.  One build of a plan at a time (calls on one stream
+ *                                are ordered).
+ * vd_bvh_lbvh_plan_release       synchronises the stream first (a queued build uses the plan's memory).
+ * vd_bvh_build_lbvh_batch        host pointers inside the items (mesh_info too), host n_tri (may be NULL) and results;
+ *                                synchronous: stage, plan, build, copy back, release.  VD_ERR_INVALID_ARG with items[m].status
+ *                                set when a mesh has n_bad_indices != 0 (nothing is copied back), as vd_bvh_build_lbvh.
+ * Per-frame order: INTEGRATION.md 3d.  Measured against a loop of single builds: profiles/blas_lbvh_batch.md.               */
+#define VD_BVH_LBVH_BATCH_MAX_ITEMS (1u << 16)
+typedef struct VdBvhLbvhBatchItem {
+    const float* verts_xyz;     /* n_vert * 3, read at every build                                   */
+    uint32_t*    indices_inout; /* tri_cap * 3, mesh-local; the first 3 * n_tri are permuted in place */
+    VdBvhNode*   nodes;         /* node_cap >= max(2, 2 * tri_cap), 16-byte aligned                   */
+    VdMeshInfo*  mesh_info;     /* optional: min / max refreshed as vd_bvh_refit_planned_dev does     */
+    uint32_t     n_vert, tri_cap, node_cap;
+    int32_t      status;        /* written by the plan call                                           */
+} VdBvhLbvhBatchItem;
+typedef struct VdBvhLbvhPlan VdBvhLbvhPlan;
+int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items /* host array, device pointers inside */, uint32_t n_items,
+                         VdBvhLbvhPlan** out);
+int vd_bvh_build_lbvh_planned_dev(VdCtx* ctx, const VdBvhLbvhPlan* plan, const uint32_t* d_n_tri /* DEVICE, n_items; NULL = every tri_cap */,
+                                  VdBvhLbvhResult* d_results /* DEVICE, n_items */);
+int vd_bvh_lbvh_plan_release(VdCtx* ctx, VdBvhLbvhPlan* plan);
+int vd_bvh_build_lbvh_batch(VdCtx* ctx, VdBvhLbvhBatchItem* items /* host pointers inside */, uint32_t n_items,
+                            const uint32_t* n_tri /* host, may be NULL */, VdBvhLbvhResult* results /* host */);
+
 /* Batched BLAS build (NEW): K meshes in ONE build.  MeshPool::add builds one BLAS per mesh at load
  * (crates/pools/src/mesh/mod.rs:309-351: Sponza-class scenes are hundreds of small meshes) and a
  * single build has a fixed cost of launches and host round trips that dwarfs a 15 k-triangle mesh.

@@ -54,6 +54,7 @@ CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run t
 TLAS_MAX_INSTANCES = 32768
 TLAS_WIDE_MAX_INSTANCES = 1 << 24   # VD_TLAS_WIDE_MAX_INSTANCES: vd_tlas_build_lbvh_wide*, vd_trace_wide*
 BVH_LBVH_MAX_TRIANGLES = 1 << 24    # VD_BVH_LBVH_MAX_TRIANGLES: vd_bvh_build_lbvh*
+BVH_LBVH_BATCH_MAX_ITEMS = 1 << 16  # VD_BVH_LBVH_BATCH_MAX_ITEMS: vd_bvh_lbvh_plan_dev, vd_bvh_build_lbvh_batch
 BVH_LBVH_RESULT = np.dtype([("n_nodes", "<u4"), ("n_bad_indices", "<u4"), ("max_depth", "<u4"), ("_pad", "<u4")])   # VdBvhLbvhResult
 MAX_VIEWS = 8             # VD_MAX_VIEWS: cameras per vd_cull_compact_views* call
 BATCH_MAX_MESHES = 4096   # VD_BATCH_MAX_MESHES: meshes per vd_cull_batch* / vd_batch_mask_dev call (one-digit counting sort)
@@ -156,6 +157,17 @@ class BvhRefitItem(C.Structure):
                 ("n_vert", C.c_uint32), ("n_tri", C.c_uint32), ("n_nodes", C.c_uint32), ("status", C.c_int32)]
 
 
+class BvhLbvhBatchItem(C.Structure):
+    """VdBvhLbvhBatchItem (include/voidin_abi.h, "Batched LBVH bottom level")."""
+    _fields_ = [("verts_xyz", C.c_void_p), ("indices_inout", C.c_void_p), ("nodes", C.c_void_p), ("mesh_info", C.c_void_p),
+                ("n_vert", C.c_uint32), ("tri_cap", C.c_uint32), ("node_cap", C.c_uint32), ("status", C.c_int32)]
+
+
+# the same record as a numpy dtype (48 bytes)
+BVH_LBVH_BATCH_ITEM = np.dtype([("verts_xyz", "<u8"), ("indices_inout", "<u8"), ("nodes", "<u8"), ("mesh_info", "<u8"),
+                                ("n_vert", "<u4"), ("tri_cap", "<u4"), ("node_cap", "<u4"), ("status", "<i4")])
+
+
 class BvhBuildStats(C.Structure):
     """VdBvhBuildStats (include/voidin_abi.h, instrumentation)."""
     _fields_ = [("ms_precompute", C.c_float), ("ms_phase_a", C.c_float), ("ms_mid", C.c_float), ("ms_phase_b", C.c_float),
@@ -197,6 +209,10 @@ PROTOTYPES = {
     "vd_bvh_build_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
     "vd_bvh_build_lbvh_dev": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
     "vd_bvh_build_lbvh": (_I, [_P, _P, _U, _P, _U, _P, _U, _P]),
+    "vd_bvh_lbvh_plan_dev": (_I, [_P, _P, _U, C.POINTER(_P)]),
+    "vd_bvh_build_lbvh_planned_dev": (_I, [_P, _P, _P, _P]),
+    "vd_bvh_lbvh_plan_release": (_I, [_P, _P]),
+    "vd_bvh_build_lbvh_batch": (_I, [_P, _P, _U, _P, _P]),
     "vd_bvh_build_batch": (_I, [_P, _P, _U, _P, C.c_uint64, _U, _P]),
     "vd_bvh_build_batch_dev": (_I, [_P, _P, _U, _P, C.c_uint64, _U, _P]),
     "vd_bvh_refit_plan_dev": (_I, [_P, _P, _U, C.POINTER(_P)]),

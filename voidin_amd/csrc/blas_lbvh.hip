@@ -16,7 +16,15 @@
 //                                its own node and those of its leaf children; the root writes the result;
 //   6. blas_lbvh_permute_kernel  the index triples in sorted order.
 // Separate launches are the synchronisation between the passes.
+//
+// vd_bvh_lbvh_plan_dev / vd_bvh_build_lbvh_planned_dev build MANY meshes with the same six passes, each run once over one slot space
+// in which every mesh owns a run of 256-slot units, through the same per-mesh __device__ bodies; the sort is tlas.hip's segmented
+// variant (vd_lbvh_batch_sort_boxes).  Every mesh's triangle count is read from device memory by every pass, so the launches -
+// 19 or 23 kernels, no memset, one more kernel for VdMeshInfo bounds - are the same whatever the counts are ("the batched build" below).
 #include "vd_common.hpp"
+
+#include <new>
+#include <vector>
 
 namespace {
 
@@ -38,6 +46,7 @@ struct LbvhWork {
 };
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t work_bytes(uint32_t T) { return 2 * up256(24 * (size_t)T) + up256(12 * (size_t)T) + 7 * up256(4 * (size_t)T) + vd_lbvh_sort_bytes(T); }
+size_t work_bytes_batch(uint32_t S) { return 2 * up256(24 * (size_t)S) + up256(12 * (size_t)S) + 7 * up256(4 * (size_t)S) + vd_lbvh_batch_sort_bytes(S); }
 LbvhWork carve(void* base, uint32_t T) {
     char* p = reinterpret_cast<char*>(base);
     auto take = [&](size_t bytes) { char* q = p; p += up256(bytes); return q; };
@@ -84,11 +93,10 @@ __device__ __forceinline__ void node_store(VdBvhNode* nodes, unsigned id, const 
     w[1] = make_float4(six[3], six[4], six[5], __uint_as_float(count));
 }
 
-__global__ __launch_bounds__(kBlock) void blas_lbvh_boxes_kernel(const float* __restrict__ verts, unsigned n_vert, const unsigned* __restrict__ indices,
-                                                                 unsigned T, float* __restrict__ tbox, unsigned* __restrict__ idx_copy,
-                                                                 VdBvhLbvhResult* result) {
-    const unsigned t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= T) return;
+// The per-mesh bodies of the six passes: what one thread does for ONE mesh, given that mesh's arrays.  The single-mesh kernels
+// call them with the thread's index in the grid, the batched ones (below) with the slot's position inside its mesh.
+__device__ __forceinline__ void boxes_body(unsigned t, const float* __restrict__ verts, unsigned n_vert, const unsigned* __restrict__ indices,
+                                           float* __restrict__ tbox, unsigned* __restrict__ idx_copy, unsigned* n_bad) {
     Box3 b = box_empty();
     unsigned bad = 0;
 #pragma unroll
@@ -104,13 +112,20 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_boxes_kernel(const float* __
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) { tbox[6u * t + q] = b.mn[q]; tbox[6u * t + 3 + q] = b.mx[q]; }
-    if (bad) atomicAdd(&result->n_bad_indices, bad);
+    if (bad) atomicAdd(n_bad, bad);
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_boxes_kernel(const float* __restrict__ verts, unsigned n_vert, const unsigned* __restrict__ indices,
+                                                                 unsigned T, float* __restrict__ tbox, unsigned* __restrict__ idx_copy,
+                                                                 VdBvhLbvhResult* result) {
+    const unsigned t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= T) return;
+    boxes_body(t, verts, n_vert, indices, tbox, idx_copy, &result->n_bad_indices);
 }
 
-__global__ __launch_bounds__(kBlock) void blas_lbvh_tree_kernel(const unsigned* __restrict__ keys, unsigned T, unsigned* __restrict__ rlo,
-                                                                unsigned* __restrict__ rhi, unsigned* __restrict__ split, unsigned* __restrict__ par_int,
-                                                                unsigned* __restrict__ par_leaf, unsigned* __restrict__ arrived) {
-    const int i = (int)(blockIdx.x * kBlock + threadIdx.x), N = (int)T;
+__device__ __forceinline__ void tree_body(int i, const unsigned* __restrict__ keys, unsigned T, unsigned* __restrict__ rlo,
+                                          unsigned* __restrict__ rhi, unsigned* __restrict__ split, unsigned* __restrict__ par_int,
+                                          unsigned* __restrict__ par_leaf, unsigned* __restrict__ arrived) {
+    const int N = (int)T;
     if (i >= N - 1) return;
     int lo, hi, gamma;
     vd_lbvh_range(keys, N, i, lo, hi, gamma);
@@ -121,13 +136,17 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_tree_kernel(const unsigned* 
     if (i == 0) par_int[0] = kNoParent;
     arrived[i] = 0u;
 }
+__global__ __launch_bounds__(kBlock) void blas_lbvh_tree_kernel(const unsigned* __restrict__ keys, unsigned T, unsigned* __restrict__ rlo,
+                                                                unsigned* __restrict__ rhi, unsigned* __restrict__ split, unsigned* __restrict__ par_int,
+                                                                unsigned* __restrict__ par_leaf, unsigned* __restrict__ arrived) {
+    tree_body((int)(blockIdx.x * kBlock + threadIdx.x), keys, T, rlo, rhi, split, par_int, par_leaf, arrived);
+}
 
 // One thread per radix leaf (g < T) and per radix interior node (g - T): those that are EMITTED leaves fold their box and climb.
-__global__ __launch_bounds__(kBlock) void blas_lbvh_fit_kernel(unsigned T, const unsigned* __restrict__ vals, const float* __restrict__ tbox,
-                                                               const unsigned* __restrict__ rlo, const unsigned* __restrict__ rhi,
-                                                               const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
-                                                               const unsigned* __restrict__ par_leaf, float* ibox, unsigned* meta, unsigned* arrived) {
-    const unsigned g = blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void fit_body(unsigned g, unsigned T, const unsigned* __restrict__ vals, const float* __restrict__ tbox,
+                                         const unsigned* __restrict__ rlo, const unsigned* __restrict__ rhi,
+                                         const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
+                                         const unsigned* __restrict__ par_leaf, float* ibox, unsigned* meta, unsigned* arrived) {
     if (T < 2u || g >= 2u * T - 1u) return;
     Box3 b = box_empty();
     unsigned up;
@@ -171,6 +190,12 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_fit_kernel(unsigned T, const
         if (up == kNoParent) return;
     }
 }
+__global__ __launch_bounds__(kBlock) void blas_lbvh_fit_kernel(unsigned T, const unsigned* __restrict__ vals, const float* __restrict__ tbox,
+                                                               const unsigned* __restrict__ rlo, const unsigned* __restrict__ rhi,
+                                                               const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
+                                                               const unsigned* __restrict__ par_leaf, float* ibox, unsigned* meta, unsigned* arrived) {
+    fit_body(blockIdx.x * kBlock + threadIdx.x, T, vals, tbox, rlo, rhi, split, par_int, par_leaf, ibox, meta, arrived);
+}
 
 // interior nodes in the subtree of a child of p: 0 for a leaf child
 __device__ __forceinline__ unsigned left_interior(const unsigned* __restrict__ rlo, const unsigned* __restrict__ split, const unsigned* __restrict__ meta, unsigned p) {
@@ -178,12 +203,11 @@ __device__ __forceinline__ unsigned left_interior(const unsigned* __restrict__ r
     return rlo[p] == gm ? 0u : meta[gm] >> 8;
 }
 
-__global__ __launch_bounds__(kBlock) void blas_lbvh_number_kernel(unsigned T, const unsigned* __restrict__ vals, const float* __restrict__ tbox,
-                                                                  const unsigned* __restrict__ rlo, const unsigned* __restrict__ rhi,
-                                                                  const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
-                                                                  const float* __restrict__ ibox, const unsigned* __restrict__ meta,
-                                                                  VdBvhNode* __restrict__ nodes, unsigned node_cap, VdBvhLbvhResult* result) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void number_body(unsigned i, unsigned T, const unsigned* __restrict__ vals, const float* __restrict__ tbox,
+                                            const unsigned* __restrict__ rlo, const unsigned* __restrict__ rhi,
+                                            const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
+                                            const float* __restrict__ ibox, const unsigned* __restrict__ meta,
+                                            VdBvhNode* __restrict__ nodes, unsigned node_cap, VdBvhLbvhResult* result) {
     const float zero[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (T <= 3u) {                                         // node 0 is the one leaf
         if (i != 0u) return;
@@ -220,14 +244,131 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_number_kernel(unsigned T, co
         result->n_nodes = 2u + 2u * (m >> 8); result->max_depth = m & 255u;
     }
 }
+__global__ __launch_bounds__(kBlock) void blas_lbvh_number_kernel(unsigned T, const unsigned* __restrict__ vals, const float* __restrict__ tbox,
+                                                                  const unsigned* __restrict__ rlo, const unsigned* __restrict__ rhi,
+                                                                  const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
+                                                                  const float* __restrict__ ibox, const unsigned* __restrict__ meta,
+                                                                  VdBvhNode* __restrict__ nodes, unsigned node_cap, VdBvhLbvhResult* result) {
+    number_body(blockIdx.x * kBlock + threadIdx.x, T, vals, tbox, rlo, rhi, split, par_int, ibox, meta, nodes, node_cap, result);
+}
 
+__device__ __forceinline__ void permute_body(unsigned p, const unsigned* __restrict__ vals, const unsigned* __restrict__ idx_copy,
+                                             unsigned* __restrict__ indices) {
+    const size_t s = 3u * (size_t)vals[p];
+    indices[3u * p] = idx_copy[s]; indices[3u * p + 1u] = idx_copy[s + 1u]; indices[3u * p + 2u] = idx_copy[s + 2u];
+}
 __global__ __launch_bounds__(kBlock) void blas_lbvh_permute_kernel(unsigned T, const unsigned* __restrict__ vals, const unsigned* __restrict__ idx_copy,
                                                                    unsigned* __restrict__ indices) {
     const unsigned p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= T) return;
-    const size_t s = 3u * (size_t)vals[p];
-    indices[3u * p] = idx_copy[s]; indices[3u * p + 1u] = idx_copy[s + 1u]; indices[3u * p + 2u] = idx_copy[s + 2u];
+    permute_body(p, vals, idx_copy, indices);
 }
+
+// ---- the batched build (vd_bvh_lbvh_plan_dev / vd_bvh_build_lbvh_planned_dev) ---------------------------------------------------
+// All meshes of a plan lie in ONE slot space: item m owns the slots [slot0, slot0 + n_units * 256), n_units = ceil(tri_cap / 256), so
+// a 256-thread block (and a unit of the segmented sort, tlas.hip) never spans two meshes and the mesh of a block is one scalar
+// load.  Every array of LbvhWork is laid out over the slots; a mesh's part of it starts at slot0 and is what the single build's
+// array is for that mesh: positions, radix node ids and vals are mesh-local.  T_m = min(d_n_tri[m], tri_cap) is read on the
+// device by every pass; a lane whose position is beyond T_m leaves.  Grids come from the slot count alone.
+struct BatchItemDev {
+    const float* verts; unsigned* indices; VdBvhNode* nodes; VdMeshInfo* info;
+    unsigned n_vert, node_cap, n_chunks /* of the MeshInfo fold */, _pad[5];
+};
+static_assert(sizeof(BatchItemDev) == 64, "one item record per cache-line half");
+
+struct BatchSlot { unsigned m, j, T, slot0; };           // the mesh of this thread's slot, its position in it, the mesh's count
+__device__ __forceinline__ BatchSlot batch_slot(unsigned unit, const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                const unsigned* __restrict__ n_tri) {
+    BatchSlot b;
+    b.m = unit_seg[unit];
+    const VdLbvhSeg sg = segs[b.m];
+    b.slot0 = sg.slot0;
+    b.j = unit * kBlock + threadIdx.x - sg.slot0;
+    b.T = vd_lbvh_seg_count(sg, n_tri, b.m);
+    return b;
+}
+static_assert(kBlock == kVdLbvhBatchUnit, "a block is a unit of the slot space");
+
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_boxes_kernel(const BatchItemDev* __restrict__ items, const VdLbvhSeg* __restrict__ segs,
+                                                                       const unsigned* __restrict__ unit_seg, const unsigned* __restrict__ n_tri,
+                                                                       float* __restrict__ tbox, unsigned* __restrict__ idx_copy, unsigned* __restrict__ ext,
+                                                                       unsigned* n_bad /* per mesh, the plan's: 0 between builds */) {
+    const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
+    if (b.j == 0u) {                                       // the mesh's extent words start from the neutral elements (read by the NEXT launch)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { ext[6u * b.m + q] = 0xffffffffu; ext[6u * b.m + 3 + q] = 0u; }
+    }
+    if (b.j >= b.T) return;
+    const BatchItemDev it = items[b.m];
+    boxes_body(b.j, it.verts, it.n_vert, it.indices, tbox + 6u * (size_t)b.slot0, idx_copy + 3u * (size_t)b.slot0, n_bad + b.m);
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_tree_kernel(const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                                      const unsigned* __restrict__ n_tri, const unsigned* __restrict__ keys, LbvhWork w) {
+    const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
+    if (b.j + 1u >= b.T) return;                           // interior nodes 0 .. T - 2
+    tree_body((int)b.j, keys + b.slot0, b.T, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0, w.par_int + b.slot0, w.par_leaf + b.slot0,
+              w.arrived + b.slot0);
+}
+// blocks [0, n_units): the radix leaves; blocks [n_units, 2 n_units): the radix interior nodes
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_fit_kernel(unsigned n_units, const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                                     const unsigned* __restrict__ n_tri, const unsigned* __restrict__ vals, LbvhWork w) {
+    const bool interior = blockIdx.x >= n_units;
+    const BatchSlot b = batch_slot(interior ? blockIdx.x - n_units : blockIdx.x, segs, unit_seg, n_tri);
+    if (b.T < 2u || b.j + (interior ? 1u : 0u) >= b.T) return;
+    fit_body(interior ? b.T + b.j : b.j, b.T, vals + b.slot0, w.tbox + 6u * (size_t)b.slot0, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0,
+             w.par_int + b.slot0, w.par_leaf + b.slot0, w.ibox + 6u * (size_t)b.slot0, w.meta + b.slot0, w.arrived + b.slot0);
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_number_kernel(const BatchItemDev* __restrict__ items, const VdLbvhSeg* __restrict__ segs,
+                                                                        const unsigned* __restrict__ unit_seg, const unsigned* __restrict__ n_tri,
+                                                                        const unsigned* __restrict__ vals, LbvhWork w, VdBvhLbvhResult* results) {
+    const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
+    if (b.j >= b.T) return;                                // T == 0: no node, the result stays all zero
+    const BatchItemDev it = items[b.m];
+    number_body(b.j, b.T, vals + b.slot0, w.tbox + 6u * (size_t)b.slot0, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0, w.par_int + b.slot0,
+                w.ibox + 6u * (size_t)b.slot0, w.meta + b.slot0, it.nodes, it.node_cap, results + b.m);
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_permute_kernel(const BatchItemDev* __restrict__ items, const VdLbvhSeg* __restrict__ segs,
+                                                                         const unsigned* __restrict__ unit_seg, const unsigned* __restrict__ n_tri,
+                                                                         const unsigned* __restrict__ vals, const unsigned* __restrict__ idx_copy,
+                                                                         unsigned* n_bad, VdBvhLbvhResult* results) {
+    const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
+    if (b.j == 0u) {                                       // every mesh has this slot, whatever T: the rest of its result, and the count re-armed
+        results[b.m].n_bad_indices = n_bad[b.m]; n_bad[b.m] = 0u;
+        results[b.m]._pad = 0u;
+        if (b.T == 0u) { results[b.m].n_nodes = 0u; results[b.m].max_depth = 0u; }      // otherwise: blas_lbvh_batch_number_kernel's, a launch ago
+    }
+    if (b.j >= b.T) return;
+    permute_body(b.j, vals + b.slot0, idx_copy + 3u * (size_t)b.slot0, items[b.m].indices);
+}
+// VdMeshInfo.min / max of every item that carries one: a block per chunk {item, first vertex} (vd_common.hpp: vd_mesh_bounds_fold)
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_bounds_kernel(const BatchItemDev* __restrict__ items, const uint2* __restrict__ chunks, int* keys,
+                                                                        unsigned* done) {
+    const uint2 ch = chunks[blockIdx.x];
+    const BatchItemDev it = items[ch.x];
+    vd_mesh_bounds_fold(it.verts, it.n_vert, it.info, it.n_chunks, ch.y, keys + 6u * ch.x, done + ch.x);
+}
+
+int fail_item(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t m, const char* what) {
+    items[m].status = VD_ERR_INVALID_ARG;
+    if (ctx) snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_lbvh_plan: item %u: %s", m, what);
+    return VD_ERR_INVALID_ARG;
+}
+
+}  // namespace
+
+struct VdBvhLbvhPlan {
+    unsigned n_items = 0, n_slots = 0, n_bound_chunks = 0;
+    void* dev = nullptr;                                   // ONE allocation: the tables, then the work memory
+    BatchItemDev* d_items = nullptr;
+    uint2* d_bound_chunks = nullptr;                       // per block of the MeshInfo fold: {item, first vertex}
+    int* d_bound_keys = nullptr;                           // per item: 3 min keys, 3 max keys, neutral between builds
+    unsigned* d_bound_done = nullptr;                      // per item: 0 between builds
+    unsigned* d_bad = nullptr;                             // per item: indices >= n_vert counted by the boxes pass; 0 between builds
+    VdLbvhBatchLayout layout = {};
+    LbvhWork w = {};
+};
+
+namespace {
 
 int check_args(VdCtx* ctx, const void* verts, const void* indices, uint32_t n_tri, const void* nodes, uint32_t node_cap) {
     if (!verts || !indices || !nodes) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: null vertices / indices / nodes");
@@ -294,6 +435,207 @@ int vd_bvh_build_lbvh(VdCtx* ctx, const float* verts_xyz, uint32_t n_vert, uint3
     if ((rc = vd_fetch_blob(ctx, out_nodes, &blobs[2]))) return rc;
     if ((rc = vd_fetch_blob(ctx, indices_inout, &blobs[1]))) return rc;
     *out_n_nodes = res.n_nodes;
+    return VD_OK;
+}
+
+int vd_bvh_lbvh_plan_release(VdCtx* ctx, VdBvhLbvhPlan* plan) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx || !plan) return VD_ERR_INVALID_ARG;
+    (void)hipStreamSynchronize(ctx->stream);               // a queued build still uses the plan's memory
+    if (plan->dev) (void)hipFree(plan->dev);
+    delete plan;
+    return VD_OK;
+}
+
+int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items, VdBvhLbvhPlan** out) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!out) return VD_ERR_INVALID_ARG;
+    *out = nullptr;
+    if ((n_items && !items) || n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS) {
+        if (ctx) snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_lbvh_plan: null item array, or n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS");
+        return VD_ERR_INVALID_ARG;
+    }
+    for (uint32_t m = 0; m < n_items; ++m) items[m].status = VD_OK;
+    std::vector<BatchItemDev> h_items;
+    std::vector<VdLbvhSeg> h_segs;
+    std::vector<unsigned> h_unit_seg;
+    std::vector<uint2> h_ext_chunks, h_bound_chunks;
+    try {
+        h_items.resize(n_items); h_segs.resize(n_items);
+        uint64_t slots = 0;
+        for (uint32_t m = 0; m < n_items; ++m) {
+            const VdBvhLbvhBatchItem& it = items[m];
+            if (!it.verts_xyz || !it.indices_inout || !it.nodes) return fail_item(ctx, items, m, "null vertices / indices / nodes");
+            if (it.tri_cap == 0u) return fail_item(ctx, items, m, "tri_cap == 0");
+            if (it.tri_cap > VD_BVH_LBVH_MAX_TRIANGLES) return fail_item(ctx, items, m, "tri_cap > VD_BVH_LBVH_MAX_TRIANGLES");
+            if (it.node_cap < (it.tri_cap < 2u ? 2u : 2u * it.tri_cap)) return fail_item(ctx, items, m, "node_cap < max(2, 2 * tri_cap)");
+            if ((reinterpret_cast<uintptr_t>(it.nodes) & 15u) != 0u) return fail_item(ctx, items, m, "nodes is not 16-byte aligned");
+            const unsigned n_units = (it.tri_cap + kVdLbvhBatchUnit - 1u) / kVdLbvhBatchUnit;
+            if (slots + (uint64_t)n_units * kVdLbvhBatchUnit > VD_BVH_LBVH_MAX_TRIANGLES)
+                return fail_item(ctx, items, m, "the capacities, each rounded up to 256, add up to more than VD_BVH_LBVH_MAX_TRIANGLES");
+            h_segs[m] = VdLbvhSeg{(unsigned)slots, it.tri_cap, n_units, 0u};
+            h_unit_seg.insert(h_unit_seg.end(), n_units, m);
+            for (unsigned c = 0; c < it.tri_cap; c += kVdLbvhExtentChunk) h_ext_chunks.push_back(make_uint2(m, c));
+            BatchItemDev& d = h_items[m];
+            d = BatchItemDev{};
+            d.verts = it.verts_xyz; d.indices = it.indices_inout; d.nodes = it.nodes; d.info = it.mesh_info;
+            d.n_vert = it.n_vert; d.node_cap = it.node_cap;
+            if (it.mesh_info) {
+                d.n_chunks = it.n_vert ? (unsigned)(((size_t)it.n_vert + kVdVertChunk - 1u) / kVdVertChunk) : 1u;      // an empty fold still writes (+inf, -inf)
+                for (unsigned c = 0; c < d.n_chunks; ++c) h_bound_chunks.push_back(make_uint2(m, c * kVdVertChunk));
+            }
+            slots += (uint64_t)n_units * kVdLbvhBatchUnit;
+        }
+        if (!ctx) return VD_ERR_INVALID_ARG;               // (the items are judged without a context: nothing above touches the device)
+        VdBvhLbvhPlan* p = new VdBvhLbvhPlan();
+        p->n_items = n_items; p->n_slots = (unsigned)slots; p->n_bound_chunks = (unsigned)h_bound_chunks.size();
+        *out = p;
+        if (n_items == 0) return VD_OK;
+        const uint32_t S = p->n_slots;
+        const size_t o_items = 0, o_segs = up256(sizeof(BatchItemDev) * n_items), o_unit = o_segs + up256(sizeof(VdLbvhSeg) * n_items),
+                     o_echunks = o_unit + up256(4 * h_unit_seg.size()), o_ext = o_echunks + up256(8 * h_ext_chunks.size()),
+                     o_bchunks = o_ext + up256(24 * (size_t)n_items), o_bkeys = o_bchunks + up256(8 * h_bound_chunks.size()),
+                     o_bdone = o_bkeys + up256(24 * (size_t)n_items), o_bad = o_bdone + up256(4 * (size_t)n_items),
+                     o_work = o_bad + up256(4 * (size_t)n_items),
+                     total = o_work + work_bytes_batch(S);
+        std::vector<int> h_keys(6 * (size_t)n_items);
+        for (size_t m = 0; m < n_items; ++m)
+            for (int q = 0; q < 6; ++q) h_keys[6 * m + q] = q < 3 ? kVdKeyPosInf : kVdKeyNegInf;
+        hipError_t e = hipMalloc(&p->dev, total);
+        if (e != hipSuccess) { delete p; *out = nullptr; VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_lbvh_plan: device memory"); }
+        char* base = reinterpret_cast<char*>(p->dev);
+        e = hipMemset(base, 0, o_work);                    // the fold's done counters and the bad-index counts start at 0 and come back to 0 after every build
+        if (e == hipSuccess) e = hipMemcpy(base + o_items, h_items.data(), sizeof(BatchItemDev) * n_items, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + o_segs, h_segs.data(), sizeof(VdLbvhSeg) * n_items, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + o_unit, h_unit_seg.data(), 4 * h_unit_seg.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + o_echunks, h_ext_chunks.data(), 8 * h_ext_chunks.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + o_bkeys, h_keys.data(), 4 * h_keys.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !h_bound_chunks.empty()) e = hipMemcpy(base + o_bchunks, h_bound_chunks.data(), 8 * h_bound_chunks.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the uploads ran on the default stream; the build runs on the context's
+        if (e != hipSuccess) {
+            (void)hipFree(p->dev); delete p; *out = nullptr;
+            VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
+        }
+        p->d_items = reinterpret_cast<BatchItemDev*>(base + o_items);
+        p->d_bound_chunks = reinterpret_cast<uint2*>(base + o_bchunks);
+        p->d_bound_keys = reinterpret_cast<int*>(base + o_bkeys);
+        p->d_bound_done = reinterpret_cast<unsigned*>(base + o_bdone);
+        p->d_bad = reinterpret_cast<unsigned*>(base + o_bad);
+        p->layout.n_slots = S; p->layout.n_chunks = (unsigned)h_ext_chunks.size();
+        p->layout.d_segs = reinterpret_cast<const VdLbvhSeg*>(base + o_segs);
+        p->layout.d_unit_seg = reinterpret_cast<const unsigned*>(base + o_unit);
+        p->layout.d_chunks = reinterpret_cast<const uint2*>(base + o_echunks);
+        p->layout.d_ext = reinterpret_cast<unsigned*>(base + o_ext);
+        p->w = carve(base + o_work, S);                    // .sort: vd_lbvh_batch_sort_bytes(S)
+    } catch (const std::bad_alloc&) {
+        if (*out) { delete *out; *out = nullptr; }
+        if (!ctx) return VD_ERR_OOM;
+        VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_lbvh_plan: host memory");
+    }
+    return VD_OK;
+}
+
+int vd_bvh_build_lbvh_planned_dev(VdCtx* ctx, const VdBvhLbvhPlan* plan, const uint32_t* d_n_tri, VdBvhLbvhResult* d_results) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (!plan || !d_results) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_planned: null plan / results");
+    if (plan->n_items == 0u) return VD_OK;
+    const VdLbvhBatchLayout& L = plan->layout;
+    const LbvhWork& w = plan->w;
+    const unsigned n_units = L.n_slots / kBlock;
+    hipStream_t st = ctx->stream;
+    // No memset of d_results: every word of a result is stored by a kernel (the last pass completes it and re-arms the plan's
+    // bad-index count), so a captured call is kernels only - a memset node of a HIP graph was seen to fill with other bytes than
+    // it was given from the second replay on (profiles/blas_lbvh_batch.md).
+    vd_time_begin(ctx);
+    hipLaunchKernelGGL(blas_lbvh_batch_boxes_kernel, dim3(n_units), dim3(kBlock), 0, st, plan->d_items, L.d_segs, L.d_unit_seg, d_n_tri, w.tbox, w.idx, L.d_ext,
+                       plan->d_bad);
+    const unsigned *keys = nullptr, *vals = nullptr;
+    int rc;
+    if ((rc = vd_lbvh_batch_sort_boxes(ctx, w.tbox, &L, d_n_tri, w.sort, &keys, &vals))) { vd_time_end(ctx); return rc; }
+    hipLaunchKernelGGL(blas_lbvh_batch_tree_kernel, dim3(n_units), dim3(kBlock), 0, st, L.d_segs, L.d_unit_seg, d_n_tri, keys, w);
+    hipLaunchKernelGGL(blas_lbvh_batch_fit_kernel, dim3(2u * n_units), dim3(kBlock), 0, st, n_units, L.d_segs, L.d_unit_seg, d_n_tri, vals, w);
+    hipLaunchKernelGGL(blas_lbvh_batch_number_kernel, dim3(n_units), dim3(kBlock), 0, st, plan->d_items, L.d_segs, L.d_unit_seg, d_n_tri, vals, w, d_results);
+    hipLaunchKernelGGL(blas_lbvh_batch_permute_kernel, dim3(n_units), dim3(kBlock), 0, st, plan->d_items, L.d_segs, L.d_unit_seg, d_n_tri, vals, w.idx,
+                       plan->d_bad, d_results);
+    if (plan->n_bound_chunks)
+        hipLaunchKernelGGL(blas_lbvh_batch_bounds_kernel, dim3(plan->n_bound_chunks), dim3(kBlock), 0, st, plan->d_items, plan->d_bound_chunks,
+                           plan->d_bound_keys, plan->d_bound_done);
+    vd_time_end(ctx);
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    return VD_OK;
+}
+
+int vd_bvh_build_lbvh_batch(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items, const uint32_t* n_tri, VdBvhLbvhResult* results) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx) return VD_ERR_INVALID_ARG;
+    if (n_items && (!items || !results)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_batch: null items / results");
+    if (n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_batch: n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS");
+    if (n_items == 0u) return VD_OK;
+    // one device allocation: per item vertices, indices, nodes and (optional) MeshInfo, then the counts and the results
+    std::vector<VdBvhLbvhBatchItem> d_items;
+    std::vector<size_t> offs;
+    size_t total = 0;
+    auto place = [&](size_t bytes) { const size_t at = total; total += up256(bytes ? bytes : 1); offs.push_back(at); return at; };
+    try {
+        d_items.assign(items, items + n_items);
+        offs.reserve(4 * (size_t)n_items + 2);
+        for (uint32_t m = 0; m < n_items; ++m) {
+            items[m].status = VD_OK;
+            const VdBvhLbvhBatchItem& it = items[m];
+            if (!it.verts_xyz || !it.indices_inout || !it.nodes) return fail_item(ctx, items, m, "null vertices / indices / nodes");
+            if (it.tri_cap == 0u || it.tri_cap > VD_BVH_LBVH_MAX_TRIANGLES) return fail_item(ctx, items, m, "tri_cap == 0 or > VD_BVH_LBVH_MAX_TRIANGLES");
+            if (it.node_cap < (it.tri_cap < 2u ? 2u : 2u * it.tri_cap)) return fail_item(ctx, items, m, "node_cap < max(2, 2 * tri_cap)");
+            place(12 * (size_t)it.n_vert); place(12 * (size_t)it.tri_cap); place(sizeof(VdBvhNode) * (size_t)it.node_cap); place(sizeof(VdMeshInfo));
+        }
+    } catch (const std::bad_alloc&) {
+        VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_build_lbvh_batch: host memory");
+    }
+    const size_t o_cnt = place(4 * (size_t)n_items), o_res = place(sizeof(VdBvhLbvhResult) * (size_t)n_items);
+    char* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), total) != hipSuccess) VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_build_lbvh_batch: staging");
+    hipError_t e = hipSuccess;
+    for (uint32_t m = 0; m < n_items && e == hipSuccess; ++m) {
+        const VdBvhLbvhBatchItem& it = items[m];
+        VdBvhLbvhBatchItem& di = d_items[m];
+        di.verts_xyz = reinterpret_cast<const float*>(d + offs[4 * m]); di.indices_inout = reinterpret_cast<uint32_t*>(d + offs[4 * m + 1]);
+        di.nodes = reinterpret_cast<VdBvhNode*>(d + offs[4 * m + 2]);
+        di.mesh_info = it.mesh_info ? reinterpret_cast<VdMeshInfo*>(d + offs[4 * m + 3]) : nullptr;
+        if (it.n_vert) e = hipMemcpy(d + offs[4 * m], it.verts_xyz, 12 * (size_t)it.n_vert, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + offs[4 * m + 1], it.indices_inout, 12 * (size_t)it.tri_cap, hipMemcpyHostToDevice);
+        if (e == hipSuccess && it.mesh_info) e = hipMemcpy(d + offs[4 * m + 3], it.mesh_info, sizeof(VdMeshInfo), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && n_tri) e = hipMemcpy(d + o_cnt, n_tri, 4 * (size_t)n_items, hipMemcpyHostToDevice);
+    VdBvhLbvhPlan* plan = nullptr;
+    int rc = VD_OK;
+    if (e == hipSuccess) {
+        rc = vd_bvh_lbvh_plan_dev(ctx, d_items.data(), n_items, &plan);
+        for (uint32_t m = 0; m < n_items; ++m) items[m].status = d_items[m].status;
+        if (rc == VD_OK) rc = vd_bvh_build_lbvh_planned_dev(ctx, plan, n_tri ? reinterpret_cast<const uint32_t*>(d + o_cnt) : nullptr,
+                                                            reinterpret_cast<VdBvhLbvhResult*>(d + o_res));
+        if (rc == VD_OK) {
+            e = hipStreamSynchronize(ctx->stream);
+            if (e == hipSuccess) e = hipMemcpy(results, d + o_res, sizeof(VdBvhLbvhResult) * (size_t)n_items, hipMemcpyDeviceToHost);
+        }
+    }
+    if (rc == VD_OK && e == hipSuccess) {
+        for (uint32_t m = 0; m < n_items; ++m)
+            if (results[m].n_bad_indices != 0u) { rc = fail_item(ctx, items, m, "an index >= n_vert"); }
+            else if (results[m].n_nodes > items[m].node_cap) { rc = VD_ERR_HIP; snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build_lbvh_batch: implausible node count"); }
+    }
+    if (rc == VD_OK && e == hipSuccess) {
+        for (uint32_t m = 0; m < n_items && e == hipSuccess; ++m) {
+            const VdBvhLbvhBatchItem& it = items[m];
+            const uint32_t T = n_tri ? (n_tri[m] < it.tri_cap ? n_tri[m] : it.tri_cap) : it.tri_cap;
+            if (results[m].n_nodes) e = hipMemcpy(it.nodes, d + offs[4 * m + 2], sizeof(VdBvhNode) * (size_t)results[m].n_nodes, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && T) e = hipMemcpy(it.indices_inout, d + offs[4 * m + 1], 12 * (size_t)T, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && it.mesh_info) e = hipMemcpy(it.mesh_info, d + offs[4 * m + 3], sizeof(VdMeshInfo), hipMemcpyDeviceToHost);
+        }
+    }
+    if (plan) (void)vd_bvh_lbvh_plan_release(ctx, plan);
+    (void)hipFree(d);
+    if (rc != VD_OK) return rc;
+    if (e != hipSuccess) VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
     return VD_OK;
 }
 

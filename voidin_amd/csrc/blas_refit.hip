@@ -37,9 +37,8 @@ namespace {
 
 constexpr unsigned kNoParent = 0xffffffffu;
 constexpr unsigned kBlock = 256u;
-constexpr unsigned kVertChunk = 4096u;                 // vertices per block of the MeshInfo fold
-constexpr int kKeyPosInf = 0x7f800000;                 // vd_key(+inf): start (and re-armed value) of a min
-constexpr int kKeyNegInf = (int)0x807fffff;            // vd_key(-inf): of a max
+constexpr unsigned kVertChunk = kVdVertChunk;          // vertices per block of the MeshInfo fold (vd_common.hpp: vd_mesh_bounds_fold)
+constexpr int kKeyPosInf = kVdKeyPosInf, kKeyNegInf = kVdKeyNegInf;      // the neutral keys of its min / max
 
 struct RefitItemDev {
     const float* verts; const unsigned* indices; VdBvhNode* nodes; VdMeshInfo* info;
@@ -125,51 +124,8 @@ __device__ __forceinline__ void leaf_climb(const RefitItemDev* __restrict__ item
 }
 
 __device__ __forceinline__ void bounds_fold(const RefitItemDev* __restrict__ items, const uint2 chunk, int* keys, unsigned* done) {
-    __shared__ int part[6][kBlock / 64u];
     const RefitItemDev it = items[chunk.x];
-    int k[6] = {kKeyPosInf, kKeyPosInf, kKeyPosInf, kKeyNegInf, kKeyNegInf, kKeyNegInf};
-    const unsigned end = it.n_vert - chunk.y < kVertChunk ? it.n_vert : chunk.y + kVertChunk;
-    for (unsigned v = chunk.y + threadIdx.x; v < end; v += kBlock) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float p = it.verts[3u * (size_t)v + q];
-            const int lo = vd_key_lo(p), hi = vd_key_hi(p);
-            k[q] = lo < k[q] ? lo : k[q]; k[3 + q] = hi > k[3 + q] ? hi : k[3 + q];
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const int o = __shfl_xor(k[q], off);
-            k[q] = q < 3 ? (o < k[q] ? o : k[q]) : (o > k[q] ? o : k[q]);
-        }
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) part[q][threadIdx.x >> 6] = k[q];
-    }
-    __syncthreads();
-    if (threadIdx.x != 0u) return;
-    keys += 6u * chunk.x;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        int r = part[q][0];
-        for (unsigned w = 1; w < kBlock / 64u; ++w) r = q < 3 ? (part[q][w] < r ? part[q][w] : r) : (part[q][w] > r ? part[q][w] : r);
-        if (q < 3) (void)__hip_atomic_fetch_min(&keys[q], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else (void)__hip_atomic_fetch_max(&keys[q], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned old = __hip_atomic_fetch_add(&done[chunk.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old + 1u < it.n_chunks) return;
-    __hip_atomic_store(&done[chunk.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {                      // read and re-arm in one atomic each
-        it.info->min[q] = vd_unkey(__hip_atomic_exchange(&keys[q], kKeyPosInf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        it.info->max[q] = vd_unkey(__hip_atomic_exchange(&keys[3 + q], kKeyNegInf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
+    vd_mesh_bounds_fold(it.verts, it.n_vert, it.info, it.n_chunks, chunk.y, keys + 6u * chunk.x, done + chunk.x);      // vd_common.hpp
 }
 
 template <bool kFences>

@@ -1486,6 +1486,160 @@ int lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, un
     *keys = k[0]; *vals = v[0];                                                     // four passes: back in the first pair
     return VD_OK;
 }
+// ---- the same codes and sort for MANY box arrays side by side (blas_lbvh.hip: vd_bvh_build_lbvh_planned_dev) ----------------------
+// Segment m owns the slots [slot0, slot0 + n_units * kVdLbvhBatchUnit) of one slot space; the first T_m = vd_lbvh_seg_count of
+// them hold boxes, the others are ABSENT: no box is read for them and their code is kLbvhAbsentCode, above every real code, so
+// they sort behind the segment's boxes.  The order is (segment, code, input position): a UNIT is a wave's 256 consecutive slots and
+// never spans two segments, the digit table is indexed [segment][digit][unit in segment], and the exclusive scan of the whole table
+// (rs_scan_kernel / rs_scan_part_kernel as they are) then starts segment m's digits at slot0 - every slot is counted - so no pair
+// leaves its segment.  Four passes whatever the number of segments; all grids come from the slot count, none from the T_m.
+constexpr unsigned kLbvhAbsentCode = 0x40000000u;
+constexpr unsigned kBatchUnit = kVdLbvhBatchUnit;
+// one block per CHUNK {segment, first slot of the segment's} of at most kVdLbvhExtentChunk slots: fold in registers, six atomics
+__global__ __launch_bounds__(256) void lbvh_extent_seg_kernel(const float* __restrict__ boxes, const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ n_live,
+                                                              const uint2* __restrict__ chunks, unsigned* __restrict__ ext /*[segment][6]*/) {
+    __shared__ unsigned s_part[4][6];
+    const uint2 ch = chunks[blockIdx.x];
+    const VdLbvhSeg sg = segs[ch.x];
+    const unsigned T = vd_lbvh_seg_count(sg, n_live, ch.x), end = min(T, ch.y + kVdLbvhExtentChunk);
+    unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    for (unsigned j = ch.y + threadIdx.x; j < end; j += 256u) {
+        float c[3];
+        if (!lbvh_centre(boxes, sg.slot0 + j, c)) continue;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], ord_of(c[k])); hi[k] = max(hi[k], ord_of(c[k])); }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], (unsigned)__shfl_xor((int)lo[k], off)); hi[k] = max(hi[k], (unsigned)__shfl_xor((int)hi[k], off)); }
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { s_part[threadIdx.x >> 6][k] = lo[k]; s_part[threadIdx.x >> 6][3 + k] = hi[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 6u || ch.y >= T) return;            // a chunk without a box sends nothing
+    const unsigned k = threadIdx.x;
+    unsigned r = s_part[0][k];
+    for (int w = 1; w < 4; ++w) r = k < 3u ? min(r, s_part[w][k]) : max(r, s_part[w][k]);
+    if (k < 3u) atomicMin(ext + 6u * ch.x + k, r); else atomicMax(ext + 6u * ch.x + k, r);
+}
+__global__ __launch_bounds__(256) void lbvh_keys_seg_kernel(const float* __restrict__ boxes, unsigned n_slots, const VdLbvhSeg* __restrict__ segs,
+                                                            const unsigned* __restrict__ n_live, const unsigned* __restrict__ unit_seg,
+                                                            const unsigned* __restrict__ ext, unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
+    const unsigned s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n_slots) return;
+    const unsigned m = unit_seg[s / kBatchUnit];
+    const VdLbvhSeg sg = segs[m];
+    const unsigned j = s - sg.slot0;
+    float c[3];
+    unsigned key = kLbvhAbsentCode;
+    if (j < vd_lbvh_seg_count(sg, n_live, m)) {
+        key = kLbvhBadCode;
+        if (lbvh_centre(boxes, s, c)) {
+            unsigned q[3];
+            for (int k = 0; k < 3; ++k) {
+                const float lo = of_ord(ext[6u * m + k]), hi = of_ord(ext[6u * m + 3 + k]);
+                const float t = hi > lo ? (c[k] - lo) / (hi - lo) : 0.0f;
+                q[k] = (unsigned)fminf(fmaxf(t * 1024.0f, 0.0f), 1023.0f);
+            }
+            key = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
+        }
+    }
+    keys[s] = key;
+    vals[s] = j;                                           // segment-local: the position the box came at
+}
+// where unit `unit` of the slot space keeps digit 0 in the table: digit d is n_units of its segment further on
+__device__ __forceinline__ size_t rs_seg_slot(const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg, unsigned unit, unsigned& stride) {
+    const VdLbvhSeg sg = segs[unit_seg[unit]];
+    const unsigned u0 = sg.slot0 / kBatchUnit;
+    stride = sg.n_units;
+    return (size_t)256u * u0 + (unit - u0);
+}
+__global__ __launch_bounds__(64 * kSortWaves) void rs_count_seg_kernel(const unsigned* __restrict__ keys, unsigned shift, unsigned n_units,
+                                                                       const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                                       unsigned* __restrict__ table) {
+    __shared__ unsigned s_h[kSortWaves][256];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
+    for (unsigned d = lane; d < 256u; d += 64u) s_h[wave][d] = 0u;
+    vd_wave_lds_sync();
+    if (unit < n_units) {
+        const unsigned b0 = unit * kBatchUnit;
+        for (unsigned g = 0; g < kBatchUnit; g += 64u) atomicAdd(&s_h[wave][(keys[b0 + g + lane] >> shift) & 255u], 1u);
+        vd_wave_lds_sync();
+        unsigned stride;
+        const size_t at0 = rs_seg_slot(segs, unit_seg, unit, stride);
+        for (unsigned d = lane; d < 256u; d += 64u) table[at0 + (size_t)d * stride] = s_h[wave][d];
+    }
+}
+__global__ __launch_bounds__(64 * kSortWaves) void rs_scatter_seg_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, unsigned shift,
+                                                                         unsigned n_units, const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                                         const unsigned* __restrict__ table, const unsigned* __restrict__ part_offsets,
+                                                                         unsigned* __restrict__ keys_out, unsigned* __restrict__ vals_out) {
+    __shared__ unsigned s_off[kSortWaves][256];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, unit = blockIdx.x * kSortWaves + wave;
+    if (unit >= n_units) return;
+    unsigned stride;
+    const size_t at0 = rs_seg_slot(segs, unit_seg, unit, stride);
+    for (unsigned d = lane; d < 256u; d += 64u) {
+        const size_t at = at0 + (size_t)d * stride;
+        s_off[wave][d] = table[at] + (part_offsets ? part_offsets[at / kScanPart] : 0u);
+    }
+    vd_wave_lds_sync();
+    const unsigned b0 = unit * kBatchUnit;
+    for (unsigned g = 0; g < kBatchUnit; g += 64u) {
+        const unsigned i = b0 + g + lane;
+        const unsigned key = keys[i], val = vals[i];
+        const unsigned d = (key >> shift) & 255u;
+        unsigned long long same = ~0ull;
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long bm = __ballot((d >> bit) & 1u);
+            same &= ((d >> bit) & 1u) ? bm : ~bm;
+        }
+        const unsigned rank = vd_mbcnt(same), cnt = (unsigned)__popcll(same);
+        const unsigned dst = s_off[wave][d] + rank;
+        vd_wave_lds_sync();
+        if (rank == 0u) s_off[wave][d] += cnt;             // the first lane of each digit advances the unit's offset
+        vd_wave_lds_sync();
+        keys_out[dst] = key; vals_out[dst] = val;
+    }
+}
+size_t lbvh_batch_sort_bytes(uint32_t n_slots) {
+    const size_t n_units = n_slots / kBatchUnit, m = 256 * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
+    return 4 * lbvh_arr_bytes(n_slots) + ((4 * (m + n_parts) + 255) & ~(size_t)255);
+}
+int lbvh_batch_sort_boxes(VdCtx* ctx, const float* d_boxes, const VdLbvhBatchLayout& L, const unsigned* d_n_live, void* work, unsigned** keys, unsigned** vals) {
+    hipStream_t st = ctx->stream;
+    const unsigned n = L.n_slots, n_units = n / kBatchUnit;
+    const size_t arr = lbvh_arr_bytes(n);
+    char* base = reinterpret_cast<char*>(work);
+    unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
+    unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
+    unsigned* table = reinterpret_cast<unsigned*>(base + 4 * arr);                  // 256 * n_units words
+    const unsigned m = 256u * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
+    unsigned* totals = table + m;
+    const bool parts = m > kScanSingle;
+    hipLaunchKernelGGL(lbvh_extent_seg_kernel, dim3(L.n_chunks), dim3(256), 0, st, d_boxes, L.d_segs, d_n_live, L.d_chunks, L.d_ext);
+    hipLaunchKernelGGL(lbvh_keys_seg_kernel, dim3(n / 256u), dim3(256), 0, st, d_boxes, n, L.d_segs, d_n_live, L.d_unit_seg, L.d_ext, k[0], v[0]);
+    const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int x = pass & 1, y = x ^ 1;
+        hipLaunchKernelGGL(rs_count_seg_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], 8u * pass, n_units, L.d_segs, L.d_unit_seg, table);
+        if (parts) {
+            hipLaunchKernelGGL(rs_scan_part_kernel, dim3(n_parts), dim3(256), 0, st, table, m, totals);
+            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, totals, n_parts);
+        } else {
+            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, m);
+        }
+        hipLaunchKernelGGL(rs_scatter_seg_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], 8u * pass, n_units, L.d_segs, L.d_unit_seg, table,
+                           parts ? totals : (const unsigned*)nullptr, k[y], v[y]);
+    }
+    VD_HIP_CHECK(ctx, hipGetLastError());
+    *keys = k[0]; *vals = v[0];
+    return VD_OK;
+}
 // work memory of one build: the sort's, then parent links and arrival words for 2n + 2 nodes
 template <typename Node>
 int lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, Node* d_nodes, void* work) {
@@ -1725,6 +1879,14 @@ size_t vd_lbvh_sort_bytes(uint32_t n) { return lbvh_sort_bytes(n); }
 int vd_lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, const unsigned** keys, const unsigned** vals) {
     unsigned *k = nullptr, *v = nullptr;
     const int rc = lbvh_sort_boxes(ctx, d_boxes, n, work, &k, &v);
+    *keys = k; *vals = v;
+    return rc;
+}
+size_t vd_lbvh_batch_sort_bytes(uint32_t n_slots) { return lbvh_batch_sort_bytes(n_slots); }
+int vd_lbvh_batch_sort_boxes(VdCtx* ctx, const float* d_boxes, const VdLbvhBatchLayout* layout, const unsigned* d_n_live, void* work,
+                             const unsigned** keys, const unsigned** vals) {
+    unsigned *k = nullptr, *v = nullptr;
+    const int rc = lbvh_batch_sort_boxes(ctx, d_boxes, *layout, d_n_live, work, &k, &v);
     *keys = k; *vals = v;
     return rc;
 }

@@ -120,6 +120,24 @@ int vd_tlas_lbvh_from_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlas
 // (vd_lbvh_sort_bytes(n) bytes, 256-byte aligned).  Enqueues only.  n <= 2^24.
 size_t vd_lbvh_sort_bytes(uint32_t n);
 int vd_lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, const unsigned** keys, const unsigned** vals);
+// tlas.hip: ... and for MANY box arrays side by side in one slot space (blas_lbvh.hip: the batched build).  Segment m owns the slots
+// [slot0, slot0 + n_units * kVdLbvhBatchUnit); its first min(d_n_live[m], cap) slots (cap when d_n_live is null) hold boxes, read at
+// d_boxes + 6 * slot.  After the call every segment's slots hold its pairs sorted by (code, position in the segment), the absent
+// slots behind them; *vals are positions INSIDE the segment.  d_ext (6 words per segment) must hold the neutral elements
+// (3 x 0xffffffff, 3 x 0) when the call starts.  The number of launches depends on n_slots alone (<= or > 16 384: the scan in
+// parts), never on the counts.  `work`: vd_lbvh_batch_sort_bytes(n_slots) bytes, 256-byte aligned.  Enqueues only.
+constexpr unsigned kVdLbvhBatchUnit = 256, kVdLbvhExtentChunk = 2048;
+struct VdLbvhSeg { unsigned slot0, cap, n_units, _pad; };
+struct VdLbvhBatchLayout {
+    unsigned n_slots, n_chunks;            // n_slots: a multiple of kVdLbvhBatchUnit
+    const VdLbvhSeg* d_segs;               // per segment
+    const unsigned* d_unit_seg;            // per unit of the slot space: its segment
+    const uint2* d_chunks;                 // {segment, first position}: ceil(cap / kVdLbvhExtentChunk) per segment
+    unsigned* d_ext;                       // 6 words per segment
+};
+size_t vd_lbvh_batch_sort_bytes(uint32_t n_slots);
+int vd_lbvh_batch_sort_boxes(VdCtx* ctx, const float* d_boxes, const VdLbvhBatchLayout* layout, const unsigned* d_n_live, void* work,
+                             const unsigned** keys, const unsigned** vals);
 // ... and into 2n + 1 WIDE nodes: n <= VD_TLAS_WIDE_MAX_INSTANCES.
 int vd_tlas_lbvh_from_boxes_wide(VdCtx* ctx, const float* d_boxes, uint32_t n, VdTlasNodeWide* d_nodes, void* work);
 // tlas.hip: the refit (vd_tlas_refit*) of a top level whose leaves sit at 1..n, from ready leaf boxes (six floats per INSTANCE; leaf
@@ -280,6 +298,66 @@ __device__ __forceinline__ void vd_lbvh_range(const unsigned* __restrict__ keys,
     }
     gamma = i + sp * d + min(d, 0);
     lo = min(i, j); hi = max(i, j);
+}
+
+// boxes in segment m of a batched slot space: the count on the device, read as the capacity when it is above it (or absent)
+__device__ __forceinline__ unsigned vd_lbvh_seg_count(const VdLbvhSeg& sg, const unsigned* __restrict__ n_live, unsigned m) {
+    return n_live ? min(n_live[m], sg.cap) : sg.cap;
+}
+
+// ---- VdMeshInfo.min / max of one mesh inside a launch that serves many (blas_refit.hip, blas_lbvh.hip) --------------------------
+// MeshPool::calculate_bounds (crates/pools/src/mesh/mod.rs:22-27): the fold over ALL n_vert vertices from (+inf, -inf), NaN ignored,
+// on the order-preserving integer image of the float bits.  One 256-thread block folds kVdVertChunk vertices from `first` on and
+// sends six integer atomics to keys6; the block whose arrival completes the mesh (n_chunks of them) writes info->min / max and puts
+// keys6 and *done back to their neutral values: nothing is cleared between launches.
+constexpr unsigned kVdVertChunk = 4096u;
+constexpr int kVdKeyPosInf = 0x7f800000;               // vd_key(+inf): start (and re-armed value) of a min
+constexpr int kVdKeyNegInf = (int)0x807fffff;          // vd_key(-inf): of a max
+__device__ __forceinline__ void vd_mesh_bounds_fold(const float* __restrict__ verts, unsigned n_vert, VdMeshInfo* info, unsigned n_chunks, unsigned first,
+                                                    int* keys6, unsigned* done) {
+    __shared__ int part[6][4];
+    int k[6] = {kVdKeyPosInf, kVdKeyPosInf, kVdKeyPosInf, kVdKeyNegInf, kVdKeyNegInf, kVdKeyNegInf};
+    const unsigned end = n_vert - first < kVdVertChunk ? n_vert : first + kVdVertChunk;
+    for (unsigned v = first + threadIdx.x; v < end; v += 256u) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float p = verts[3u * (size_t)v + q];
+            const int lo = vd_key_lo(p), hi = vd_key_hi(p);
+            k[q] = lo < k[q] ? lo : k[q]; k[3 + q] = hi > k[3 + q] ? hi : k[3 + q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int o = __shfl_xor(k[q], off);
+            k[q] = q < 3 ? (o < k[q] ? o : k[q]) : (o > k[q] ? o : k[q]);
+        }
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) part[q][threadIdx.x >> 6] = k[q];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0u) return;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+        int r = part[q][0];
+        for (unsigned w = 1; w < 4u; ++w) r = q < 3 ? (part[q][w] < r ? part[q][w] : r) : (part[q][w] > r ? part[q][w] : r);
+        if (q < 3) (void)__hip_atomic_fetch_min(&keys6[q], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else (void)__hip_atomic_fetch_max(&keys6[q], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned old = __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old + 1u < n_chunks) return;
+    __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {                      // read and re-arm in one atomic each
+        info->min[q] = vd_unkey(__hip_atomic_exchange(&keys6[q], kVdKeyPosInf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        info->max[q] = vd_unkey(__hip_atomic_exchange(&keys6[3 + q], kVdKeyNegInf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
 }
 
 // ---- single-pass ordered scan across workgroups ("decoupled look-back") ----------------

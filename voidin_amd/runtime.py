@@ -299,6 +299,69 @@ class Context:
         self._chk(self.lib.vd_bvh_build_lbvh_dev(self.h, abi.ptr(d_verts), n_vert, abi.ptr(d_indices), n_tri,
                                                  abi.ptr(d_nodes), node_cap, abi.ptr(d_result)))
 
+    # Batched LBVH bottom level: many meshes per call, the triangle counts on the device (voidin_abi.h "Batched LBVH bottom level")
+    class BvhLbvhPlan:
+        """vd_bvh_lbvh_plan_dev: the layout of K meshes - pointers and capacities - validated once, with all work memory of their
+        build.  `items` is an (abi.BvhLbvhBatchItem * K) with device pointers (a failed plan leaves the offending item's status
+        set); the plan keeps those pointers, so the caller keeps the tensors alive."""
+
+        def __init__(self, ctx: "Context", items, n_items=None):
+            self.ctx, self.items = ctx, items
+            self.n_items = len(items) if n_items is None else int(n_items)
+            h = C.c_void_p()
+            ctx._chk(ctx.lib.vd_bvh_lbvh_plan_dev(ctx.h, C.addressof(items) if self.n_items else None, self.n_items, C.byref(h)))
+            self.h = h
+
+        def build(self, d_n_tri, d_results):
+            self.ctx.bvh_build_lbvh_planned_dev(self, d_n_tri, d_results)
+
+        def close(self):
+            if getattr(self, "h", None):
+                self.ctx.lib.vd_bvh_lbvh_plan_release(self.ctx.h, self.h)
+                self.h = None
+
+        def __del__(self):
+            try:
+                self.close()
+            except Exception:
+                pass
+
+    def bvh_lbvh_plan(self, items, n_items=None) -> "Context.BvhLbvhPlan":
+        return Context.BvhLbvhPlan(self, items, n_items)
+
+    def bvh_build_lbvh_planned_dev(self, plan: "Context.BvhLbvhPlan", d_n_tri, d_results):
+        """vd_bvh_build_lbvh_planned_dev: enqueues the build of every mesh of the plan.  d_n_tri: K uint32 counts in DEVICE memory
+        (None = every tri_cap); d_results: 16 * K bytes of DEVICE memory."""
+        self._chk(self.lib.vd_bvh_build_lbvh_planned_dev(self.h, plan.h, abi.ptr(d_n_tri) if d_n_tri is not None else None, abi.ptr(d_results)))
+
+    def bvh_build_lbvh_batch(self, meshes, n_tri=None, mesh_infos=None):
+        """vd_bvh_build_lbvh_batch, host arrays.  meshes: [(vertices (V,3) f32, indices (3 * tri_cap,) u32)]; n_tri: per mesh, the
+        triangles to build from (None = all; above the capacity = all); mesh_infos: None, or per mesh None / a 1-element
+        abi.MESH_INFO array whose min / max are refreshed in place.  -> [(nodes, indices with the first 3 T permuted, result)].
+        A mesh with an index >= n_vert raises VD_ERR_INVALID_ARG; `.items` of the error names it by status."""
+        K = len(meshes)
+        items = (abi.BvhLbvhBatchItem * max(K, 1))()
+        keep = []
+        for m, (v, i) in enumerate(meshes):
+            v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+            idx = np.array(i, dtype=np.uint32).reshape(-1).copy()
+            cap = len(idx) // 3
+            nodes = np.zeros(max(2 * cap, 2), dtype=abi.BVH_NODE)
+            keep.append((v, idx, nodes))
+            items[m].verts_xyz, items[m].indices_inout, items[m].nodes = v.ctypes.data, idx.ctypes.data, nodes.ctypes.data
+            info = None if mesh_infos is None else mesh_infos[m]
+            items[m].mesh_info = None if info is None else info.ctypes.data
+            items[m].n_vert, items[m].tri_cap, items[m].node_cap = len(v), cap, len(nodes)
+        counts = None if n_tri is None else np.ascontiguousarray(n_tri, dtype=np.uint32)
+        assert counts is None or len(counts) == K
+        results = np.zeros(max(K, 1), dtype=abi.BVH_LBVH_RESULT)
+        try:
+            self._chk(self.lib.vd_bvh_build_lbvh_batch(self.h, C.addressof(items), K, None if counts is None else counts.ctypes.data, results.ctypes.data))
+        except VoidinError as e:
+            e.items = items
+            raise
+        return [(keep[m][2][: int(results[m]["n_nodes"])].copy(), keep[m][1], results[m].copy()) for m in range(K)]
+
     def bvh_build_batch(self, meshes, packed=True):
         """K meshes in ONE build (vd_bvh_build_batch; MeshPool::add for a whole scene, mesh/mod.rs:309-351).
         meshes: [(vertices (V,3) f32, indices (3T,) u32)].  packed: one shared node array, each mesh's nodes behind the
