@@ -187,6 +187,9 @@ class BvhBuilder {
     // NEW (voidin_abi.h "LBVH bottom level"): an LBVH over the triangles in the same node layout and numbering - NOT the
     // reference's tree - built in a fraction of the time: for a mesh whose triangles change every frame.  `indices` is
     // rewritten in sorted code order.  Every consumer of a Bvh takes it (refit, traverse_iter, the trace entry points).
+    // Gpu::set_option(VD_OPT_BLAS_LBVH_MAX_DEPTH, 23) once, and every tree built here - and by MeshPool::add_fast, rebuild_fast,
+    // add_many_fast and rebuild_many_fast, which come through here or through the batched build - has max_depth <= 23: what the
+    // 24-entry stack of the WGSL traverse_bvh can walk.  Without it a real mesh gives a deeper tree (the helmet: 24).
     Bvh build_fast() {
         Bvh bvh;
         bvh.nodes.resize(2 * n_triangles_ > 2 ? 2 * n_triangles_ : 2);

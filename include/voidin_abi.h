@@ -206,6 +206,12 @@ typedef enum VdOption {
     VD_OPT_TLAS_PROFILE = 17,     /* 1: the indexed build prints its in-kernel cycle counters             */
     VD_OPT_TLAS_CHAIN_LDS = 18,   /* 0: the single-workgroup chain reads its slot arrays from memory even when
                                      they would fit LDS (<= 5600 instances); default 1 (A/B)               */
+    VD_OPT_BLAS_LBVH_MAX_DEPTH = 19,/* D >= 1: vd_bvh_build_lbvh* build the DEPTH-BOUNDED topology defined at "LBVH bottom level" below -
+                                     max_depth <= D for every input, so D = 23 makes every tree fit the 24-entry stack of the WGSL
+                                     traverse_bvh.  Values above 62 are read as 62 (which no input reaches: the unbounded tree's bytes).
+                                     Two more launches and 8 more bytes of work memory per triangle; a build is refused
+                                     (VD_ERR_INVALID_ARG) when n_tri > 2^(D+1) can not be held.  vd_bvh_lbvh_plan_dev latches the
+                                     value.  Default 0: unbounded - the launches, memory and bytes of a library without the option */
     VD_OPT_BLAS_WIDE_PAYLOAD = 30,/* 1: vd_bvh_build moves the 8-byte payload (what meshes above 2^25 triangles use) at
                                      any size (tests); default 0                                                  */
     VD_OPT_BLAS_REFIT_FENCES = 31,/* 1: vd_bvh_refit_planned_dev adds an agent-scope release / acquire fence pair around every arrival-counter
@@ -534,6 +540,22 @@ int vd_bvh_build_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
  *             n_nodes = 2 with node 0 a leaf.
  *   boxes     a leaf's is the union of its triangles' boxes, an interior node's the union of its children's:
  *             vd_bvh_refit(lbvh(x), x) changes no byte.
+ *   depth-bounded topology   with VD_OPT_BLAS_LBVH_MAX_DEPTH = D >= 1 (default 0: the topology above), box, code, order, numbering
+ *             and boxes stay as defined; only the topology changes.  Let needr(k) = 0 for k <= 3, else bits(k - 1) - 1: the depth
+ *             of the radix tree over the integers 0 .. k - 1 cut off at nodes of <= 3 positions.  Top-down, a node covers the
+ *             sorted positions [lo, hi] at depth d, k = hi - lo + 1 of them.  k <= 3: a leaf, as above.  In RADIX MODE (the
+ *             root's) let s be the split above: the first position whose key code << 32 | position has the highest bit in which
+ *             the end keys differ.  If d + 1 + needr(max(s - lo, hi - s + 1)) <= D the node splits at s and both children are in
+ *             radix mode; otherwise it is a SWITCH NODE: it and everything below it are in POSITION MODE with base = its lo.  In
+ *             position mode the split is the radix split over p - base: b = the highest bit in which lo - base and hi - base
+ *             differ, s = base + (((lo - base) >> b | 1) << b).  d + needr(k) <= D holds for every node - at the root that is
+ *             needr(n_tri) <= D, i.e. n_tri <= 2^(D+1); a radix child keeps it by the rule; a position subtree is exactly
+ *             needr(k) deep - so max_depth <= D FOR EVERY INPUT.  A build with needr(n_tri) > D is refused before anything is
+ *             launched (VD_ERR_INVALID_ARG; the message names the smallest bound that works): D = 23 takes every n_tri <=
+ *             VD_BVH_LBVH_MAX_TRIANGLES.  For D >= 53 the rule cannot fire (30 code bits, then at most 2^24 positions).  The tree
+ *             is still a function of the input alone, the call still only enqueues: two more launches, 8 more bytes of work memory
+ *             per triangle (the same warm-up rule for graph capture).  On real meshes D = 23 moves a few dozen positions (the
+ *             helmet: 5 switch nodes over 34 of 15 452 positions; trace rate within 1 % of the unbounded tree's): profiles/blas_lbvh_bounded.md.
  * No byte of out_nodes past n_nodes is written.  The build is TOTAL: there is no VD_ERR_DEGENERATE - duplicate triangles,
  * collinear centres, NaN and infinite vertices all give a valid tree.
  *
@@ -545,10 +567,11 @@ int vd_bvh_build_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
  *   max_depth  edges on the longest path from node 0 to a leaf.  The WGSL traverse_bvh (bvh.wgsl:35-75) pushes the root, and
  *              for every interior node it enters BOTH children before it pops one, so a ray that enters both children all
  *              the way down the deepest path holds max_depth + 1 entries.  Its stack (stack.wgsl, STACK_LEN = 24) is
- *              UNCHECKED: use the tree there only when max_depth <= 23.  An LBVH over real meshes passes that (24 for the
- *              15 k-triangle helmet, profiles/blas_lbvh.md): build such a mesh with vd_bvh_build.  vd_trace*'s 128
- *              entries (with its overflow pass behind them) hold any tree this build can make: 62 key bits bound
- *              max_depth by 62.
+ *              UNCHECKED: use the tree there only when max_depth <= 23.  The UNBOUNDED LBVH over a real mesh does NOT pass
+ *              that: 24 for the 15 k-triangle helmet, 24 to 34 for the knots of profiles/blas_lbvh.md.  A renderer whose
+ *              shader walks the array sets VD_OPT_BLAS_LBVH_MAX_DEPTH to 23 once, and every build then passes by
+ *              construction.  vd_trace*'s 128 entries (with its overflow pass behind them) hold any tree this build can
+ *              make: 62 key bits bound max_depth by 62.
  * vd_bvh_build_lbvh: host pointers, synchronous: stage, build, copy back.  VD_ERR_INVALID_ARG when n_bad_indices != 0.
  * Which builder for which mesh, and the trace rate through either tree: profiles/blas_lbvh.md.                        */
 #define VD_BVH_LBVH_MAX_TRIANGLES (1u << 24)
@@ -578,13 +601,17 @@ int vd_bvh_build_lbvh(VdCtx* ctx, const float* verts_xyz, uint32_t n_vert, uint3
  *                                items[m].status set (no plan is returned) for: a null verts_xyz / indices_inout / nodes;
  *                                tri_cap == 0; node_cap < max(2, 2 * tri_cap); nodes not 16-byte aligned; the capacities, each
  *                                rounded up to 256, adding up to more than VD_BVH_LBVH_MAX_TRIANGLES (the item that crosses
- *                                it); and, without a status, n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS.  The items are judged
+ *                                it); under VD_OPT_BLAS_LBVH_MAX_DEPTH = D, needr(tri_cap) > D (T_m <= tri_cap then keeps every
+ *                                count on the device inside the bound); and, without a status, n_items >
+ *                                VD_BVH_LBVH_BATCH_MAX_ITEMS.  The option is LATCHED here: it sizes the plan's memory and fixes
+ *                                its launch list, and changing it later does not touch an existing plan.  The items are judged
  *                                before the context is looked at, so a null ctx with a bad item names that item too.
  *                                n_items == 0 is VD_OK: a plan that does nothing.
  * vd_bvh_build_lbvh_planned_dev  ONLY ENQUEUES on the context's stream: no host read, no allocation, nothing on the host that
  *                                depends on the counts - it can be captured into a HIP graph and replayed after d_n_tri has
- *                                changed.  The number of launches depends on the plan's capacities alone (19 or 23 kernels and no
- *                                memset, one more kernel when an item carries a mesh_info), never on n_items or the counts.  A null
+ *                                changed.  The number of launches depends on the plan alone (19 or 23 kernels by its capacities, 21 or 25
+ *                                for a depth-bounded plan, no memset, one more kernel when an item carries a mesh_info), never on
+ *                                n_items or the counts.  A null
  *                                plan or d_results is VD_ERR_INVALID_ARG.  One build of a plan at a time (calls on one stream
  *                                are ordered).
  * vd_bvh_lbvh_plan_release       synchronises the stream first (a queued build uses the plan's memory).

@@ -17,10 +17,22 @@
 //   6. blas_lbvh_permute_kernel  the index triples in sorted order.
 // Separate launches are the synchronisation between the passes.
 //
+// VD_OPT_BLAS_LBVH_MAX_DEPTH = D >= 1 (voidin_abi.h: the depth-bounded topology) adds two passes behind pass 3, over work memory
+// that is taken only then:
+//   3b. blas_lbvh_bound_kernel   a sorted position climbs the radix tree twice - once to count its ancestors, which gives every
+//                                ancestor's depth, once to find the TOPMOST one whose Karras split breaks d + 1 + needr(larger
+//                                child) <= D, its switch node - and writes an explicit 64-bit key: (code, position) under no
+//                                switch node, else (the codes' common prefix under the switch node, position - its first position),
+//                                the low word behind the positions' common prefix where the codes are all equal;
+//   3c. blas_lbvh_tree_kernel    again, over those keys (vd_lbvh_range with the low word from an array): above the switch nodes
+//                                the tree is what it was, below one it is the radix tree of the relative positions.
+// Passes 4 - 6 run as they are.  D == 0: none of this is launched, allocated or passed.
+//
 // vd_bvh_lbvh_plan_dev / vd_bvh_build_lbvh_planned_dev build MANY meshes with the same six passes, each run once over one slot space
 // in which every mesh owns a run of 256-slot units, through the same per-mesh __device__ bodies; the sort is tlas.hip's segmented
 // variant (vd_lbvh_batch_sort_boxes).  Every mesh's triangle count is read from device memory by every pass, so the launches -
-// 19 or 23 kernels, no memset, one more kernel for VdMeshInfo bounds - are the same whatever the counts are ("the batched build" below).
+// 19 or 23 kernels (21 or 25 for a plan made under VD_OPT_BLAS_LBVH_MAX_DEPTH), no memset, one more kernel for VdMeshInfo bounds - are
+// the same whatever the counts are ("the batched build" below).
 #include "vd_common.hpp"
 
 #include <new>
@@ -44,10 +56,19 @@ struct LbvhWork {
     unsigned* arrived;      // T
     void* sort;             // vd_lbvh_sort_bytes(T)
 };
+struct LbvhKeys {           // the depth-bounded build only: the explicit 64-bit key of every sorted position
+    unsigned* hi;           // T
+    unsigned* low;          // T
+};
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t work_bytes(uint32_t T) { return 2 * up256(24 * (size_t)T) + up256(12 * (size_t)T) + 7 * up256(4 * (size_t)T) + vd_lbvh_sort_bytes(T); }
-size_t work_bytes_batch(uint32_t S) { return 2 * up256(24 * (size_t)S) + up256(12 * (size_t)S) + 7 * up256(4 * (size_t)S) + vd_lbvh_batch_sort_bytes(S); }
-LbvhWork carve(void* base, uint32_t T) {
+size_t key_bytes(uint32_t T, bool bounded) { return bounded ? 2 * up256(4 * (size_t)T) : 0; }
+size_t work_bytes(uint32_t T, bool bounded) {
+    return 2 * up256(24 * (size_t)T) + up256(12 * (size_t)T) + 7 * up256(4 * (size_t)T) + key_bytes(T, bounded) + vd_lbvh_sort_bytes(T);
+}
+size_t work_bytes_batch(uint32_t S, bool bounded) {
+    return 2 * up256(24 * (size_t)S) + up256(12 * (size_t)S) + 7 * up256(4 * (size_t)S) + key_bytes(S, bounded) + vd_lbvh_batch_sort_bytes(S);
+}
+LbvhWork carve(void* base, uint32_t T, LbvhKeys* bounded /* null: the unbounded build's layout */) {
     char* p = reinterpret_cast<char*>(base);
     auto take = [&](size_t bytes) { char* q = p; p += up256(bytes); return q; };
     LbvhWork w;
@@ -56,6 +77,7 @@ LbvhWork carve(void* base, uint32_t T) {
     w.ibox = reinterpret_cast<float*>(take(24 * (size_t)T));
     unsigned** words[7] = {&w.lo, &w.hi, &w.split, &w.par_int, &w.par_leaf, &w.meta, &w.arrived};
     for (unsigned** a : words) *a = reinterpret_cast<unsigned*>(take(4 * (size_t)T));
+    if (bounded) { bounded->hi = reinterpret_cast<unsigned*>(take(4 * (size_t)T)); bounded->low = reinterpret_cast<unsigned*>(take(4 * (size_t)T)); }
     w.sort = p;
     return w;
 }
@@ -122,13 +144,14 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_boxes_kernel(const float* __
     boxes_body(t, verts, n_vert, indices, tbox, idx_copy, &result->n_bad_indices);
 }
 
-__device__ __forceinline__ void tree_body(int i, const unsigned* __restrict__ keys, unsigned T, unsigned* __restrict__ rlo,
+template <typename Low>
+__device__ __forceinline__ void tree_body(int i, const unsigned* __restrict__ keys, Low low, unsigned T, unsigned* __restrict__ rlo,
                                           unsigned* __restrict__ rhi, unsigned* __restrict__ split, unsigned* __restrict__ par_int,
                                           unsigned* __restrict__ par_leaf, unsigned* __restrict__ arrived) {
     const int N = (int)T;
     if (i >= N - 1) return;
     int lo, hi, gamma;
-    vd_lbvh_range(keys, N, i, lo, hi, gamma);
+    vd_lbvh_range(keys, low, N, i, lo, hi, gamma);
     rlo[i] = (unsigned)lo; rhi[i] = (unsigned)hi; split[i] = (unsigned)gamma;
     const unsigned me = (unsigned)i << 1;
     if (lo == gamma) par_leaf[gamma] = me; else par_int[gamma] = me;
@@ -139,7 +162,61 @@ __device__ __forceinline__ void tree_body(int i, const unsigned* __restrict__ ke
 __global__ __launch_bounds__(kBlock) void blas_lbvh_tree_kernel(const unsigned* __restrict__ keys, unsigned T, unsigned* __restrict__ rlo,
                                                                 unsigned* __restrict__ rhi, unsigned* __restrict__ split, unsigned* __restrict__ par_int,
                                                                 unsigned* __restrict__ par_leaf, unsigned* __restrict__ arrived) {
-    tree_body((int)(blockIdx.x * kBlock + threadIdx.x), keys, T, rlo, rhi, split, par_int, par_leaf, arrived);
+    tree_body((int)(blockIdx.x * kBlock + threadIdx.x), keys, VdLbvhLowIsPosition{}, T, rlo, rhi, split, par_int, par_leaf, arrived);
+}
+
+// ---- the depth bound (VD_OPT_BLAS_LBVH_MAX_DEPTH) --------------------------------------------------------------------------------
+// depth of the radix tree over the integers 0 .. k - 1 cut off at nodes of <= 3 positions
+__host__ __device__ __forceinline__ unsigned needr(unsigned k) { return k <= 3u ? 0u : 31u - (unsigned)__builtin_clz(k - 1u); }
+
+// One thread per sorted position p < T of a mesh of T >= 2: the explicit key of that position.  Every ancestor of the radix leaf
+// covers > 3 positions or lies inside an emitted leaf; only the former have a split to judge, and those are the emitted interior
+// nodes, so the radix depth of one is its depth in the array.  The ancestors BELOW the topmost rule-breaker belong to a subtree that
+// the second tree pass replaces: they are looked at for the same test only, and the topmost one wins.
+__device__ __forceinline__ void bound_body(unsigned p, unsigned T, unsigned D, const unsigned* __restrict__ keys, const unsigned* __restrict__ rlo,
+                                           const unsigned* __restrict__ rhi, const unsigned* __restrict__ split, const unsigned* __restrict__ par_int,
+                                           const unsigned* __restrict__ par_leaf, unsigned* __restrict__ key_hi, unsigned* __restrict__ key_low) {
+    const unsigned code = keys[p];
+    unsigned hw = code, lw = p;
+    if (T > 3u) {
+        const unsigned first = par_leaf[p] >> 1;
+        unsigned len = 1u;                                  // ancestors of the leaf, the root included: 62 key bits bound them
+        for (unsigned k = first; k != 0u && len < 64u; ++len) k = par_int[k] >> 1;
+        unsigned c = kNoParent, k = first;
+        for (unsigned j = 0; j < len; ++j) {               // ancestor j from below is at depth len - 1 - j
+            const unsigned lo = rlo[k], hi = rhi[k];
+            if (hi - lo >= 3u) {
+                const unsigned gm = split[k];
+                if (len - j + needr(max(gm - lo + 1u, hi - gm)) > D) c = k;      // depth + 1 + needr(larger child) > D
+            }
+            k = par_int[k] >> 1;                           // (of the root: not used)
+        }
+        if (c != kNoParent) {
+            const unsigned lo = rlo[c], hi = rhi[c], cl = keys[lo], ch = keys[hi];
+            lw = p - lo;
+            if (cl != ch) {                                 // the end keys share delta = clz < 32 bits, all of the code
+                hw = code & ~(0xffffffffu >> __clz((int)(cl ^ ch)));
+            } else {                                       // ... 32 + clz(lo ^ hi): one code, and the positions' common prefix stays
+                const unsigned sh = 32u - (unsigned)__clz((int)(lo ^ hi));       // 64 - delta; hi - lo >= 3: lo != hi
+                if (sh < 32u) lw |= lo >> sh << sh;
+            }
+        }
+    }
+    key_hi[p] = hw; key_low[p] = lw;
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_bound_kernel(unsigned T, unsigned D, const unsigned* __restrict__ keys, const unsigned* __restrict__ rlo,
+                                                                 const unsigned* __restrict__ rhi, const unsigned* __restrict__ split,
+                                                                 const unsigned* __restrict__ par_int, const unsigned* __restrict__ par_leaf,
+                                                                 unsigned* __restrict__ key_hi, unsigned* __restrict__ key_low) {
+    const unsigned p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= T) return;
+    bound_body(p, T, D, keys, rlo, rhi, split, par_int, par_leaf, key_hi, key_low);
+}
+// the tree pass over explicit keys: every link, range and arrival word of the first one is written again
+__global__ __launch_bounds__(kBlock) void blas_lbvh_tree_keys_kernel(const unsigned* __restrict__ key_hi, const unsigned* __restrict__ key_low, unsigned T,
+                                                                     unsigned* __restrict__ rlo, unsigned* __restrict__ rhi, unsigned* __restrict__ split,
+                                                                     unsigned* __restrict__ par_int, unsigned* __restrict__ par_leaf, unsigned* __restrict__ arrived) {
+    tree_body((int)(blockIdx.x * kBlock + threadIdx.x), key_hi, VdLbvhLowArray{key_low}, T, rlo, rhi, split, par_int, par_leaf, arrived);
 }
 
 // One thread per radix leaf (g < T) and per radix interior node (g - T): those that are EMITTED leaves fold their box and climb.
@@ -306,8 +383,23 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_batch_tree_kernel(const VdLb
                                                                       const unsigned* __restrict__ n_tri, const unsigned* __restrict__ keys, LbvhWork w) {
     const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
     if (b.j + 1u >= b.T) return;                           // interior nodes 0 .. T - 2
-    tree_body((int)b.j, keys + b.slot0, b.T, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0, w.par_int + b.slot0, w.par_leaf + b.slot0,
-              w.arrived + b.slot0);
+    tree_body((int)b.j, keys + b.slot0, VdLbvhLowIsPosition{}, b.T, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0, w.par_int + b.slot0,
+              w.par_leaf + b.slot0, w.arrived + b.slot0);
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_bound_kernel(const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                                       const unsigned* __restrict__ n_tri, const unsigned* __restrict__ keys, unsigned D,
+                                                                       LbvhWork w, LbvhKeys k) {
+    const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
+    if (b.T < 2u || b.j >= b.T) return;
+    bound_body(b.j, b.T, D, keys + b.slot0, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0, w.par_int + b.slot0, w.par_leaf + b.slot0,
+               k.hi + b.slot0, k.low + b.slot0);
+}
+__global__ __launch_bounds__(kBlock) void blas_lbvh_batch_tree_keys_kernel(const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
+                                                                           const unsigned* __restrict__ n_tri, LbvhWork w, LbvhKeys k) {
+    const BatchSlot b = batch_slot(blockIdx.x, segs, unit_seg, n_tri);
+    if (b.j + 1u >= b.T) return;
+    tree_body((int)b.j, k.hi + b.slot0, VdLbvhLowArray{k.low + b.slot0}, b.T, w.lo + b.slot0, w.hi + b.slot0, w.split + b.slot0, w.par_int + b.slot0,
+              w.par_leaf + b.slot0, w.arrived + b.slot0);
 }
 // blocks [0, n_units): the radix leaves; blocks [n_units, 2 n_units): the radix interior nodes
 __global__ __launch_bounds__(kBlock) void blas_lbvh_batch_fit_kernel(unsigned n_units, const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
@@ -366,15 +458,29 @@ struct VdBvhLbvhPlan {
     unsigned* d_bad = nullptr;                             // per item: indices >= n_vert counted by the boxes pass; 0 between builds
     VdLbvhBatchLayout layout = {};
     LbvhWork w = {};
+    unsigned max_depth = 0;                                // VD_OPT_BLAS_LBVH_MAX_DEPTH as it was when the plan was made; 0: unbounded
+    LbvhKeys k = {};                                       // ... and the explicit keys, when it is not
 };
 
 namespace {
+
+// VD_OPT_BLAS_LBVH_MAX_DEPTH as the builds read it: 0 = unbounded (the default), at most 62
+unsigned depth_bound(const VdCtx* ctx) {
+    const long long d = ctx->option(VD_OPT_BLAS_LBVH_MAX_DEPTH, 0);
+    return (unsigned)(d > 62 ? 62 : d);
+}
 
 int check_args(VdCtx* ctx, const void* verts, const void* indices, uint32_t n_tri, const void* nodes, uint32_t node_cap) {
     if (!verts || !indices || !nodes) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: null vertices / indices / nodes");
     if (n_tri == 0u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: n_tri == 0");
     if (n_tri > VD_BVH_LBVH_MAX_TRIANGLES) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: n_tri > VD_BVH_LBVH_MAX_TRIANGLES");
     if (node_cap < (n_tri < 2u ? 2u : 2u * n_tri)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: node_cap < max(2, 2 * n_tri)");
+    const unsigned D = depth_bound(ctx);
+    if (D && needr(n_tri) > D) {
+        snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build_lbvh: VD_OPT_BLAS_LBVH_MAX_DEPTH = %u cannot hold %u triangles: the smallest bound that can is %u",
+                 D, n_tri, needr(n_tri));
+        return VD_ERR_INVALID_ARG;
+    }
     return VD_OK;
 }
 
@@ -391,8 +497,10 @@ int vd_bvh_build_lbvh_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
     if (!d_result) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_dev: null result");
     if ((reinterpret_cast<uintptr_t>(d_out_nodes) & 15u) != 0u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_dev: d_out_nodes is not 16-byte aligned");
     const uint32_t T = n_tri;
-    if ((rc = vd_ensure(ctx, &ctx->blas_lbvh_state, &ctx->blas_lbvh_state_bytes, work_bytes(T)))) return rc;
-    const LbvhWork w = carve(ctx->blas_lbvh_state, T);
+    const unsigned D = depth_bound(ctx);
+    if ((rc = vd_ensure(ctx, &ctx->blas_lbvh_state, &ctx->blas_lbvh_state_bytes, work_bytes(T, D != 0u)))) return rc;
+    LbvhKeys k = {};
+    const LbvhWork w = carve(ctx->blas_lbvh_state, T, D ? &k : nullptr);
     hipStream_t st = ctx->stream;
     VD_HIP_CHECK(ctx, hipMemsetAsync(d_result, 0, sizeof(VdBvhLbvhResult), st));
     vd_time_begin(ctx);
@@ -402,6 +510,11 @@ int vd_bvh_build_lbvh_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
     if ((rc = vd_lbvh_sort_boxes(ctx, w.tbox, T, w.sort, &keys, &vals))) { vd_time_end(ctx); return rc; }
     if (T >= 2u) {
         hipLaunchKernelGGL(blas_lbvh_tree_kernel, dim3(grid), dim3(kBlock), 0, st, keys, T, w.lo, w.hi, w.split, w.par_int, w.par_leaf, w.arrived);
+        if (D && T > 3u) {                                 // (a mesh of <= 3 triangles is one leaf under any bound)
+            hipLaunchKernelGGL(blas_lbvh_bound_kernel, dim3(grid), dim3(kBlock), 0, st, T, D, keys, w.lo, w.hi, w.split, w.par_int, w.par_leaf, k.hi, k.low);
+            hipLaunchKernelGGL(blas_lbvh_tree_keys_kernel, dim3(grid), dim3(kBlock), 0, st, k.hi, k.low, T, w.lo, w.hi, w.split, w.par_int, w.par_leaf,
+                               w.arrived);
+        }
         hipLaunchKernelGGL(blas_lbvh_fit_kernel, dim3((2u * T + kBlock - 1u) / kBlock), dim3(kBlock), 0, st, T, vals, w.tbox, w.lo, w.hi, w.split,
                            w.par_int, w.par_leaf, w.ibox, w.meta, w.arrived);
     }
@@ -456,6 +569,7 @@ int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items
         return VD_ERR_INVALID_ARG;
     }
     for (uint32_t m = 0; m < n_items; ++m) items[m].status = VD_OK;
+    const unsigned D = ctx ? depth_bound(ctx) : 0u;        // latched: the plan's memory and launch list follow it, later changes of the option do not
     std::vector<BatchItemDev> h_items;
     std::vector<VdLbvhSeg> h_segs;
     std::vector<unsigned> h_unit_seg;
@@ -470,6 +584,12 @@ int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items
             if (it.tri_cap > VD_BVH_LBVH_MAX_TRIANGLES) return fail_item(ctx, items, m, "tri_cap > VD_BVH_LBVH_MAX_TRIANGLES");
             if (it.node_cap < (it.tri_cap < 2u ? 2u : 2u * it.tri_cap)) return fail_item(ctx, items, m, "node_cap < max(2, 2 * tri_cap)");
             if ((reinterpret_cast<uintptr_t>(it.nodes) & 15u) != 0u) return fail_item(ctx, items, m, "nodes is not 16-byte aligned");
+            if (D && needr(it.tri_cap) > D) {               // T_m <= tri_cap: every count the device can hold then fits the bound
+                char what[160];
+                snprintf(what, sizeof(what), "VD_OPT_BLAS_LBVH_MAX_DEPTH = %u cannot hold tri_cap = %u: the smallest bound that can is %u", D, it.tri_cap,
+                         needr(it.tri_cap));
+                return fail_item(ctx, items, m, what);
+            }
             const unsigned n_units = (it.tri_cap + kVdLbvhBatchUnit - 1u) / kVdLbvhBatchUnit;
             if (slots + (uint64_t)n_units * kVdLbvhBatchUnit > VD_BVH_LBVH_MAX_TRIANGLES)
                 return fail_item(ctx, items, m, "the capacities, each rounded up to 256, add up to more than VD_BVH_LBVH_MAX_TRIANGLES");
@@ -489,6 +609,7 @@ int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items
         if (!ctx) return VD_ERR_INVALID_ARG;               // (the items are judged without a context: nothing above touches the device)
         VdBvhLbvhPlan* p = new VdBvhLbvhPlan();
         p->n_items = n_items; p->n_slots = (unsigned)slots; p->n_bound_chunks = (unsigned)h_bound_chunks.size();
+        p->max_depth = D;
         *out = p;
         if (n_items == 0) return VD_OK;
         const uint32_t S = p->n_slots;
@@ -497,7 +618,7 @@ int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items
                      o_bchunks = o_ext + up256(24 * (size_t)n_items), o_bkeys = o_bchunks + up256(8 * h_bound_chunks.size()),
                      o_bdone = o_bkeys + up256(24 * (size_t)n_items), o_bad = o_bdone + up256(4 * (size_t)n_items),
                      o_work = o_bad + up256(4 * (size_t)n_items),
-                     total = o_work + work_bytes_batch(S);
+                     total = o_work + work_bytes_batch(S, D != 0u);
         std::vector<int> h_keys(6 * (size_t)n_items);
         for (size_t m = 0; m < n_items; ++m)
             for (int q = 0; q < 6; ++q) h_keys[6 * m + q] = q < 3 ? kVdKeyPosInf : kVdKeyNegInf;
@@ -526,7 +647,7 @@ int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items
         p->layout.d_unit_seg = reinterpret_cast<const unsigned*>(base + o_unit);
         p->layout.d_chunks = reinterpret_cast<const uint2*>(base + o_echunks);
         p->layout.d_ext = reinterpret_cast<unsigned*>(base + o_ext);
-        p->w = carve(base + o_work, S);                    // .sort: vd_lbvh_batch_sort_bytes(S)
+        p->w = carve(base + o_work, S, D ? &p->k : nullptr);      // .sort: vd_lbvh_batch_sort_bytes(S)
     } catch (const std::bad_alloc&) {
         if (*out) { delete *out; *out = nullptr; }
         if (!ctx) return VD_ERR_OOM;
@@ -554,6 +675,10 @@ int vd_bvh_build_lbvh_planned_dev(VdCtx* ctx, const VdBvhLbvhPlan* plan, const u
     int rc;
     if ((rc = vd_lbvh_batch_sort_boxes(ctx, w.tbox, &L, d_n_tri, w.sort, &keys, &vals))) { vd_time_end(ctx); return rc; }
     hipLaunchKernelGGL(blas_lbvh_batch_tree_kernel, dim3(n_units), dim3(kBlock), 0, st, L.d_segs, L.d_unit_seg, d_n_tri, keys, w);
+    if (plan->max_depth) {
+        hipLaunchKernelGGL(blas_lbvh_batch_bound_kernel, dim3(n_units), dim3(kBlock), 0, st, L.d_segs, L.d_unit_seg, d_n_tri, keys, plan->max_depth, w, plan->k);
+        hipLaunchKernelGGL(blas_lbvh_batch_tree_keys_kernel, dim3(n_units), dim3(kBlock), 0, st, L.d_segs, L.d_unit_seg, d_n_tri, w, plan->k);
+    }
     hipLaunchKernelGGL(blas_lbvh_batch_fit_kernel, dim3(2u * n_units), dim3(kBlock), 0, st, n_units, L.d_segs, L.d_unit_seg, d_n_tri, vals, w);
     hipLaunchKernelGGL(blas_lbvh_batch_number_kernel, dim3(n_units), dim3(kBlock), 0, st, plan->d_items, L.d_segs, L.d_unit_seg, d_n_tri, vals, w, d_results);
     hipLaunchKernelGGL(blas_lbvh_batch_permute_kernel, dim3(n_units), dim3(kBlock), 0, st, plan->d_items, L.d_segs, L.d_unit_seg, d_n_tri, vals, w.idx,

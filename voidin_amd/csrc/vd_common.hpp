@@ -275,29 +275,42 @@ typedef unsigned long long vd_u64;
 // ---- Karras' binary radix tree over sorted 30-bit codes (tlas.hip: lbvh_tree_kernel, blas_lbvh.hip: blas_lbvh_tree_kernel) ----
 // length of the common prefix of the codes at sorted positions i and j (-1 outside the array); equal codes: their positions decide,
 // i.e. the keys are the 64-bit words code << 32 | sorted position
-__device__ __forceinline__ int vd_lbvh_delta(const unsigned* __restrict__ keys, int n, int i, int j) {
+// The LOW word of those keys: the sorted position itself (VdLbvhLowIsPosition - nothing is read), or a word per position from an
+// array (VdLbvhLowArray: the depth-bounded bottom level, blas_lbvh.hip, whose keys are explicit).  Either way the 64-bit keys are
+// distinct and ascending.
+struct VdLbvhLowIsPosition { __device__ __forceinline__ unsigned operator()(int i) const { return (unsigned)i; } };
+struct VdLbvhLowArray { const unsigned* __restrict__ low; __device__ __forceinline__ unsigned operator()(int i) const { return low[i]; } };
+template <typename Low>
+__device__ __forceinline__ int vd_lbvh_delta(const unsigned* __restrict__ keys, Low low, int n, int i, int j) {
     if (j < 0 || j >= n) return -1;
     const unsigned a = keys[i], b = keys[j];
-    return a != b ? __clz((int)(a ^ b)) : 32 + __clz((int)((unsigned)i ^ (unsigned)j));
+    return a != b ? __clz((int)(a ^ b)) : 32 + __clz((int)(low(i) ^ low(j)));
+}
+__device__ __forceinline__ int vd_lbvh_delta(const unsigned* __restrict__ keys, int n, int i, int j) {
+    return vd_lbvh_delta(keys, VdLbvhLowIsPosition{}, n, i, j);
 }
 // Karras 2012 for interior node i of n - 1: the sorted positions [lo, hi] it covers and its split - the left child covers
 // [lo, gamma], the right one [gamma + 1, hi]; a child of one position is that leaf, any other is interior node gamma / gamma + 1.
-__device__ __forceinline__ void vd_lbvh_range(const unsigned* __restrict__ keys, int N, int i, int& lo, int& hi, int& gamma) {
-    const int d = vd_lbvh_delta(keys, N, i, i + 1) - vd_lbvh_delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = vd_lbvh_delta(keys, N, i, i - d);
+template <typename Low>
+__device__ __forceinline__ void vd_lbvh_range(const unsigned* __restrict__ keys, Low low, int N, int i, int& lo, int& hi, int& gamma) {
+    const int d = vd_lbvh_delta(keys, low, N, i, i + 1) - vd_lbvh_delta(keys, low, N, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = vd_lbvh_delta(keys, low, N, i, i - d);
     int lmax = 2;
-    while (vd_lbvh_delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
+    while (vd_lbvh_delta(keys, low, N, i, i + lmax * d) > dmin) lmax <<= 1;
     int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1) if (vd_lbvh_delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
+    for (int t = lmax >> 1; t >= 1; t >>= 1) if (vd_lbvh_delta(keys, low, N, i, i + (l + t) * d) > dmin) l += t;
     const int j = i + l * d;
-    const int dnode = vd_lbvh_delta(keys, N, i, j);
+    const int dnode = vd_lbvh_delta(keys, low, N, i, j);
     int sp = 0;
     for (int t = (l + 1) >> 1; ; t = (t + 1) >> 1) {
-        if (vd_lbvh_delta(keys, N, i, i + (sp + t) * d) > dnode) sp += t;
+        if (vd_lbvh_delta(keys, low, N, i, i + (sp + t) * d) > dnode) sp += t;
         if (t == 1) break;
     }
     gamma = i + sp * d + min(d, 0);
     lo = min(i, j); hi = max(i, j);
+}
+__device__ __forceinline__ void vd_lbvh_range(const unsigned* __restrict__ keys, int N, int i, int& lo, int& hi, int& gamma) {
+    vd_lbvh_range(keys, VdLbvhLowIsPosition{}, N, i, lo, hi, gamma);
 }
 
 // boxes in segment m of a batched slot space: the count on the device, read as the capacity when it is above it (or absent)
