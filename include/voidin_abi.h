@@ -423,6 +423,7 @@ int vd_expand_mask_dev(VdCtx* ctx, const uint64_t* d_mask, uint32_t n_total, uin
  * in 32 survives.
  *   vd_mask_to_indices_dev  ascending list of the set bits of a shard mask (ceil(n_inst/64) words) as
  *                           GLOBAL instance indices first_instance + i; *d_out_count = their number.
+ *                           Words [*d_out_count, n_inst) of d_out_indices are NOT written.
  *   vd_indices_to_draws_dev d_out[k] = the command emit_draws writes for instance d_indices[k] with
  *                           instance_count = 1 (mesh fields through d_mesh_ids, as vd_expand_mask_dev).
  * vd_indices_to_draws(concat over shards of vd_mask_to_indices(vd_cull_mask(shard))) == vd_cull_compact
@@ -501,6 +502,7 @@ int vd_cull_batch(VdCtx* ctx, const VdCameraUniform* camera,
  *   out_nodes      capacity node_cap (>= 2*n_tri as the reference allocates, blas.rs:52)
  *   out_n_nodes    number of nodes used (`nodes.truncate(pool)`, blas.rs:93); node 1 is
  *                  the reference's never-used all-zero slot
+ * No byte of out_nodes past n_nodes is written.
  * VD_ERR_DEGENERATE where the reference would crash.
  *
  * vd_bvh_build_dev takes device pointers but - unlike the per-frame `*_dev` entry points - it
