@@ -1,10 +1,15 @@
 """Run-time half of the fence-free hand-offs: every kernel with an inter-workgroup protocol is run many
 times and every result is compared byte for byte with the first one (and the first one with the oracle elsewhere in
-the suite).  A race shows up as a run that differs.  tests/test_isa_protocols.py checks the emitted code."""
+the suite).  A race shows up as a run that differs.  tests/test_isa_protocols.py checks the emitted code.
+Repeating ONE input finds nondeterminism, not staleness: tests/test_gpu_handoffs.py alternates inputs, and so does the
+second half of the refit climb here."""
 import numpy as np
 import pytest
 import torch
 
+import handoff_cases
+from conftest import fields_equal, first_difference
+from voidin_amd import abi
 from voidin_amd import dist as vdist
 from voidin_amd import synth
 
@@ -45,7 +50,11 @@ def test_split_cull_scan_hand_off_repeats(ctx):
         del d_i, d_o
 
 
-def test_tlas_refit_climb_repeats(ctx):
+def test_tlas_refit_climb_repeats(ctx, oracle):
+    """200 refits of the instances the tree was built from give the build back - every box handed over then holds the bytes it
+    held one launch earlier, so a STALE read passes.  Then 200 refits that alternate between those instances and a moved copy
+    (every translation and scale changed: tests/handoff_cases.py), each compared with the oracle's refit of that set: every
+    interior box differs from what the launch before left in its place."""
     meshes = synth.mesh_infos()
     d_m = ctx.upload(meshes)
     for n, wide in ((32768, False), (65536, True)):
@@ -57,6 +66,20 @@ def test_tlas_refit_climb_repeats(ctx):
         for it in range(200):
             ctx.tlas_refit_dev(d_i, n, d_m, len(meshes), d_t, wide=wide)
             assert torch.equal(d_t, built), f"refit n={n}: run {it} differs from the build"
+        dt = abi.TLAS_NODE_WIDE if wide else abi.TLAS_NODE
+        topology = built.cpu().numpy().view(dt)
+        sets = [inst, handoff_cases.moved(inst)]
+        want = [oracle.tlas_refit(s, meshes, topology) for s in sets]
+        assert fields_equal(want[0], topology), "the oracle's refit of the built instances is the build"
+        holds, kept = handoff_cases.teeth(want[0], want[1], handoff_cases.tlas_interior(want[0]))
+        assert holds, f"{kept} interior boxes do not change between the two sets"
+        d_sets, d_want = [ctx.upload(s) for s in sets], [ctx.upload(w) for w in want]
+        for it in range(200):
+            d_i.copy_(d_sets[it & 1])
+            ctx.tlas_refit_dev(d_i, n, d_m, len(meshes), d_t, wide=wide)
+            if not torch.equal(d_t, d_want[it & 1]):
+                got = d_t.cpu().numpy().view(dt)
+                pytest.fail(f"refit n={n}: run {it} ({'moved' if it & 1 else 'built'} instances) differs from the oracle at {first_difference(got, want[it & 1])}")
 
 
 def test_several_workgroup_tlas_chain_repeats(ctx):
