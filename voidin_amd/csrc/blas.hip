@@ -30,6 +30,7 @@
 // restores the reference's pre-order node numbering locally from (start, -count) keys.  C: DFS numbering of
 // the (small) top tree on the host while phase B runs, parallel copy-out.
 #include "vd_common.hpp"
+#include "blas_top.hpp"      // the top tree's structs and its numbering: host only, tested on the CPU
 
 #include <chrono>
 #include <type_traits>
@@ -1266,14 +1267,7 @@ struct Seg {
     int bin_min[3][8][3], bin_max[3][8][3];
 };
 
-struct TopNode {                      // temporary top-tree node
-    float mn[3]; unsigned start;
-    float mx[3]; unsigned count;
-    unsigned kind;                    // 0 leaf, 1 big interior, 2 small root
-    unsigned left;                    // tmp id of the left child (right = left + 1) for kind 1
-    unsigned small;                   // index into the small-root list for kind 2
-    unsigned pad;
-};
+// (TopNode, the temporary top-tree node: blas_top.hpp)
 
 struct MidRoot { unsigned start, count, node, pad; int cbk[6]; int pad2[2]; };   // a segment the mid tier takes over
 
@@ -2400,8 +2394,7 @@ __global__ __launch_bounds__(kMidThreads, (VD_MID_WGS * kMidThreads / 64 + 3) / 
 // =============================================================================================
 // Phase C: copy-out.
 // =============================================================================================
-struct TopOut { unsigned final_index, pair, mesh; };   // pair = final left_first for interior nodes; mesh: whose node array
-
+// (TopOut, a top-tree node's final place: blas_top.hpp)
 __global__ void c_top_kernel(const TopNode* top, const TopOut* tout, unsigned n_top, const MeshDesc* __restrict__ meshes) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_top) return;
@@ -2515,259 +2508,339 @@ struct Arena {
     }
 };
 
-// One mesh of a build, host side.  d_out == nullptr: packed - the mesh's nodes follow the previous mesh's in the batch's
-// shared node buffer (MeshPool's `bvh_index = bvh_nodes.len()` bookkeeping, mesh/mod.rs:320-345).
-struct BuildMesh {
-    const float* d_verts; uint32_t n_vert; uint32_t* d_idx; uint32_t n_tri; VdBvhNode* d_out; uint32_t node_cap;
-    uint32_t out_n_nodes, out_first;
+// =============================================================================================
+// The build, host side: bvh_build_batch_impl (below) is the sequence of these stages.
+// =============================================================================================
+
+// The sizes of one build; build_plan launches nothing.
+struct BuildPlan {
+    size_t T;                                                   // triangles of all meshes
+    unsigned n_chunks;                                          // chunks of kChunk triangles, every mesh's rounded up
+    unsigned seg_cap, mid_cap, item_cap, small_cap, top_cap;    // entries of the device-side lists
+    bool wide_pay;                                              // Pay8 instead of Pay4
 };
 
-int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_packed, uint64_t packed_cap, uint32_t packed_first,
-                         uint32_t* out_failed_mesh) {
+int build_plan(VdCtx* ctx, const BuildMesh* hm, uint32_t K, BuildPlan* pl) {
     size_t T = 0;
     unsigned n_chunks = 0;
     for (uint32_t m = 0; m < K; ++m) { T += hm[m].n_tri; n_chunks += (hm[m].n_tri + kChunk - 1u) / kChunk; }
     if (T > 0x3fffffffu) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build: more than 2^30 - 1 triangles in one build");
-    const uint32_t n_tri = (uint32_t)T;
-    const unsigned seg_cap = (unsigned)(T / kSmallMax + 2);
-    const unsigned mid_cap = seg_cap;
-    const unsigned item_cap = (unsigned)(T / kItem + seg_cap + 2);
-    const unsigned small_cap = (unsigned)(T / 4 + 2);
-    const unsigned top_cap = (unsigned)(2 * (size_t)small_cap + 4 * (size_t)seg_cap + 2 * (size_t)K + 64);
-    const bool wide_pay = T > kPay4Max || ctx->option(VD_OPT_BLAS_WIDE_PAYLOAD, 0) != 0;
-    // ---- scratch layout ----
-    Arena probe{nullptr, 0};
-    auto layout = [&](Arena& a, bool) {
-        struct P { u32x2 *pay0, *pay1; f32x4 *cent, *cent1; TriBox *boxes, *boxes1; unsigned *bits21, *ids32;
-                   unsigned *falsepos, *truepos, *final_ids, *stack, *idx_copy;
-                   unsigned char* is_u; Seg *seg0, *seg1; MidRoot* mid; unsigned *item_seg, *item_cnt, *item_cnt1, *item_pre; TopNode* top; SmallRoot* small;
-                   unsigned* sub_interior; TmpNode* subnodes; unsigned short* submap; LevelCtl* ctl; int* root_keys; TopOut* tout; unsigned* root_pair;
-                   MeshDesc* meshes; unsigned* bad_mesh;
-#ifdef VD_TUNING
-                   unsigned long long* cls_prof;
-#endif
-                 } p;
-        // payload ping-pong: 4 bytes per triangle up to 2^25 triangles, 8 beyond (allocated for the width in use)
-        const size_t pay_words = wide_pay ? T : (T + 1) / 2;
-        p.pay0 = a.take<u32x2>(pay_words); p.pay1 = a.take<u32x2>(pay_words);
-        p.cent = a.take<f32x4>(T); p.boxes = a.take<TriBox>(T); p.cent1 = a.take<f32x4>(T); p.boxes1 = a.take<TriBox>(T);
-        p.bits21 = a.take<unsigned>(T); p.ids32 = a.take<unsigned>(T);
-        p.falsepos = a.take<unsigned>(T); p.truepos = a.take<unsigned>(T);
-        p.final_ids = a.take<unsigned>(T); p.stack = a.take<unsigned>(T); p.idx_copy = a.take<unsigned>(3 * T);
-        p.is_u = a.take<unsigned char>(T);
-        p.seg0 = a.take<Seg>(seg_cap); p.seg1 = a.take<Seg>(seg_cap); p.mid = a.take<MidRoot>(mid_cap);
-        p.item_seg = a.take<unsigned>(item_cap); p.item_cnt = a.take<unsigned>(item_cap); p.item_cnt1 = a.take<unsigned>(item_cap); p.item_pre = a.take<unsigned>(item_cap + 1);
-        p.top = a.take<TopNode>(top_cap); p.small = a.take<SmallRoot>(small_cap); p.sub_interior = a.take<unsigned>(small_cap);
-        p.subnodes = a.take<TmpNode>(2 * T + 2); p.submap = a.take<unsigned short>(2 * T + 2); p.ctl = a.take<LevelCtl>(1); p.root_keys = a.take<int>(16 * (size_t)K);
-        p.tout = a.take<TopOut>(top_cap); p.root_pair = a.take<unsigned>(small_cap);
-        p.meshes = a.take<MeshDesc>(K); p.bad_mesh = a.take<unsigned>(1);
-#ifdef VD_TUNING
-        p.cls_prof = a.take<unsigned long long>(64 * 64);  // 64 replicas of 64 counters
-#endif
-        return p;
-    };
-    (void)layout(probe, false);
-    int rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, probe.off + 256);
-    if (rc) return rc;
-    Arena arena{reinterpret_cast<char*>(ctx->scratch), 0};
-    auto P = layout(arena, true);
-    hipStream_t st = ctx->stream;
-    VdBvhBuildStats& stats = ctx->bvh_stats;
-    stats = VdBvhBuildStats{};
-    auto t_mark = std::chrono::steady_clock::now();
-    auto lap = [&](float& slot) {
-        const auto now = std::chrono::steady_clock::now();
-        slot += std::chrono::duration<float, std::milli>(now - t_mark).count();
-        t_mark = now;
-    };
+    pl->T = T; pl->n_chunks = n_chunks;
+    pl->seg_cap = (unsigned)(T / kSmallMax + 2);
+    pl->mid_cap = pl->seg_cap;
+    pl->item_cap = (unsigned)(T / kItem + pl->seg_cap + 2);
+    pl->small_cap = (unsigned)(T / 4 + 2);
+    pl->top_cap = (unsigned)(2 * (size_t)pl->small_cap + 4 * (size_t)pl->seg_cap + 2 * (size_t)K + 64);
+    pl->wide_pay = T > kPay4Max || ctx->option(VD_OPT_BLAS_WIDE_PAYLOAD, 0) != 0;
+    return VD_OK;
+}
 
-    vd_time_begin(ctx);
-    // pinned staging, first use: [MeshDesc K][root keys 16 K] (phase C lays it out again for its own tables)
-    const size_t off_keys = sizeof(MeshDesc) * (size_t)K;
-    {
-        int rc_s = vd_ensure_host(ctx, off_keys + 64 * (size_t)K + 64);
-        if (rc_s) return rc_s;
+// The build's device scratch, carved from ctx->scratch (a null-based arena gives its size).
+struct Scratch {
+    u32x2 *pay0, *pay1; f32x4 *cent, *cent1; TriBox *boxes, *boxes1; unsigned *bits21, *ids32;
+    unsigned *falsepos, *truepos, *final_ids, *stack, *idx_copy;
+    unsigned char* is_u; Seg *seg0, *seg1; MidRoot* mid; unsigned *item_seg, *item_cnt, *item_cnt1, *item_pre; TopNode* top; SmallRoot* small;
+    unsigned* sub_interior; TmpNode* subnodes; unsigned short* submap; LevelCtl* ctl; int* root_keys; TopOut* tout; unsigned* root_pair;
+    MeshDesc* meshes; unsigned* bad_mesh;
+#ifdef VD_TUNING
+    unsigned long long* cls_prof;
+#endif
+};
+
+Scratch carve_scratch(Arena& a, const BuildPlan& pl, uint32_t K) {
+    Scratch p;
+    const size_t T = pl.T;
+    // payload ping-pong: 4 bytes per triangle up to 2^25 triangles, 8 beyond (allocated for the width in use)
+    const size_t pay_words = pl.wide_pay ? T : (T + 1) / 2;
+    p.pay0 = a.take<u32x2>(pay_words); p.pay1 = a.take<u32x2>(pay_words);
+    p.cent = a.take<f32x4>(T); p.boxes = a.take<TriBox>(T); p.cent1 = a.take<f32x4>(T); p.boxes1 = a.take<TriBox>(T);
+    p.bits21 = a.take<unsigned>(T); p.ids32 = a.take<unsigned>(T);
+    p.falsepos = a.take<unsigned>(T); p.truepos = a.take<unsigned>(T);
+    p.final_ids = a.take<unsigned>(T); p.stack = a.take<unsigned>(T); p.idx_copy = a.take<unsigned>(3 * T);
+    p.is_u = a.take<unsigned char>(T);
+    p.seg0 = a.take<Seg>(pl.seg_cap); p.seg1 = a.take<Seg>(pl.seg_cap); p.mid = a.take<MidRoot>(pl.mid_cap);
+    p.item_seg = a.take<unsigned>(pl.item_cap); p.item_cnt = a.take<unsigned>(pl.item_cap); p.item_cnt1 = a.take<unsigned>(pl.item_cap);
+    p.item_pre = a.take<unsigned>(pl.item_cap + 1);
+    p.top = a.take<TopNode>(pl.top_cap); p.small = a.take<SmallRoot>(pl.small_cap); p.sub_interior = a.take<unsigned>(pl.small_cap);
+    p.subnodes = a.take<TmpNode>(2 * T + 2); p.submap = a.take<unsigned short>(2 * T + 2); p.ctl = a.take<LevelCtl>(1); p.root_keys = a.take<int>(16 * (size_t)K);
+    p.tout = a.take<TopOut>(pl.top_cap); p.root_pair = a.take<unsigned>(pl.small_cap);
+    p.meshes = a.take<MeshDesc>(K); p.bad_mesh = a.take<unsigned>(1);
+#ifdef VD_TUNING
+    p.cls_prof = a.take<unsigned long long>(64 * 64);  // 64 replicas of 64 counters
+#endif
+    return p;
+}
+
+// The two layouts of the pinned staging (ctx->host_stage), one after the other: what the precompute uploads, and - the
+// staging may have moved in between - the top tree with what phase C uploads.
+struct PinnedIn { MeshDesc* desc; int* keys; };
+PinnedIn carve_pinned_in(Arena& a, uint32_t K) {
+    PinnedIn p;
+    p.desc = a.take<MeshDesc>(K); p.keys = a.take<int>(16 * (size_t)K);
+    return p;
+}
+struct PinnedTop { TopNode* top; TopOut* out; unsigned *ord, *sub, *root_pair; MeshDesc* desc; };
+PinnedTop carve_pinned_top(Arena& a, unsigned n_top, unsigned n_small, uint32_t K) {
+    PinnedTop p;
+    p.top = a.take<TopNode>(n_top); p.out = a.take<TopOut>(n_top); p.ord = a.take<unsigned>(n_top);
+    p.sub = a.take<unsigned>(n_small); p.root_pair = a.take<unsigned>(n_small); p.desc = a.take<MeshDesc>(K);
+    return p;
+}
+
+// An error return must not leave what it queued running over scratch the next call reuses: armed with a stream, waits for
+// it when the scope ends.
+struct StreamJoin {
+    hipStream_t s = nullptr;
+    ~StreamJoin() { if (s) (void)hipStreamSynchronize(s); }
+};
+
+// What the stages of one build hand on.
+struct Build {
+    VdCtx* ctx; uint32_t K;
+    BuildPlan pl; Scratch P; ArrSet sets[2];
+    LevelCtl h_ctl;               // the control words as the host last read them
+    unsigned n_top, n_small;      // final once the mid tier is through
+    unsigned mid_early;           // mid-tier roots already started on the second stream
+    StreamJoin aux_join;          // ... which an error return waits for
+};
+
+struct Lap {                      // host milliseconds since the last lap, added to a slot of the stats
+    std::chrono::steady_clock::time_point mark = std::chrono::steady_clock::now();
+    void operator()(float& slot) {
+        const auto now = std::chrono::steady_clock::now();
+        slot += std::chrono::duration<float, std::milli>(now - mark).count();
+        mark = now;
     }
-    MeshDesc* h_desc = reinterpret_cast<MeshDesc*>(ctx->host_stage);
-    {
-        int* h_keys = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->host_stage) + off_keys);
-        unsigned base = 0, chunk0 = 0;
-        for (uint32_t m = 0; m < K; ++m) {
-            h_desc[m] = MeshDesc{hm[m].d_verts, hm[m].d_idx, hm[m].d_idx, hm[m].d_out, hm[m].n_vert, hm[m].n_tri, base, chunk0};
-            base += hm[m].n_tri; chunk0 += (hm[m].n_tri + kChunk - 1u) / kChunk;
-            static const int init[16] = {kBig, kBig, kBig, -kBig - 1, -kBig - 1, -kBig - 1, kBig, kBig, kBig, -kBig - 1, -kBig - 1, -kBig - 1, 0, 0, 0, 0};
-            memcpy(h_keys + 16 * (size_t)m, init, sizeof(init));
-        }
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(P.meshes, h_desc, sizeof(MeshDesc) * (size_t)K, hipMemcpyHostToDevice, st));
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(P.root_keys, h_keys, 64 * (size_t)K, hipMemcpyHostToDevice, st));
-        VD_HIP_CHECK(ctx, hipMemsetAsync(P.ctl, 0, sizeof(LevelCtl), st));
-        VD_HIP_CHECK(ctx, hipMemsetAsync(P.bad_mesh, 0xff, 4, st));
-        VD_HIP_CHECK(ctx, hipMemsetAsync(P.is_u, 0, T, st));
+};
+
+// The second stream and its event: made when a build first needs them.
+int ensure_aux(VdCtx* ctx) {
+    if (!ctx->aux_stream) VD_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
+    if (!ctx->ev_aux) VD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
+    return VD_OK;
+}
+
+// LevelCtl::err as a refusal.  A degenerate input comes first everywhere; which other bits a site takes for an internal
+// error, and what it calls it, is the site's.
+int ctl_refusal(VdCtx* ctx, unsigned err, unsigned internal_bits, const char* internal_msg) {
+    if (err & ERR_DEGENERATE)
+        VD_FAIL(ctx, VD_ERR_DEGENERATE, "vd_bvh_build: every split candidate rejected (the reference builder crashes on this input)");
+    if (err & internal_bits) VD_FAIL(ctx, VD_ERR_HIP, internal_msg);
+    return VD_OK;
+}
+
+// The mesh table: every mesh's arrays and where its triangles and chunks start in the batch.  d_packed == nullptr: before
+// place_nodes, a packed mesh has no node array yet (nothing before phase C looks at it).
+void fill_mesh_table(MeshDesc* desc, const BuildMesh* hm, uint32_t K, VdBvhNode* d_packed) {
+    unsigned base = 0, chunk0 = 0;
+    for (uint32_t m = 0; m < K; ++m) {
+        VdBvhNode* out = hm[m].d_out || !d_packed ? hm[m].d_out : d_packed + hm[m].out_first;
+        desc[m] = MeshDesc{hm[m].d_verts, hm[m].d_idx, hm[m].d_idx, out, hm[m].n_vert, hm[m].n_tri, base, chunk0};
+        base += hm[m].n_tri; chunk0 += (hm[m].n_tri + kChunk - 1u) / kChunk;
     }
+}
+
+// Uploads the mesh table and the neutral root keys, clears the control words, runs the precompute, the roots and the first
+// level's set-up, and waits for them: B.h_ctl.  Refuses an index >= n_vert.
+int precompute(Build& B, const BuildMesh* hm, uint32_t* out_failed_mesh) {
+    VdCtx* ctx = B.ctx;
+    const Scratch& P = B.P;
+    const uint32_t K = B.K;
+    hipStream_t st = ctx->stream;
+    Arena probe{nullptr, 0};
+    (void)carve_pinned_in(probe, K);
+    const int rc = vd_ensure_host(ctx, probe.off);
+    if (rc) return rc;
+    Arena pinned{reinterpret_cast<char*>(ctx->host_stage), 0};
+    const PinnedIn h = carve_pinned_in(pinned, K);
+    fill_mesh_table(h.desc, hm, K, nullptr);
+    for (uint32_t m = 0; m < K; ++m) {
+        static const int init[16] = {kBig, kBig, kBig, -kBig - 1, -kBig - 1, -kBig - 1, kBig, kBig, kBig, -kBig - 1, -kBig - 1, -kBig - 1, 0, 0, 0, 0};
+        memcpy(h.keys + 16 * (size_t)m, init, sizeof(init));
+    }
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(P.meshes, h.desc, sizeof(MeshDesc) * (size_t)K, hipMemcpyHostToDevice, st));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(P.root_keys, h.keys, 64 * (size_t)K, hipMemcpyHostToDevice, st));
+    VD_HIP_CHECK(ctx, hipMemsetAsync(P.ctl, 0, sizeof(LevelCtl), st));
+    VD_HIP_CHECK(ctx, hipMemsetAsync(P.bad_mesh, 0xff, 4, st));
+    VD_HIP_CHECK(ctx, hipMemsetAsync(P.is_u, 0, B.pl.T, st));
 #ifdef VD_TUNING
     VD_HIP_CHECK(ctx, hipMemsetAsync(P.cls_prof, 0, 64 * 64 * sizeof(unsigned long long), st));
 #endif
-    hipLaunchKernelGGL(blas_precompute_kernel, dim3(n_chunks), dim3(256), 0, st, P.meshes, K, P.idx_copy, P.cent, P.boxes, P.root_keys, &P.ctl->err, P.bad_mesh);
-    const ArrSet sets[2] = {ArrSet{P.cent, P.boxes}, ArrSet{P.cent1, P.boxes1}};
+    hipLaunchKernelGGL(blas_precompute_kernel, dim3(B.pl.n_chunks), dim3(256), 0, st, P.meshes, K, P.idx_copy, P.cent, P.boxes, P.root_keys, &P.ctl->err, P.bad_mesh);
     hipLaunchKernelGGL(c_root_kernel, dim3((K + 63u) / 64u), dim3(64), 0, st, P.top, P.root_keys, P.meshes, K, P.small, P.ctl, P.seg0, P.mid);
-    hipLaunchKernelGGL(a_boundary_kernel, dim3(1), dim3(1024), 0, st, (const Seg*)nullptr, P.seg0, P.ctl, P.top, P.small, P.is_u, top_cap, small_cap, P.mid, mid_cap, 0u,
-                       P.item_seg, 0);      // the first level's set-up
-
-    // ---- phase A: level loop ----
-    Seg* seg_cur = P.seg0; Seg* seg_next = P.seg1;
-    LevelCtl h_ctl;
+    hipLaunchKernelGGL(a_boundary_kernel, dim3(1), dim3(1024), 0, st, (const Seg*)nullptr, P.seg0, P.ctl, P.top, P.small, P.is_u, B.pl.top_cap, B.pl.small_cap, P.mid,
+                       B.pl.mid_cap, 0u, P.item_seg, 0);      // the first level's set-up
     unsigned h_bad = kNone;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_ctl, P.ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(&B.h_ctl, P.ctl, sizeof(LevelCtl), hipMemcpyDeviceToHost, st));
     VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_bad, P.bad_mesh, 4, hipMemcpyDeviceToHost, st));
     VD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (h_ctl.err & ERR_BAD_INDEX) {
+    if (B.h_ctl.err & ERR_BAD_INDEX) {
         if (out_failed_mesh) *out_failed_mesh = h_bad;
         snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build: index >= n_vert (mesh %u of the build)", h_bad);
         return VD_ERR_INVALID_ARG;
     }
-    unsigned n_seg = h_ctl.n_seg;
-    int levels = 0;
-    stats.kernel_launches = 3;
-    lap(stats.ms_precompute);
-    // one level of phase A; PayT = Pay4 / Pay8 (see there)
-    unsigned n_launch = 0;
-    auto run_level = [&](auto pay_tag, unsigned n_seg_now, size_t active_bound, Seg* seg_cur, Seg* seg_next, int level, bool scan_free) {
-        using PayT = decltype(pay_tag);
-        typedef typename PayT::T PT;
-        const ArrSet cur = sets[level & 1], nxt = sets[(level + 1) & 1];
-        // upper bound of items this level: sum ceil(count/kItem) <= active/kItem + n_seg, `active` = the triangles still in
-        // segments of phase A (it only falls from level to level; the last levels of an uneven tree hold a few segments, and a
-        // grid of 8 200 workgroups costs 4.9 us to start even if every one of them leaves at once: profiles/r05_blas_issue_cost.log)
-        const unsigned items_ub = (unsigned)(std::min<size_t>(T, active_bound) / kItem) + n_seg_now + 1;
-        PT* src = reinterpret_cast<PT*>(P.pay0); PT* dst = reinterpret_cast<PT*>(P.pay1);
-        unsigned* const cnt[2] = {P.item_cnt, P.item_cnt1};      // round c counts in cnt[c & 1]
-        hipLaunchKernelGGL((a_bits_kernel<PayT>), dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, cur.cent, P.bits21, cnt[0]);
-        for (int c = 0; c <= kCand; ++c) {
-            const int cc = c < kCand ? c : -1;       // -1: final re-shuffle with each segment's best plane
-            if (c == kCand) {
-                hipLaunchKernelGGL((a_bin_kernel<PayT>), dim3((items_ub + kBinItems - 1) / kBinItems), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, cur.boxes,
-                                   P.is_u, P.bits21);
-                hipLaunchKernelGGL(a_eval_kernel, dim3(n_seg_now), dim3(64), 0, st, seg_cur, P.ctl, cur.boxes);
-            }
-            // the true counts of round c: from a_bits (c = 0), from the a_apply of round c - 1, or - the final shuffle, whose
-            // plane a_eval has only just chosen - from a_count, which also puts that axis' bits into the 4-byte payload
-            if (c == kCand)
-                hipLaunchKernelGGL((a_count_kernel<PayT>), dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, cc, cnt[c & 1], P.bits21, 1);
-            const int mode = c + 1 >= kCand ? 0 : ((c + 1) % 7 == 0 ? 2 : 1);
-            unsigned* const cnt_next = mode ? cnt[(c + 1) & 1] : nullptr;
-            // prefixes: from a_scan, or - segments of <= 1024 items - added up by the workgroups themselves (prefix_begin)
-            const unsigned* pre = scan_free ? cnt[c & 1] : P.item_pre;
-            if (!scan_free) hipLaunchKernelGGL(a_scan_kernel, dim3(1), dim3(1024), 0, st, seg_cur, P.ctl, cnt[c & 1], P.item_pre);
-            auto ranks = scan_free ? a_ranks_kernel<PayT, true> : a_ranks_kernel<PayT, false>;
-            const RoundK rk = make_round<PayT>(cc);
-            hipLaunchKernelGGL(ranks, dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, rk, pre, P.falsepos, P.truepos, cnt_next);
-            auto apply = scan_free ? (mode == 0 ? a_apply_kernel<PayT, 0, true> : mode == 1 ? a_apply_kernel<PayT, 1, true> : a_apply_kernel<PayT, 2, true>)
-                                   : (mode == 0 ? a_apply_kernel<PayT, 0, false> : mode == 1 ? a_apply_kernel<PayT, 1, false> : a_apply_kernel<PayT, 2, false>);
-            hipLaunchKernelGGL(apply, dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, dst, rk, pre,
-                               P.falsepos, P.truepos, P.is_u, P.bits21, cnt_next);
-            n_launch += scan_free ? 2u : 3u;
-            PT* t = src; src = dst; dst = t;
-        }
-        // 22 swaps: the arrangement is back in pay0
-        hipLaunchKernelGGL((a_child_kernel<PayT>), dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, reinterpret_cast<const PT*>(P.pay0), cur.boxes,
-                           cur.cent, nxt.boxes, nxt.cent);
-        // this level's children + the next level's set-up: one launch (a_boundary_kernel)
-        hipLaunchKernelGGL(a_boundary_kernel, dim3((n_seg_now + kFinalChunk - 1u) / kFinalChunk), dim3(1024), 0, st, seg_cur, seg_next, P.ctl, P.top, P.small, P.is_u,
-                           top_cap, small_cap, P.mid, mid_cap, (unsigned)((level + 1) & 1), P.item_seg, 1);
-    };
-    // The mid tier does not wait for the last levels: segments <= kMidMax go to the mid list as they appear, and after
-    // every level the roots listed since the last launch start on the second stream, beside the levels that remain
-    // (those stream through HBM, the mid tier computes out of LDS); the rest of the list follows on the main stream.  Disjoint position ranges, shared
-    // lists appended by atomics - and no numbering depends on the order in which top nodes or small roots were listed.
-    unsigned mid_early = 0;
-    struct AuxJoin {          // an error return must not leave the early launch running over scratch the next call reuses
-        hipStream_t s = nullptr;
-        ~AuxJoin() { if (s) (void)hipStreamSynchronize(s); }
-    } aux_join;
-    auto launch_mid = [&](hipStream_t on, unsigned first, unsigned count) -> int {
-        if (!ctx->mid_lds_opt_in) {   // per context (= per device), not per process
-            VD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(blas_mid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MidLds)));
-            ctx->mid_lds_opt_in = true;
-        }
-        hipLaunchKernelGGL(blas_mid_kernel, dim3(count), dim3(kMidThreads), sizeof(MidLds), on, P.mid, &P.ctl->n_mid, P.ids32, sets[0], sets[1],
-                           P.ctl, P.top, P.small, top_cap, small_cap, first);
-        stats.kernel_launches += 1;
-        return VD_OK;
-    };
-    // The host stays ONE LEVEL AHEAD of the device: level L + 1 is queued - its grids sized by what level L's exact counts
-    // allow (at most twice as many segments, none larger than level L's largest) - before the host waits for the control
-    // words level L leaves behind, so the device never idles for the round trip (~60 us per level before).  The kernels
-    // read the true counts from the control words; the level queued after the last real one finds no items and falls
-    // through.  Control words travel into pinned memory (two slots) behind an event each.
-    if (n_seg > 0) {
-        if (!ctx->lvl_pinned) VD_HIP_CHECK(ctx, hipHostMalloc(&ctx->lvl_pinned, 2 * sizeof(LevelCtl)));
-        for (int e = 0; e < 2; ++e)
-            if (!ctx->ev_lvl[e]) VD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_lvl[e], hipEventDisableTiming));
-        LevelCtl* h_pin = reinterpret_cast<LevelCtl*>(ctx->lvl_pinned);
-        struct MainJoin {        // an error return must not leave queued levels running over scratch the next call reuses
-            hipStream_t s = nullptr;
-            ~MainJoin() { if (s) (void)hipStreamSynchronize(s); }
-        } main_join;
-        main_join.s = st;
-        auto queue_level = [&](unsigned n_seg_bound, unsigned max_count_bound, size_t active_bound) {
-            const bool scan_free = (max_count_bound + kItem - 1) / kItem <= 1024u;
-            if (wide_pay) run_level(Pay8{}, n_seg_bound, active_bound, seg_cur, seg_next, levels, scan_free);
-            else run_level(Pay4{}, n_seg_bound, active_bound, seg_cur, seg_next, levels, scan_free);
-            Seg* t = seg_cur; seg_cur = seg_next; seg_next = t;
-            stats.kernel_launches += 5 + n_launch; n_launch = 0;
-            levels += 1;
-        };
-        queue_level(n_seg, h_ctl.max_count, h_ctl.active);   // level 0: exact
-        unsigned bound = (unsigned)std::min<size_t>(2 * (size_t)n_seg, seg_cap), max_bound = h_ctl.max_count;
-        size_t active_bound = h_ctl.active;
-        for (;;) {
-            const int slot = (levels - 1) & 1;               // the control words the last queued level leaves
-            VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_pin[slot], P.ctl, sizeof(LevelCtl), hipMemcpyDeviceToHost, st));
-            VD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_lvl[slot], st));
-            if (levels > 4096) VD_FAIL(ctx, VD_ERR_HIP, "vd_bvh_build: level loop did not terminate");
-            queue_level(bound, max_bound, active_bound);     // one level ahead
-            VD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_lvl[slot]));
-            h_ctl = h_pin[slot];
-            if (h_ctl.err & ERR_DEGENERATE)
-                VD_FAIL(ctx, VD_ERR_DEGENERATE, "vd_bvh_build: every split candidate rejected (the reference builder crashes on this input)");
-            if (h_ctl.err) VD_FAIL(ctx, VD_ERR_HIP, "vd_bvh_build: internal capacity exceeded");
-            n_seg = h_ctl.n_seg;
-            if (n_seg == 0) { levels -= 1; break; }          // the level just queued is empty
-            bound = (unsigned)std::min<size_t>(2 * (size_t)n_seg, seg_cap); max_bound = h_ctl.max_count; active_bound = h_ctl.active;
-            if (h_ctl.n_mid >= mid_early + kMidEarlyMin) {   // enough new roots to be worth a launch beside the levels in flight
-                if (!ctx->aux_stream) VD_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-                if (!ctx->ev_aux) VD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
-                const int rc_m = launch_mid(ctx->aux_stream, mid_early, h_ctl.n_mid - mid_early);    // these roots are complete: the event above is behind their level
-                if (rc_m) return rc_m;
-                VD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_aux, ctx->aux_stream));
-                mid_early = h_ctl.n_mid;
-                aux_join.s = ctx->aux_stream;
-            }
-        }
-        main_join.s = nullptr;
-    }
-    stats.levels_phase_a = (uint32_t)levels;
-    lap(stats.ms_phase_a);
+    ctx->bvh_stats.kernel_launches = 3;
+    return VD_OK;
+}
 
-    // ---- mid tier: segments of kSmallMax < n <= kMidMax, one workgroup each, down to small roots ----
-    if (h_ctl.n_mid) {
-        if (h_ctl.n_mid > mid_early) { const int rc_m = launch_mid(st, mid_early, h_ctl.n_mid - mid_early); if (rc_m) return rc_m; }
-        if (mid_early) VD_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_aux, 0));
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_ctl, P.ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
-        VD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        if (h_ctl.err & ERR_DEGENERATE)
-            VD_FAIL(ctx, VD_ERR_DEGENERATE, "vd_bvh_build: every split candidate rejected (the reference builder crashes on this input)");
-        if (h_ctl.err) VD_FAIL(ctx, VD_ERR_HIP, "vd_bvh_build: internal capacity exceeded");
-        aux_join.s = nullptr;     // the main stream waited for the early launch and the host for the main stream
+// One level of phase A, queued; PayT = Pay4 / Pay8 (see there).  Returns the launches of its rounds (the five others are
+// the same for every level).
+template <typename PayT>
+unsigned queue_level(const Build& B, unsigned n_seg_now, size_t active_bound, Seg* seg_cur, Seg* seg_next, int level, bool scan_free) {
+    typedef typename PayT::T PT;
+    const Scratch& P = B.P;
+    hipStream_t st = B.ctx->stream;
+    const ArrSet cur = B.sets[level & 1], nxt = B.sets[(level + 1) & 1];
+    // upper bound of items this level: sum ceil(count/kItem) <= active/kItem + n_seg, `active` = the triangles still in
+    // segments of phase A (it only falls from level to level; the last levels of an uneven tree hold a few segments, and a
+    // grid of 8 200 workgroups costs 4.9 us to start even if every one of them leaves at once: profiles/r05_blas_issue_cost.log)
+    const unsigned items_ub = (unsigned)(std::min<size_t>(B.pl.T, active_bound) / kItem) + n_seg_now + 1;
+    PT* src = reinterpret_cast<PT*>(P.pay0); PT* dst = reinterpret_cast<PT*>(P.pay1);
+    unsigned* const cnt[2] = {P.item_cnt, P.item_cnt1};      // round c counts in cnt[c & 1]
+    unsigned n_launch = 0;
+    hipLaunchKernelGGL((a_bits_kernel<PayT>), dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, cur.cent, P.bits21, cnt[0]);
+    for (int c = 0; c <= kCand; ++c) {
+        const int cc = c < kCand ? c : -1;       // -1: final re-shuffle with each segment's best plane
+        if (c == kCand) {
+            hipLaunchKernelGGL((a_bin_kernel<PayT>), dim3((items_ub + kBinItems - 1) / kBinItems), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, cur.boxes,
+                               P.is_u, P.bits21);
+            hipLaunchKernelGGL(a_eval_kernel, dim3(n_seg_now), dim3(64), 0, st, seg_cur, P.ctl, cur.boxes);
+        }
+        // the true counts of round c: from a_bits (c = 0), from the a_apply of round c - 1, or - the final shuffle, whose
+        // plane a_eval has only just chosen - from a_count, which also puts that axis' bits into the 4-byte payload
+        if (c == kCand)
+            hipLaunchKernelGGL((a_count_kernel<PayT>), dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, cc, cnt[c & 1], P.bits21, 1);
+        const int mode = c + 1 >= kCand ? 0 : ((c + 1) % 7 == 0 ? 2 : 1);
+        unsigned* const cnt_next = mode ? cnt[(c + 1) & 1] : nullptr;
+        // prefixes: from a_scan, or - segments of <= 1024 items - added up by the workgroups themselves (prefix_begin)
+        const unsigned* pre = scan_free ? cnt[c & 1] : P.item_pre;
+        if (!scan_free) hipLaunchKernelGGL(a_scan_kernel, dim3(1), dim3(1024), 0, st, seg_cur, P.ctl, cnt[c & 1], P.item_pre);
+        auto ranks = scan_free ? a_ranks_kernel<PayT, true> : a_ranks_kernel<PayT, false>;
+        const RoundK rk = make_round<PayT>(cc);
+        hipLaunchKernelGGL(ranks, dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, rk, pre, P.falsepos, P.truepos, cnt_next);
+        auto apply = scan_free ? (mode == 0 ? a_apply_kernel<PayT, 0, true> : mode == 1 ? a_apply_kernel<PayT, 1, true> : a_apply_kernel<PayT, 2, true>)
+                               : (mode == 0 ? a_apply_kernel<PayT, 0, false> : mode == 1 ? a_apply_kernel<PayT, 1, false> : a_apply_kernel<PayT, 2, false>);
+        hipLaunchKernelGGL(apply, dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, src, dst, rk, pre,
+                           P.falsepos, P.truepos, P.is_u, P.bits21, cnt_next);
+        n_launch += scan_free ? 2u : 3u;
+        PT* t = src; src = dst; dst = t;
     }
-    lap(stats.ms_mid);
-    // ---- phase B ----
-    const unsigned n_small = h_ctl.n_small, n_top = h_ctl.n_top;
-    stats.n_top_nodes = n_top; stats.n_small_roots = n_small; stats.n_mid_roots = h_ctl.n_mid;
+    // 22 swaps: the arrangement is back in pay0
+    hipLaunchKernelGGL((a_child_kernel<PayT>), dim3(items_ub), dim3(256), 0, st, seg_cur, P.item_seg, P.ctl, reinterpret_cast<const PT*>(P.pay0), cur.boxes,
+                       cur.cent, nxt.boxes, nxt.cent);
+    // this level's children + the next level's set-up: one launch (a_boundary_kernel)
+    hipLaunchKernelGGL(a_boundary_kernel, dim3((n_seg_now + kFinalChunk - 1u) / kFinalChunk), dim3(1024), 0, st, seg_cur, seg_next, P.ctl, P.top, P.small, P.is_u,
+                       B.pl.top_cap, B.pl.small_cap, P.mid, B.pl.mid_cap, (unsigned)((level + 1) & 1), P.item_seg, 1);
+    return n_launch;
+}
+
+// The mid tier for `count` roots of the list from `first` on, on stream `on`.
+int launch_mid(Build& B, hipStream_t on, unsigned first, unsigned count) {
+    VdCtx* ctx = B.ctx;
+    const Scratch& P = B.P;
+    if (!ctx->mid_lds_opt_in) {   // per context (= per device), not per process
+        VD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(blas_mid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MidLds)));
+        ctx->mid_lds_opt_in = true;
+    }
+    hipLaunchKernelGGL(blas_mid_kernel, dim3(count), dim3(kMidThreads), sizeof(MidLds), on, P.mid, &P.ctl->n_mid, P.ids32, B.sets[0], B.sets[1],
+                       P.ctl, P.top, P.small, B.pl.top_cap, B.pl.small_cap, first);
+    ctx->bvh_stats.kernel_launches += 1;
+    return VD_OK;
+}
+
+// The mid tier does not wait for the last levels: segments <= kMidMax go to the mid list as they appear, and after
+// every level the roots listed since the last launch start on the second stream, beside the levels that remain
+// (those stream through HBM, the mid tier computes out of LDS); the rest of the list follows on the main stream.  Disjoint position ranges, shared
+// lists appended by atomics - and no numbering depends on the order in which top nodes or small roots were listed.
+int launch_mid_early(Build& B) {
+    VdCtx* ctx = B.ctx;
+    int rc = ensure_aux(ctx);
+    if (rc) return rc;
+    if ((rc = launch_mid(B, ctx->aux_stream, B.mid_early, B.h_ctl.n_mid - B.mid_early))) return rc;    // these roots are complete: the level's event is behind them
+    VD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_aux, ctx->aux_stream));
+    B.mid_early = B.h_ctl.n_mid;
+    B.aux_join.s = ctx->aux_stream;
+    return VD_OK;
+}
+
+// Phase A, the level loop.  The host stays ONE LEVEL AHEAD of the device: level L + 1 is queued - its grids sized by what
+// level L's exact counts allow (at most twice as many segments, none larger than level L's largest) - before the host waits
+// for the control words level L leaves behind, so the device never idles for the round trip (~60 us per level before).  The
+// kernels read the true counts from the control words; the level queued after the last real one finds no items and falls
+// through.  Control words travel into pinned memory (two slots) behind an event each.
+int phase_a(Build& B) {
+    VdCtx* ctx = B.ctx;
+    hipStream_t st = ctx->stream;
+    LevelCtl& h_ctl = B.h_ctl;
+    unsigned n_seg = h_ctl.n_seg;
+    if (n_seg == 0) return VD_OK;
+    if (!ctx->lvl_pinned) VD_HIP_CHECK(ctx, hipHostMalloc(&ctx->lvl_pinned, 2 * sizeof(LevelCtl)));
+    for (int e = 0; e < 2; ++e)
+        if (!ctx->ev_lvl[e]) VD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_lvl[e], hipEventDisableTiming));
+    LevelCtl* h_pin = reinterpret_cast<LevelCtl*>(ctx->lvl_pinned);
+    StreamJoin main_join;
+    main_join.s = st;
+    Seg* seg_cur = B.P.seg0; Seg* seg_next = B.P.seg1;
+    int levels = 0;
+    auto queue = [&](unsigned n_seg_bound, unsigned max_count_bound, size_t active_bound) {
+        const bool scan_free = (max_count_bound + kItem - 1) / kItem <= 1024u;
+        const unsigned n_launch = B.pl.wide_pay ? queue_level<Pay8>(B, n_seg_bound, active_bound, seg_cur, seg_next, levels, scan_free)
+                                                : queue_level<Pay4>(B, n_seg_bound, active_bound, seg_cur, seg_next, levels, scan_free);
+        Seg* t = seg_cur; seg_cur = seg_next; seg_next = t;
+        ctx->bvh_stats.kernel_launches += 5 + n_launch;
+        levels += 1;
+    };
+    queue(n_seg, h_ctl.max_count, h_ctl.active);   // level 0: exact
+    unsigned bound = (unsigned)std::min<size_t>(2 * (size_t)n_seg, B.pl.seg_cap), max_bound = h_ctl.max_count;
+    size_t active_bound = h_ctl.active;
+    for (;;) {
+        const int slot = (levels - 1) & 1;               // the control words the last queued level leaves
+        VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_pin[slot], B.P.ctl, sizeof(LevelCtl), hipMemcpyDeviceToHost, st));
+        VD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_lvl[slot], st));
+        if (levels > 4096) VD_FAIL(ctx, VD_ERR_HIP, "vd_bvh_build: level loop did not terminate");
+        queue(bound, max_bound, active_bound);           // one level ahead
+        VD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_lvl[slot]));
+        h_ctl = h_pin[slot];
+        int rc = ctl_refusal(ctx, h_ctl.err, ~0u, "vd_bvh_build: internal capacity exceeded");
+        if (rc) return rc;
+        n_seg = h_ctl.n_seg;
+        if (n_seg == 0) { levels -= 1; break; }          // the level just queued is empty
+        bound = (unsigned)std::min<size_t>(2 * (size_t)n_seg, B.pl.seg_cap); max_bound = h_ctl.max_count; active_bound = h_ctl.active;
+        if (h_ctl.n_mid >= B.mid_early + kMidEarlyMin && (rc = launch_mid_early(B))) return rc;   // enough new roots to be worth a launch beside the levels in flight
+    }
+    main_join.s = nullptr;
+    ctx->bvh_stats.levels_phase_a = (uint32_t)levels;
+    return VD_OK;
+}
+
+// Mid tier: segments of kSmallMax < n <= kMidMax, one workgroup each, down to small roots.  What the early launches left,
+// on the main stream, which then waits for them; the host waits for the main stream.
+int mid_tier(Build& B) {
+    VdCtx* ctx = B.ctx;
+    hipStream_t st = ctx->stream;
+    if (!B.h_ctl.n_mid) return VD_OK;
+    int rc = VD_OK;
+    if (B.h_ctl.n_mid > B.mid_early && (rc = launch_mid(B, st, B.mid_early, B.h_ctl.n_mid - B.mid_early))) return rc;
+    if (B.mid_early) VD_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_aux, 0));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(&B.h_ctl, B.P.ctl, sizeof(LevelCtl), hipMemcpyDeviceToHost, st));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if ((rc = ctl_refusal(ctx, B.h_ctl.err, ~0u, "vd_bvh_build: internal capacity exceeded"))) return rc;
+    B.aux_join.s = nullptr;     // the main stream waited for the early launch and the host for the main stream
+    return VD_OK;
+}
+
+// Phase B: the small subtrees.  The top tree is final before it starts (the stream was synchronised after the last level /
+// the mid tier), so it is fetched on the second stream and walked WHILE phase B runs (top_preorder); what depends on
+// phase B - how many node pairs each small subtree takes, h->sub - is fetched behind it.
+int phase_b(Build& B, PinnedTop* h, unsigned* ord_end) {
+    VdCtx* ctx = B.ctx;
+    const Scratch& P = B.P;
+    hipStream_t st = ctx->stream;
+    const unsigned n_small = B.n_small, n_top = B.n_top;
     if (n_small) {
         hipLaunchKernelGGL(b_order_kernel, dim3(1), dim3(1024), 0, st, P.small, &P.ctl->n_small, P.root_pair);   // root_pair is free until phase C
         hipLaunchKernelGGL(blas_small_kernel, dim3(n_small), dim3(64 * kSubWaves), sizeof(WaveLds) + sizeof(WaveQueues), st, P.small, &P.ctl->n_small, P.ids32,
-                           sets[0], sets[1], P.subnodes, P.submap, P.sub_interior, P.final_ids, &P.ctl->err, P.stack, P.root_pair
+                           B.sets[0], B.sets[1], P.subnodes, P.submap, P.sub_interior, P.final_ids, &P.ctl->err, P.stack, P.root_pair
 #ifdef VD_TUNING
                            , P.cls_prof
 #endif
@@ -2777,111 +2850,81 @@ int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_pac
         ctx->dbg_ptr2 = P.cls_prof;
 #endif
     }
-    // ---- phase C: DFS numbering of the top tree on the host ----
-    // The top tree is final before phase B starts (the stream was synchronised after the last level / the mid tier), so
-    // it is fetched on a second stream and walked WHILE phase B runs; what depends on phase B - how many node pairs
-    // each small subtree takes - enters in one linear pass over the recorded pre-order afterwards.  Pinned staging:
-    // [TopNode n_top][TopOut n_top][order n_top][sub n_small][root_pair n_small]
-    const size_t off_out = sizeof(TopNode) * (size_t)n_top, off_ord = off_out + sizeof(TopOut) * (size_t)n_top;
-    const size_t off_sub = off_ord + 4 * (size_t)n_top, off_rp = off_sub + 4 * (size_t)(n_small ? n_small : 1);
-    const size_t off_desc = (off_rp + 4 * (size_t)(n_small ? n_small : 1) + 15) & ~(size_t)15;
-    int rc_h = vd_ensure_host(ctx, off_desc + sizeof(MeshDesc) * (size_t)K);
-    if (rc_h) return rc_h;
-    if (!ctx->aux_stream) VD_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-    char* hs = reinterpret_cast<char*>(ctx->host_stage);
-    TopNode* h_top = reinterpret_cast<TopNode*>(hs);
-    TopOut* h_out = reinterpret_cast<TopOut*>(hs + off_out);
-    unsigned* h_ord = reinterpret_cast<unsigned*>(hs + off_ord);
-    unsigned* h_sub = reinterpret_cast<unsigned*>(hs + off_sub);
-    unsigned* h_root_pair = reinterpret_cast<unsigned*>(hs + off_rp);
-    h_desc = reinterpret_cast<MeshDesc*>(hs + off_desc);          // the staging may have moved: written again below
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(h_top, P.top, sizeof(TopNode) * n_top, hipMemcpyDeviceToHost, ctx->aux_stream));
+    Arena probe{nullptr, 0};
+    (void)carve_pinned_top(probe, n_top, n_small, B.K);
+    int rc = vd_ensure_host(ctx, probe.off);
+    if (rc) return rc;
+    if ((rc = ensure_aux(ctx))) return rc;
+    Arena pinned{reinterpret_cast<char*>(ctx->host_stage), 0};
+    *h = carve_pinned_top(pinned, n_top, n_small, B.K);
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(h->top, P.top, sizeof(TopNode) * n_top, hipMemcpyDeviceToHost, ctx->aux_stream));
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->aux_stream));
-    // pre-order walk of every mesh's tree, one after the other: an interior node takes the next pair when visited
-    // (blas.rs:110-112); h_ord records the visits, mesh boundaries in ord_end
-    std::vector<unsigned> ord_end(K);
-    unsigned n_ord = 0;
-    {
-        std::vector<unsigned> stk;
-        for (uint32_t m = 0; m < K; ++m) {
-            stk.push_back(2u * m);
-            while (!stk.empty()) {
-                const unsigned v = stk.back(); stk.pop_back();
-                const TopNode& t = h_top[v];
-                h_out[v].mesh = m;
-                if (t.kind == 0u) continue;
-                h_ord[n_ord++] = v;
-                if (t.kind == 1u) {
-                    stk.push_back(t.left + 1);
-                    stk.push_back(t.left);
-                }
-            }
-            h_out[2u * m + 1u].mesh = m; h_out[2u * m + 1u].final_index = 1u; h_out[2u * m + 1u].pair = 0u;
-            ord_end[m] = n_ord;
-        }
-    }
-    if (n_small) VD_HIP_CHECK(ctx, hipMemcpyAsync(h_sub, P.sub_interior, 4 * (size_t)n_small, hipMemcpyDeviceToHost, st));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(&h_ctl, P.ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    top_preorder(h->top, B.K, h->out, h->ord, ord_end);
+    if (n_small) VD_HIP_CHECK(ctx, hipMemcpyAsync(h->sub, P.sub_interior, 4 * (size_t)n_small, hipMemcpyDeviceToHost, st));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(&B.h_ctl, P.ctl, sizeof(LevelCtl), hipMemcpyDeviceToHost, st));
     VD_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (h_ctl.err & ERR_DEGENERATE)
-        VD_FAIL(ctx, VD_ERR_DEGENERATE, "vd_bvh_build: every split candidate rejected (the reference builder crashes on this input)");
-    if (h_ctl.err & ERR_INTERNAL) VD_FAIL(ctx, VD_ERR_HIP, "vd_bvh_build: phase B work list stalled");
-    lap(stats.ms_phase_b);
-    uint64_t packed_at = packed_first;
-    {
-        unsigned k = 0, base = 0, chunk0 = 0;
-        for (uint32_t m = 0; m < K; ++m) {
-            unsigned pool = 2;
-            h_out[2u * m].final_index = 0;
-            for (; k < ord_end[m]; ++k) {
-                const unsigned v = h_ord[k];
-                const TopNode& t = h_top[v];
-                const unsigned pair = pool;
-                h_out[v].pair = pair;
-                if (t.kind == 2u) {
-                    h_root_pair[t.small] = pair;
-                    pool += 2u * h_sub[t.small];
-                } else {
-                    pool += 2;
-                    h_out[t.left].final_index = pair;
-                    h_out[t.left + 1].final_index = pair + 1;
-                }
-            }
-            VdBvhNode* out = hm[m].d_out;
-            hm[m].out_n_nodes = pool; hm[m].out_first = 0;
-            if (out) {
-                if (pool > hm[m].node_cap) {
-                    if (out_failed_mesh) *out_failed_mesh = m;
-                    snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build: node_cap too small (mesh %u of the build needs %u nodes)", m, pool);
-                    return VD_ERR_INVALID_ARG;
-                }
-            } else {
-                if (packed_at + pool > packed_cap || packed_at + pool > 0xffffffffull) {     // out_first_node / bvh_index are 32-bit
-                    if (out_failed_mesh) *out_failed_mesh = m;
-                    snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build_batch: the packed node buffer is full at mesh %u (or its node indices pass 2^32)", m);
-                    return VD_ERR_INVALID_ARG;
-                }
-                out = d_packed + packed_at;
-                hm[m].out_first = (uint32_t)packed_at;
-                packed_at += pool;
-            }
-            h_desc[m] = MeshDesc{hm[m].d_verts, hm[m].d_idx, hm[m].d_idx, out, hm[m].n_vert, hm[m].n_tri, base, chunk0};
-            base += hm[m].n_tri; chunk0 += (hm[m].n_tri + kChunk - 1u) / kChunk;
-        }
-    }
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(P.meshes, h_desc, sizeof(MeshDesc) * (size_t)K, hipMemcpyHostToDevice, st));      // now with every mesh's node array
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(P.tout, h_out, sizeof(TopOut) * n_top, hipMemcpyHostToDevice, st));
-    if (n_small) VD_HIP_CHECK(ctx, hipMemcpyAsync(P.root_pair, h_root_pair, 4 * (size_t)n_small, hipMemcpyHostToDevice, st));
+    return ctl_refusal(ctx, B.h_ctl.err, ERR_INTERNAL, "vd_bvh_build: phase B work list stalled");
+}
+
+// Phase C, the copy-out into every mesh's own buffers: the mesh table - now with every mesh's node array -, the final
+// numbers of the top tree and the small roots' places, and the four kernels that write nodes and indices.
+int phase_c(Build& B, const BuildMesh* hm, const PinnedTop& h, VdBvhNode* d_packed) {
+    VdCtx* ctx = B.ctx;
+    const Scratch& P = B.P;
+    hipStream_t st = ctx->stream;
+    const unsigned n_small = B.n_small, n_top = B.n_top;
+    fill_mesh_table(h.desc, hm, B.K, d_packed);
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(P.meshes, h.desc, sizeof(MeshDesc) * (size_t)B.K, hipMemcpyHostToDevice, st));
+    VD_HIP_CHECK(ctx, hipMemcpyAsync(P.tout, h.out, sizeof(TopOut) * n_top, hipMemcpyHostToDevice, st));
+    if (n_small) VD_HIP_CHECK(ctx, hipMemcpyAsync(P.root_pair, h.root_pair, 4 * (size_t)n_small, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(c_top_kernel, dim3((n_top + 63) / 64), dim3(64), 0, st, P.top, P.tout, n_top, P.meshes);
     if (n_small) hipLaunchKernelGGL(c_sub_kernel, dim3(n_small), dim3(256), 0, st, P.small, P.sub_interior, P.root_pair, n_small, P.subnodes, P.submap, P.tout, P.meshes);
-    hipLaunchKernelGGL(c_ids_big_leaves_kernel, dim3((n_top + 63) / 64), dim3(64), 0, st, P.top, n_top, P.ids32, sets[0], sets[1], P.final_ids);
-    hipLaunchKernelGGL(c_permute_kernel, dim3(n_chunks), dim3(256), 0, st, P.final_ids, P.idx_copy, P.meshes, K);
+    hipLaunchKernelGGL(c_ids_big_leaves_kernel, dim3((n_top + 63) / 64), dim3(64), 0, st, P.top, n_top, P.ids32, B.sets[0], B.sets[1], P.final_ids);
+    hipLaunchKernelGGL(c_permute_kernel, dim3(B.pl.n_chunks), dim3(256), 0, st, P.final_ids, P.idx_copy, P.meshes, B.K);
     vd_time_end(ctx);
     VD_HIP_CHECK(ctx, hipGetLastError());
     VD_HIP_CHECK(ctx, hipStreamSynchronize(st));   // the pinned staging is reused by the next build
-    stats.kernel_launches += (n_small ? 2 : 0) + 3;
+    ctx->bvh_stats.kernel_launches += (n_small ? 2 : 0) + 3;
+    return VD_OK;
+}
+
+// K meshes in one build.  A refusal between vd_time_begin and vd_time_end leaves the timing bracket open, as it always did.
+int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_packed, uint64_t packed_cap, uint32_t packed_first,
+                         uint32_t* out_failed_mesh) {
+    Build B{ctx, K};
+    int rc = build_plan(ctx, hm, K, &B.pl);
+    if (rc) return rc;
+    Arena probe{nullptr, 0};
+    (void)carve_scratch(probe, B.pl, K);
+    if ((rc = vd_ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, probe.off + 256))) return rc;
+    Arena arena{reinterpret_cast<char*>(ctx->scratch), 0};
+    B.P = carve_scratch(arena, B.pl, K);
+    B.sets[0] = ArrSet{B.P.cent, B.P.boxes}; B.sets[1] = ArrSet{B.P.cent1, B.P.boxes1};
+    VdBvhBuildStats& stats = ctx->bvh_stats;
+    stats = VdBvhBuildStats{};
+    Lap lap;
+
+    vd_time_begin(ctx);
+    if ((rc = precompute(B, hm, out_failed_mesh))) return rc;
+    lap(stats.ms_precompute);
+    if ((rc = phase_a(B))) return rc;
+    lap(stats.ms_phase_a);
+    if ((rc = mid_tier(B))) return rc;
+    lap(stats.ms_mid);
+    B.n_small = B.h_ctl.n_small; B.n_top = B.h_ctl.n_top;
+    stats.n_top_nodes = B.n_top; stats.n_small_roots = B.n_small; stats.n_mid_roots = B.h_ctl.n_mid;
+    PinnedTop h;
+    std::vector<unsigned> ord_end(K);
+    if ((rc = phase_b(B, &h, ord_end.data()))) return rc;
+    lap(stats.ms_phase_b);
+    number_top(h.top, h.sub, K, h.ord, ord_end.data(), h.out, h.root_pair, hm);
+    uint32_t failed = kNone;
+    if (!place_nodes(hm, K, packed_cap, packed_first, &failed, ctx->err, sizeof(ctx->err))) {
+        if (out_failed_mesh) *out_failed_mesh = failed;
+        return VD_ERR_INVALID_ARG;
+    }
+    if ((rc = phase_c(B, hm, h, d_packed))) return rc;
     lap(stats.ms_phase_c);
-    (void)n_tri;
     return VD_OK;
 }
 
@@ -2941,26 +2984,16 @@ int vd_bvh_build(VdCtx* ctx, const float* verts, uint32_t n_vert, uint32_t* idx,
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     int rc = check_build_args(ctx, verts, n_vert, idx, n_tri, out, node_cap, out_n_nodes);
     if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t vb = (size_t)n_vert * 12, ib = (size_t)n_tri * 12;
-    const size_t nb = sizeof(VdBvhNode) * (size_t)node_cap;
-    rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, vb + 256);
-    if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, ib + 256);
-    if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, nb + 256);
-    if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->stage_in, verts, vb, hipMemcpyHostToDevice, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->stage_aux, idx, ib, hipMemcpyHostToDevice, ctx->stream));
-    BuildMesh one{reinterpret_cast<const float*>(ctx->stage_in), n_vert, reinterpret_cast<uint32_t*>(ctx->stage_aux), n_tri,
-                  reinterpret_cast<VdBvhNode*>(ctx->stage_out), node_cap, 0u, 0u};
+    VdBlob b[3] = {{verts, (size_t)n_vert * 12, 256, nullptr}, {idx, (size_t)n_tri * 12, 256, nullptr},
+                   {nullptr, sizeof(VdBvhNode) * (size_t)node_cap, 256, nullptr}};
+    if ((rc = vd_stage_blobs(ctx, b, 3))) return rc;
+    BuildMesh one{static_cast<const float*>(b[0].dev), n_vert, static_cast<uint32_t*>(b[1].dev), n_tri, static_cast<VdBvhNode*>(b[2].dev), node_cap, 0u, 0u};
     rc = bvh_build_batch_impl(ctx, &one, 1u, nullptr, 0, 0u, nullptr);
     if (rc) return rc;
     *out_n_nodes = one.out_n_nodes;
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(idx, ctx->stage_aux, ib, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipMemcpyAsync(out, ctx->stage_out, sizeof(VdBvhNode) * (size_t)*out_n_nodes, hipMemcpyDeviceToHost, ctx->stream));
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return VD_OK;
+    b[2].bytes = sizeof(VdBvhNode) * (size_t)one.out_n_nodes;      // the nodes in use: nothing behind them is written
+    void* const back[3] = {nullptr, idx, out};
+    return vd_fetch_blobs(ctx, back, b, 3);
 }
 
 // K meshes in ONE build (header: "Batched BLAS build").
@@ -2988,22 +3021,29 @@ static int batch_args(VdCtx* ctx, const VdBvhBatchItem* items, uint32_t n_items,
     return VD_OK;
 }
 
+// What a batch call reports per item, and where the packed range ends.  failed: the one mesh a refusal is about (kNone:
+// the whole build); a refused call reports no nodes and ends the packed range where it began.
+static void batch_results(VdBvhBatchItem* items, uint32_t n_items, const BuildMesh* hm, int rc, uint32_t failed, uint32_t packed_first,
+                          uint32_t* out_packed_end) {
+    uint32_t end = packed_first;
+    for (uint32_t m = 0; m < n_items; ++m) {
+        items[m].out_n_nodes = rc ? 0u : hm[m].out_n_nodes;
+        items[m].out_first_node = rc ? 0u : hm[m].out_first;
+        items[m].status = rc ? (failed == kNone || failed == m ? rc : VD_OK) : VD_OK;
+        if (!rc && !items[m].out_nodes) end = hm[m].out_first + hm[m].out_n_nodes;
+    }
+    if (out_packed_end) *out_packed_end = end;
+}
+
 int vd_bvh_build_batch_dev(VdCtx* ctx, VdBvhBatchItem* items, uint32_t n_items, VdBvhNode* d_packed_nodes, uint64_t packed_cap,
                            uint32_t packed_first, uint32_t* out_packed_end) {
     VdDeviceGuard vd_guard_(ctx);
     std::vector<BuildMesh> hm;
     int rc = batch_args(ctx, items, n_items, d_packed_nodes, packed_cap, packed_first, hm);
     if (rc) return rc;
-    uint32_t failed = 0xffffffffu;
+    uint32_t failed = kNone;
     rc = bvh_build_batch_impl(ctx, hm.data(), n_items, d_packed_nodes, packed_cap, packed_first, &failed);
-    uint32_t end = packed_first;
-    for (uint32_t m = 0; m < n_items; ++m) {
-        items[m].out_n_nodes = rc ? 0u : hm[m].out_n_nodes;
-        items[m].out_first_node = rc ? 0u : hm[m].out_first;
-        items[m].status = rc ? (failed == 0xffffffffu || failed == m ? rc : VD_OK) : VD_OK;
-        if (!rc && !items[m].out_nodes) end = hm[m].out_first + hm[m].out_n_nodes;
-    }
-    if (out_packed_end) *out_packed_end = end;
+    batch_results(items, n_items, hm.data(), rc, failed, packed_first, out_packed_end);
     return rc;
 }
 
@@ -3013,56 +3053,38 @@ int vd_bvh_build_batch(VdCtx* ctx, VdBvhBatchItem* items, uint32_t n_items, VdBv
     std::vector<BuildMesh> hm;
     int rc = batch_args(ctx, items, n_items, packed_nodes, packed_cap, packed_first, hm);
     if (rc) return rc;
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    // staging: [vertices of all meshes][indices of all meshes] in, [nodes: 2 * n_tri per mesh, the reference's own bound] out
-    size_t vb = 0, ib = 0, nb = 0;
+    // staged per mesh: vertices, indices (both ways), and room for 2 * n_tri + 2 nodes, the reference's own bound
+    std::vector<VdBlob> b(3 * (size_t)n_items);
     for (uint32_t m = 0; m < n_items; ++m) {
-        vb += ((size_t)items[m].n_vert * 12 + 255) & ~(size_t)255;
-        ib += ((size_t)items[m].n_tri * 12 + 255) & ~(size_t)255;
-        nb += sizeof(VdBvhNode) * (2 * (size_t)items[m].n_tri + 2);
+        b[3 * m] = VdBlob{items[m].verts_xyz, (size_t)items[m].n_vert * 12, 256, nullptr};
+        b[3 * m + 1] = VdBlob{items[m].indices_inout, (size_t)items[m].n_tri * 12, 256, nullptr};
+        b[3 * m + 2] = VdBlob{nullptr, sizeof(VdBvhNode) * (2 * (size_t)items[m].n_tri + 2), 256, nullptr};
     }
-    rc = vd_ensure(ctx, &ctx->stage_in, &ctx->stage_in_bytes, vb + 256);
-    if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_aux, &ctx->stage_aux_bytes, ib + 256);
-    if (rc) return rc;
-    rc = vd_ensure(ctx, &ctx->stage_out, &ctx->stage_out_bytes, nb + 256);
-    if (rc) return rc;
-    char* dv = reinterpret_cast<char*>(ctx->stage_in); char* di = reinterpret_cast<char*>(ctx->stage_aux);
-    VdBvhNode* dn = reinterpret_cast<VdBvhNode*>(ctx->stage_out);
+    if ((rc = vd_stage_blobs(ctx, b.data(), (unsigned)b.size()))) return rc;
     for (uint32_t m = 0; m < n_items; ++m) {
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(dv, items[m].verts_xyz, (size_t)items[m].n_vert * 12, hipMemcpyHostToDevice, ctx->stream));
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(di, items[m].indices_inout, (size_t)items[m].n_tri * 12, hipMemcpyHostToDevice, ctx->stream));
-        hm[m].d_verts = reinterpret_cast<const float*>(dv); hm[m].d_idx = reinterpret_cast<uint32_t*>(di);
-        hm[m].d_out = dn; hm[m].node_cap = 2u * items[m].n_tri + 2u;
-        dv += ((size_t)items[m].n_vert * 12 + 255) & ~(size_t)255;
-        di += ((size_t)items[m].n_tri * 12 + 255) & ~(size_t)255;
-        dn += 2 * (size_t)items[m].n_tri + 2;
+        hm[m].d_verts = static_cast<const float*>(b[3 * m].dev); hm[m].d_idx = static_cast<uint32_t*>(b[3 * m + 1].dev);
+        hm[m].d_out = static_cast<VdBvhNode*>(b[3 * m + 2].dev); hm[m].node_cap = 2u * items[m].n_tri + 2u;
     }
-    uint32_t failed = 0xffffffffu;
+    uint32_t failed = kNone;
     rc = bvh_build_batch_impl(ctx, hm.data(), n_items, nullptr, 0, 0u, &failed);
     uint64_t at = packed_first;
-    for (uint32_t m = 0; m < n_items && !rc; ++m) {        // room on the caller's side
+    for (uint32_t m = 0; m < n_items && !rc; ++m) {        // room on the caller's side, and a packed item's place there
         const uint32_t need = hm[m].out_n_nodes;
         if (items[m].out_nodes ? need > items[m].node_cap : (at + need > packed_cap || at + need > 0xffffffffull)) {   // 32-bit node indices
             snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build_batch: item %u needs %u nodes: node_cap / packed_cap too small", m, need);
             rc = VD_ERR_INVALID_ARG; failed = m;
         }
-        if (!items[m].out_nodes) at += need;
+        if (!items[m].out_nodes) { hm[m].out_first = (uint32_t)at; at += need; }
     }
-    at = packed_first;
-    for (uint32_t m = 0; m < n_items; ++m) {
-        items[m].status = rc ? (failed == 0xffffffffu || failed == m ? rc : VD_OK) : VD_OK;
-        items[m].out_n_nodes = rc ? 0u : hm[m].out_n_nodes;
-        items[m].out_first_node = 0u;
-        if (rc) continue;
-        VdBvhNode* dst = items[m].out_nodes;
-        if (!dst) { dst = packed_nodes + at; items[m].out_first_node = (uint32_t)at; at += hm[m].out_n_nodes; }
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(items[m].indices_inout, hm[m].d_idx, (size_t)items[m].n_tri * 12, hipMemcpyDeviceToHost, ctx->stream));
-        VD_HIP_CHECK(ctx, hipMemcpyAsync(dst, hm[m].d_out, sizeof(VdBvhNode) * (size_t)hm[m].out_n_nodes, hipMemcpyDeviceToHost, ctx->stream));
+    batch_results(items, n_items, hm.data(), rc, failed, packed_first, out_packed_end);
+    std::vector<void*> back(b.size(), nullptr);            // a refused call copies nothing back
+    for (uint32_t m = 0; m < n_items && !rc; ++m) {
+        back[3 * m + 1] = items[m].indices_inout;
+        back[3 * m + 2] = items[m].out_nodes ? items[m].out_nodes : packed_nodes + hm[m].out_first;
+        b[3 * m + 2].bytes = sizeof(VdBvhNode) * (size_t)hm[m].out_n_nodes;     // the nodes in use: nothing behind them is written
     }
-    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (out_packed_end) *out_packed_end = (uint32_t)at;
-    return rc;
+    const int rc_back = vd_fetch_blobs(ctx, back.data(), b.data(), (unsigned)b.size());
+    return rc ? rc : rc_back;
 }
 
 }  // extern "C"

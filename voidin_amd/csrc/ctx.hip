@@ -52,6 +52,13 @@ int vd_fetch_blob(VdCtx* ctx, void* host, const VdBlob* blob) {
     return VD_OK;
 }
 
+int vd_fetch_blobs(VdCtx* ctx, void* const* hosts, const VdBlob* blobs, unsigned n_blobs) {
+    for (unsigned b = 0; b < n_blobs; ++b)
+        if (hosts[b] && blobs[b].bytes) VD_HIP_CHECK(ctx, hipMemcpyAsync(hosts[b], blobs[b].dev, blobs[b].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return VD_OK;
+}
+
 // grow-only pinned host staging
 int vd_ensure_host(VdCtx* ctx, size_t need) {
     if (need <= ctx->host_stage_bytes && ctx->host_stage) return VD_OK;

@@ -198,8 +198,10 @@ extern "C" __attribute__((visibility("hidden"))) int vd_fetch_lists(VdCtx* ctx, 
 // ctx.hip: the staged round trip of the host-pointer forms that are not draw lists (vd_trace*, vd_traverse*, vd_primary_rays,
 // vd_tlas_*).  vd_stage_blobs drains the stream, sizes ONE arena in ctx->stage_in, places every blob at its alignment (*dev) and
 // uploads those that have a host pointer - one without is room for a result; vd_fetch_blob copies a blob back and drains again.
+// vd_fetch_blobs: blob b to hosts[b] where that is not null, ONE drain behind them all (the SAH builder's forms: two results per mesh).
 extern "C" __attribute__((visibility("hidden"))) int vd_stage_blobs(VdCtx* ctx, VdBlob* blobs, unsigned n_blobs);
 extern "C" __attribute__((visibility("hidden"))) int vd_fetch_blob(VdCtx* ctx, void* host, const VdBlob* blob);
+extern "C" __attribute__((visibility("hidden"))) int vd_fetch_blobs(VdCtx* ctx, void* const* hosts, const VdBlob* blobs, unsigned n_blobs);
 
 // Calls f with a value of the mesh-id type of that width - unsigned char, unsigned short or unsigned: the one place
 // where an id width (1, 2 or 4 bytes; checked by the caller) picks a kernel instantiation.
