@@ -2498,16 +2498,6 @@ __global__ void c_root_kernel(TopNode* top, const int* root_keys, const MeshDesc
     top[2u * m + 1u] = z;
 }
 
-struct Arena {
-    char* base; size_t off;
-    template <typename T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base + off);
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
 // =============================================================================================
 // The build, host side: bvh_build_batch_impl (below) is the sequence of these stages.
 // =============================================================================================

@@ -33,7 +33,13 @@
 // variant (vd_lbvh_batch_sort_boxes).  Every mesh's triangle count is read from device memory by every pass, so the launches -
 // 19 or 23 kernels (21 or 25 for a plan made under VD_OPT_BLAS_LBVH_MAX_DEPTH), no memset, one more kernel for VdMeshInfo bounds - are
 // the same whatever the counts are ("the batched build" below).
+//
+// The host side: vd_bvh_lbvh_plan_dev is judge and derive (blas_lbvh_plan.hpp: pure host arithmetic, tested without a GPU by
+// tests/cpp/blas_lbvh_plan_test.cpp) -> upload (plan_upload: vd_plan_tables, ctx.hip - one allocation, tables then work memory)
+// -> the plan struct.  The host-pointer forms vd_bvh_build_lbvh and vd_bvh_build_lbvh_batch stage in the context's one arena
+// (vd_stage_blobs / vd_fetch_blob(s), ctx.hip); the batch comes back through batch_fetch.  profiles/blas_lbvh_host_layer.md.
 #include "vd_common.hpp"
+#include "blas_lbvh_plan.hpp"
 
 #include <new>
 #include <vector>
@@ -60,26 +66,26 @@ struct LbvhKeys {           // the depth-bounded build only: the explicit 64-bit
     unsigned* hi;           // T
     unsigned* low;          // T
 };
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t key_bytes(uint32_t T, bool bounded) { return bounded ? 2 * up256(4 * (size_t)T) : 0; }
-size_t work_bytes(uint32_t T, bool bounded) {
-    return 2 * up256(24 * (size_t)T) + up256(12 * (size_t)T) + 7 * up256(4 * (size_t)T) + key_bytes(T, bounded) + vd_lbvh_sort_bytes(T);
-}
-size_t work_bytes_batch(uint32_t S, bool bounded) {
-    return 2 * up256(24 * (size_t)S) + up256(12 * (size_t)S) + 7 * up256(4 * (size_t)S) + key_bytes(S, bounded) + vd_lbvh_batch_sort_bytes(S);
-}
-LbvhWork carve(void* base, uint32_t T, LbvhKeys* bounded /* null: the unbounded build's layout */) {
-    char* p = reinterpret_cast<char*>(base);
-    auto take = [&](size_t bytes) { char* q = p; p += up256(bytes); return q; };
+// The arrays over T positions (a mesh's triangles, a plan's slots) at `base`, each 256-byte aligned, the sort's work memory last.
+// base == null: only sizes them.  *sort_at = the bytes in front of the sort's.
+LbvhWork carve(void* base, size_t T, LbvhKeys* bounded /* null: the unbounded build's layout */, size_t* sort_at = nullptr) {
+    Arena a{reinterpret_cast<char*>(base), 0};
     LbvhWork w;
-    w.tbox = reinterpret_cast<float*>(take(24 * (size_t)T));
-    w.idx = reinterpret_cast<unsigned*>(take(12 * (size_t)T));
-    w.ibox = reinterpret_cast<float*>(take(24 * (size_t)T));
+    w.tbox = a.take<float>(6 * T);
+    w.idx = a.take<unsigned>(3 * T);
+    w.ibox = a.take<float>(6 * T);
     unsigned** words[7] = {&w.lo, &w.hi, &w.split, &w.par_int, &w.par_leaf, &w.meta, &w.arrived};
-    for (unsigned** a : words) *a = reinterpret_cast<unsigned*>(take(4 * (size_t)T));
-    if (bounded) { bounded->hi = reinterpret_cast<unsigned*>(take(4 * (size_t)T)); bounded->low = reinterpret_cast<unsigned*>(take(4 * (size_t)T)); }
-    w.sort = p;
+    for (unsigned** arr : words) *arr = a.take<unsigned>(T);
+    if (bounded) { bounded->hi = a.take<unsigned>(T); bounded->low = a.take<unsigned>(T); }
+    w.sort = a.take<char>(0);
+    if (sort_at) *sort_at = a.off;
     return w;
+}
+size_t work_bytes(uint32_t T, bool bounded, size_t sort_bytes /* vd_lbvh_sort_bytes(T), or the batched sort's */) {
+    LbvhKeys k;
+    size_t sort_at = 0;
+    (void)carve(nullptr, T, bounded ? &k : nullptr, &sort_at);
+    return sort_at + sort_bytes;
 }
 
 struct Box3 { float mn[3], mx[3]; };
@@ -166,9 +172,7 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_tree_kernel(const unsigned* 
 }
 
 // ---- the depth bound (VD_OPT_BLAS_LBVH_MAX_DEPTH) --------------------------------------------------------------------------------
-// depth of the radix tree over the integers 0 .. k - 1 cut off at nodes of <= 3 positions
-__host__ __device__ __forceinline__ unsigned needr(unsigned k) { return k <= 3u ? 0u : 31u - (unsigned)__builtin_clz(k - 1u); }
-
+// (needr, the depth of the radix tree over the integers 0 .. k - 1 cut off at nodes of <= 3 positions: blas_lbvh_plan.hpp)
 // One thread per sorted position p < T of a mesh of T >= 2: the explicit key of that position.  Every ancestor of the radix leaf
 // covers > 3 positions or lies inside an emitted leaf; only the former have a split to judge, and those are the emitted interior
 // nodes, so the radix depth of one is its depth in the array.  The ancestors BELOW the topmost rule-breaker belong to a subtree that
@@ -347,12 +351,7 @@ __global__ __launch_bounds__(kBlock) void blas_lbvh_permute_kernel(unsigned T, c
 // load.  Every array of LbvhWork is laid out over the slots; a mesh's part of it starts at slot0 and is what the single build's
 // array is for that mesh: positions, radix node ids and vals are mesh-local.  T_m = min(d_n_tri[m], tri_cap) is read on the
 // device by every pass; a lane whose position is beyond T_m leaves.  Grids come from the slot count alone.
-struct BatchItemDev {
-    const float* verts; unsigned* indices; VdBvhNode* nodes; VdMeshInfo* info;
-    unsigned n_vert, node_cap, n_chunks /* of the MeshInfo fold */, _pad[5];
-};
-static_assert(sizeof(BatchItemDev) == 64, "one item record per cache-line half");
-
+// (BatchItemDev, a mesh's pointers and sizes: blas_lbvh_plan.hpp, which fills it)
 struct BatchSlot { unsigned m, j, T, slot0; };           // the mesh of this thread's slot, its position in it, the mesh's count
 __device__ __forceinline__ BatchSlot batch_slot(unsigned unit, const VdLbvhSeg* __restrict__ segs, const unsigned* __restrict__ unit_seg,
                                                 const unsigned* __restrict__ n_tri) {
@@ -470,6 +469,63 @@ unsigned depth_bound(const VdCtx* ctx) {
     return (unsigned)(d > 62 ? 62 : d);
 }
 
+// The upload of a plan: its tables (blas_lbvh_plan.hpp) and the work memory over its slots in ONE allocation, the plan's pointers
+// into it.  What is not uploaded starts as zeros: the extent words are set by the boxes pass, the fold's done counters and the
+// bad-index counts start at 0 and come back to 0 after every build.
+static_assert(sizeof(VdPair) == sizeof(uint2), "chunk records are uploaded where the kernels read uint2");
+int plan_upload(VdCtx* ctx, const LbvhPlanTables& t, VdBvhLbvhPlan* p) {
+    const size_t n = t.items.size();
+    const std::vector<int> keys = vd_fold_neutral_keys(n);
+    enum { kItems, kSegs, kUnitSeg, kExtChunks, kExt, kBoundChunks, kBoundKeys, kBoundDone, kBad, kParts };
+    VdPlanPart part[kParts] = {{t.items.data(), sizeof(BatchItemDev) * n, nullptr},
+                               {t.segs.data(), sizeof(VdLbvhSeg) * n, nullptr},
+                               {t.unit_seg.data(), 4 * t.unit_seg.size(), nullptr},
+                               {t.ext_chunks.data(), sizeof(VdPair) * t.ext_chunks.size(), nullptr},
+                               {nullptr, 24 * n, nullptr},
+                               {t.bound_chunks.data(), sizeof(VdPair) * t.bound_chunks.size(), nullptr},
+                               {keys.data(), 4 * keys.size(), nullptr},
+                               {nullptr, 4 * n, nullptr},
+                               {nullptr, 4 * n, nullptr}};
+    const bool bounded = p->max_depth != 0u;
+    void* work = nullptr;
+    const int rc = vd_plan_tables(ctx, "vd_bvh_lbvh_plan", part, kParts, work_bytes(p->n_slots, bounded, vd_lbvh_batch_sort_bytes(p->n_slots)), &p->dev, &work);
+    if (rc) return rc;
+    p->d_items = static_cast<BatchItemDev*>(part[kItems].dev);
+    p->d_bound_chunks = static_cast<uint2*>(part[kBoundChunks].dev);
+    p->d_bound_keys = static_cast<int*>(part[kBoundKeys].dev);
+    p->d_bound_done = static_cast<unsigned*>(part[kBoundDone].dev);
+    p->d_bad = static_cast<unsigned*>(part[kBad].dev);
+    p->layout.d_segs = static_cast<const VdLbvhSeg*>(part[kSegs].dev);
+    p->layout.d_unit_seg = static_cast<const unsigned*>(part[kUnitSeg].dev);
+    p->layout.d_chunks = static_cast<const uint2*>(part[kExtChunks].dev);
+    p->layout.d_ext = static_cast<unsigned*>(part[kExt].dev);
+    p->w = carve(work, p->n_slots, bounded ? &p->k : nullptr);      // .sort: vd_lbvh_batch_sort_bytes(n_slots)
+    return VD_OK;
+}
+
+// The host batch's staging (vd_bvh_build_lbvh_batch): every item's blobs in this order, those of item m from kItemBlobs * m on.
+enum { kBlobVerts, kBlobIndices, kBlobNodes /* room for node_cap */, kBlobInfo /* no bytes where the item has no VdMeshInfo */, kItemBlobs };
+
+// ... and its way back, the results being on the host: a bad index or an implausible count in any item and nothing is copied;
+// else every item's n_nodes nodes, 3 * T_m indices and VdMeshInfo behind one drain.
+int batch_fetch(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items, const uint32_t* n_tri, const VdBvhLbvhResult* results, VdBlob* blobs, void** hosts) {
+    int rc = VD_OK;
+    for (uint32_t m = 0; m < n_items; ++m)
+        if (results[m].n_bad_indices != 0u) { rc = fail_item(ctx, items, m, "an index >= n_vert"); }
+        else if (results[m].n_nodes > items[m].node_cap) { rc = VD_ERR_HIP; snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build_lbvh_batch: implausible node count"); }
+    if (rc) return rc;
+    for (uint32_t m = 0; m < n_items; ++m) {
+        const VdBvhLbvhBatchItem& it = items[m];
+        const uint32_t T = n_tri ? (n_tri[m] < it.tri_cap ? n_tri[m] : it.tri_cap) : it.tri_cap;
+        VdBlob* b = blobs + kItemBlobs * (size_t)m;
+        void** h = hosts + kItemBlobs * (size_t)m;
+        b[kBlobNodes].bytes = sizeof(VdBvhNode) * (size_t)results[m].n_nodes; h[kBlobNodes] = it.nodes;
+        b[kBlobIndices].bytes = 12 * (size_t)T; h[kBlobIndices] = it.indices_inout;
+        h[kBlobInfo] = it.mesh_info;                       // (no bytes where there is none)
+    }
+    return vd_fetch_blobs(ctx, hosts, blobs, kItemBlobs * n_items);
+}
+
 int check_args(VdCtx* ctx, const void* verts, const void* indices, uint32_t n_tri, const void* nodes, uint32_t node_cap) {
     if (!verts || !indices || !nodes) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: null vertices / indices / nodes");
     if (n_tri == 0u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh: n_tri == 0");
@@ -498,7 +554,7 @@ int vd_bvh_build_lbvh_dev(VdCtx* ctx, const float* d_verts_xyz, uint32_t n_vert,
     if ((reinterpret_cast<uintptr_t>(d_out_nodes) & 15u) != 0u) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_dev: d_out_nodes is not 16-byte aligned");
     const uint32_t T = n_tri;
     const unsigned D = depth_bound(ctx);
-    if ((rc = vd_ensure(ctx, &ctx->blas_lbvh_state, &ctx->blas_lbvh_state_bytes, work_bytes(T, D != 0u)))) return rc;
+    if ((rc = vd_ensure(ctx, &ctx->blas_lbvh_state, &ctx->blas_lbvh_state_bytes, work_bytes(T, D != 0u, vd_lbvh_sort_bytes(T))))) return rc;
     LbvhKeys k = {};
     const LbvhWork w = carve(ctx->blas_lbvh_state, T, D ? &k : nullptr);
     hipStream_t st = ctx->stream;
@@ -555,7 +611,7 @@ int vd_bvh_lbvh_plan_release(VdCtx* ctx, VdBvhLbvhPlan* plan) {
     VdDeviceGuard vd_guard_(ctx);
     if (!ctx || !plan) return VD_ERR_INVALID_ARG;
     (void)hipStreamSynchronize(ctx->stream);               // a queued build still uses the plan's memory
-    if (plan->dev) (void)hipFree(plan->dev);
+    vd_plan_free(plan->dev);
     delete plan;
     return VD_OK;
 }
@@ -568,91 +624,27 @@ int vd_bvh_lbvh_plan_dev(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_items
         if (ctx) snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_lbvh_plan: null item array, or n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS");
         return VD_ERR_INVALID_ARG;
     }
-    for (uint32_t m = 0; m < n_items; ++m) items[m].status = VD_OK;
     const unsigned D = ctx ? depth_bound(ctx) : 0u;        // latched: the plan's memory and launch list follow it, later changes of the option do not
-    std::vector<BatchItemDev> h_items;
-    std::vector<VdLbvhSeg> h_segs;
-    std::vector<unsigned> h_unit_seg;
-    std::vector<uint2> h_ext_chunks, h_bound_chunks;
+    VdBvhLbvhPlan* p = nullptr;
     try {
-        h_items.resize(n_items); h_segs.resize(n_items);
-        uint64_t slots = 0;
-        for (uint32_t m = 0; m < n_items; ++m) {
-            const VdBvhLbvhBatchItem& it = items[m];
-            if (!it.verts_xyz || !it.indices_inout || !it.nodes) return fail_item(ctx, items, m, "null vertices / indices / nodes");
-            if (it.tri_cap == 0u) return fail_item(ctx, items, m, "tri_cap == 0");
-            if (it.tri_cap > VD_BVH_LBVH_MAX_TRIANGLES) return fail_item(ctx, items, m, "tri_cap > VD_BVH_LBVH_MAX_TRIANGLES");
-            if (it.node_cap < (it.tri_cap < 2u ? 2u : 2u * it.tri_cap)) return fail_item(ctx, items, m, "node_cap < max(2, 2 * tri_cap)");
-            if ((reinterpret_cast<uintptr_t>(it.nodes) & 15u) != 0u) return fail_item(ctx, items, m, "nodes is not 16-byte aligned");
-            if (D && needr(it.tri_cap) > D) {               // T_m <= tri_cap: every count the device can hold then fits the bound
-                char what[160];
-                snprintf(what, sizeof(what), "VD_OPT_BLAS_LBVH_MAX_DEPTH = %u cannot hold tri_cap = %u: the smallest bound that can is %u", D, it.tri_cap,
-                         needr(it.tri_cap));
-                return fail_item(ctx, items, m, what);
-            }
-            const unsigned n_units = (it.tri_cap + kVdLbvhBatchUnit - 1u) / kVdLbvhBatchUnit;
-            if (slots + (uint64_t)n_units * kVdLbvhBatchUnit > VD_BVH_LBVH_MAX_TRIANGLES)
-                return fail_item(ctx, items, m, "the capacities, each rounded up to 256, add up to more than VD_BVH_LBVH_MAX_TRIANGLES");
-            h_segs[m] = VdLbvhSeg{(unsigned)slots, it.tri_cap, n_units, 0u};
-            h_unit_seg.insert(h_unit_seg.end(), n_units, m);
-            for (unsigned c = 0; c < it.tri_cap; c += kVdLbvhExtentChunk) h_ext_chunks.push_back(make_uint2(m, c));
-            BatchItemDev& d = h_items[m];
-            d = BatchItemDev{};
-            d.verts = it.verts_xyz; d.indices = it.indices_inout; d.nodes = it.nodes; d.info = it.mesh_info;
-            d.n_vert = it.n_vert; d.node_cap = it.node_cap;
-            if (it.mesh_info) {
-                d.n_chunks = it.n_vert ? (unsigned)(((size_t)it.n_vert + kVdVertChunk - 1u) / kVdVertChunk) : 1u;      // an empty fold still writes (+inf, -inf)
-                for (unsigned c = 0; c < d.n_chunks; ++c) h_bound_chunks.push_back(make_uint2(m, c * kVdVertChunk));
-            }
-            slots += (uint64_t)n_units * kVdLbvhBatchUnit;
-        }
-        if (!ctx) return VD_ERR_INVALID_ARG;               // (the items are judged without a context: nothing above touches the device)
-        VdBvhLbvhPlan* p = new VdBvhLbvhPlan();
-        p->n_items = n_items; p->n_slots = (unsigned)slots; p->n_bound_chunks = (unsigned)h_bound_chunks.size();
+        // judge and derive (blas_lbvh_plan.hpp): the items are judged without a context - nothing here touches the device
+        LbvhPlanTables t;
+        uint32_t failed = 0;
+        char buf[kLbvhWhatLen];
+        if (const char* what = lbvh_plan_tables(items, n_items, D, t, &failed, buf)) return fail_item(ctx, items, failed, what);
+        if (!ctx) return VD_ERR_INVALID_ARG;
+        p = new VdBvhLbvhPlan();
+        p->n_items = n_items; p->n_slots = (unsigned)t.n_slots; p->n_bound_chunks = (unsigned)t.bound_chunks.size();
         p->max_depth = D;
-        *out = p;
-        if (n_items == 0) return VD_OK;
-        const uint32_t S = p->n_slots;
-        const size_t o_items = 0, o_segs = up256(sizeof(BatchItemDev) * n_items), o_unit = o_segs + up256(sizeof(VdLbvhSeg) * n_items),
-                     o_echunks = o_unit + up256(4 * h_unit_seg.size()), o_ext = o_echunks + up256(8 * h_ext_chunks.size()),
-                     o_bchunks = o_ext + up256(24 * (size_t)n_items), o_bkeys = o_bchunks + up256(8 * h_bound_chunks.size()),
-                     o_bdone = o_bkeys + up256(24 * (size_t)n_items), o_bad = o_bdone + up256(4 * (size_t)n_items),
-                     o_work = o_bad + up256(4 * (size_t)n_items),
-                     total = o_work + work_bytes_batch(S, D != 0u);
-        std::vector<int> h_keys(6 * (size_t)n_items);
-        for (size_t m = 0; m < n_items; ++m)
-            for (int q = 0; q < 6; ++q) h_keys[6 * m + q] = q < 3 ? kVdKeyPosInf : kVdKeyNegInf;
-        hipError_t e = hipMalloc(&p->dev, total);
-        if (e != hipSuccess) { delete p; *out = nullptr; VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_lbvh_plan: device memory"); }
-        char* base = reinterpret_cast<char*>(p->dev);
-        e = hipMemset(base, 0, o_work);                    // the fold's done counters and the bad-index counts start at 0 and come back to 0 after every build
-        if (e == hipSuccess) e = hipMemcpy(base + o_items, h_items.data(), sizeof(BatchItemDev) * n_items, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(base + o_segs, h_segs.data(), sizeof(VdLbvhSeg) * n_items, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(base + o_unit, h_unit_seg.data(), 4 * h_unit_seg.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(base + o_echunks, h_ext_chunks.data(), 8 * h_ext_chunks.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(base + o_bkeys, h_keys.data(), 4 * h_keys.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !h_bound_chunks.empty()) e = hipMemcpy(base + o_bchunks, h_bound_chunks.data(), 8 * h_bound_chunks.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the uploads ran on the default stream; the build runs on the context's
-        if (e != hipSuccess) {
-            (void)hipFree(p->dev); delete p; *out = nullptr;
-            VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
-        }
-        p->d_items = reinterpret_cast<BatchItemDev*>(base + o_items);
-        p->d_bound_chunks = reinterpret_cast<uint2*>(base + o_bchunks);
-        p->d_bound_keys = reinterpret_cast<int*>(base + o_bkeys);
-        p->d_bound_done = reinterpret_cast<unsigned*>(base + o_bdone);
-        p->d_bad = reinterpret_cast<unsigned*>(base + o_bad);
-        p->layout.n_slots = S; p->layout.n_chunks = (unsigned)h_ext_chunks.size();
-        p->layout.d_segs = reinterpret_cast<const VdLbvhSeg*>(base + o_segs);
-        p->layout.d_unit_seg = reinterpret_cast<const unsigned*>(base + o_unit);
-        p->layout.d_chunks = reinterpret_cast<const uint2*>(base + o_echunks);
-        p->layout.d_ext = reinterpret_cast<unsigned*>(base + o_ext);
-        p->w = carve(base + o_work, S, D ? &p->k : nullptr);      // .sort: vd_lbvh_batch_sort_bytes(S)
+        p->layout.n_slots = p->n_slots; p->layout.n_chunks = (unsigned)t.ext_chunks.size();
+        const int rc = n_items ? plan_upload(ctx, t, p) : VD_OK;
+        if (rc) { delete p; return rc; }                   // no plan is returned after a refusal
     } catch (const std::bad_alloc&) {
-        if (*out) { delete *out; *out = nullptr; }
+        delete p;
         if (!ctx) return VD_ERR_OOM;
         VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_lbvh_plan: host memory");
     }
+    *out = p;
     return VD_OK;
 }
 
@@ -697,71 +689,47 @@ int vd_bvh_build_lbvh_batch(VdCtx* ctx, VdBvhLbvhBatchItem* items, uint32_t n_it
     if (n_items && (!items || !results)) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_batch: null items / results");
     if (n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_build_lbvh_batch: n_items > VD_BVH_LBVH_BATCH_MAX_ITEMS");
     if (n_items == 0u) return VD_OK;
-    // one device allocation: per item vertices, indices, nodes and (optional) MeshInfo, then the counts and the results
-    std::vector<VdBvhLbvhBatchItem> d_items;
-    std::vector<size_t> offs;
-    size_t total = 0;
-    auto place = [&](size_t bytes) { const size_t at = total; total += up256(bytes ? bytes : 1); offs.push_back(at); return at; };
+    std::vector<VdBvhLbvhBatchItem> d_items;               // the items as the device sees them: the staged copies
+    std::vector<VdBlob> blobs;                             // kItemBlobs per item, then the counts and the results
+    std::vector<void*> hosts;                              // where each blob is fetched to; null: it is not
     try {
         d_items.assign(items, items + n_items);
-        offs.reserve(4 * (size_t)n_items + 2);
+        blobs.reserve(kItemBlobs * (size_t)n_items + 2);
         for (uint32_t m = 0; m < n_items; ++m) {
             items[m].status = VD_OK;
             const VdBvhLbvhBatchItem& it = items[m];
             if (!it.verts_xyz || !it.indices_inout || !it.nodes) return fail_item(ctx, items, m, "null vertices / indices / nodes");
             if (it.tri_cap == 0u || it.tri_cap > VD_BVH_LBVH_MAX_TRIANGLES) return fail_item(ctx, items, m, "tri_cap == 0 or > VD_BVH_LBVH_MAX_TRIANGLES");
             if (it.node_cap < (it.tri_cap < 2u ? 2u : 2u * it.tri_cap)) return fail_item(ctx, items, m, "node_cap < max(2, 2 * tri_cap)");
-            place(12 * (size_t)it.n_vert); place(12 * (size_t)it.tri_cap); place(sizeof(VdBvhNode) * (size_t)it.node_cap); place(sizeof(VdMeshInfo));
+            blobs.push_back(VdBlob{it.verts_xyz, 12 * (size_t)it.n_vert, 256, nullptr});
+            blobs.push_back(VdBlob{it.indices_inout, 12 * (size_t)it.tri_cap, 256, nullptr});
+            blobs.push_back(VdBlob{nullptr, sizeof(VdBvhNode) * (size_t)it.node_cap, 256, nullptr});
+            blobs.push_back(VdBlob{it.mesh_info, it.mesh_info ? sizeof(VdMeshInfo) : 0, 256, nullptr});
         }
+        blobs.push_back(VdBlob{n_tri, 4 * (size_t)n_items, 256, nullptr});
+        blobs.push_back(VdBlob{nullptr, sizeof(VdBvhLbvhResult) * (size_t)n_items, 256, nullptr});
+        hosts.assign(blobs.size(), nullptr);
     } catch (const std::bad_alloc&) {
         VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_build_lbvh_batch: host memory");
     }
-    const size_t o_cnt = place(4 * (size_t)n_items), o_res = place(sizeof(VdBvhLbvhResult) * (size_t)n_items);
-    char* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), total) != hipSuccess) VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_build_lbvh_batch: staging");
-    hipError_t e = hipSuccess;
-    for (uint32_t m = 0; m < n_items && e == hipSuccess; ++m) {
-        const VdBvhLbvhBatchItem& it = items[m];
-        VdBvhLbvhBatchItem& di = d_items[m];
-        di.verts_xyz = reinterpret_cast<const float*>(d + offs[4 * m]); di.indices_inout = reinterpret_cast<uint32_t*>(d + offs[4 * m + 1]);
-        di.nodes = reinterpret_cast<VdBvhNode*>(d + offs[4 * m + 2]);
-        di.mesh_info = it.mesh_info ? reinterpret_cast<VdMeshInfo*>(d + offs[4 * m + 3]) : nullptr;
-        if (it.n_vert) e = hipMemcpy(d + offs[4 * m], it.verts_xyz, 12 * (size_t)it.n_vert, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d + offs[4 * m + 1], it.indices_inout, 12 * (size_t)it.tri_cap, hipMemcpyHostToDevice);
-        if (e == hipSuccess && it.mesh_info) e = hipMemcpy(d + offs[4 * m + 3], it.mesh_info, sizeof(VdMeshInfo), hipMemcpyHostToDevice);
+    int rc = vd_stage_blobs(ctx, blobs.data(), (unsigned)blobs.size());
+    if (rc) return rc;
+    const VdBlob* counts = &blobs[kItemBlobs * (size_t)n_items];
+    for (uint32_t m = 0; m < n_items; ++m) {
+        const VdBlob* b = &blobs[kItemBlobs * (size_t)m];
+        d_items[m].verts_xyz = static_cast<const float*>(b[kBlobVerts].dev); d_items[m].indices_inout = static_cast<uint32_t*>(b[kBlobIndices].dev);
+        d_items[m].nodes = static_cast<VdBvhNode*>(b[kBlobNodes].dev);
+        d_items[m].mesh_info = items[m].mesh_info ? static_cast<VdMeshInfo*>(b[kBlobInfo].dev) : nullptr;
     }
-    if (e == hipSuccess && n_tri) e = hipMemcpy(d + o_cnt, n_tri, 4 * (size_t)n_items, hipMemcpyHostToDevice);
     VdBvhLbvhPlan* plan = nullptr;
-    int rc = VD_OK;
-    if (e == hipSuccess) {
-        rc = vd_bvh_lbvh_plan_dev(ctx, d_items.data(), n_items, &plan);
-        for (uint32_t m = 0; m < n_items; ++m) items[m].status = d_items[m].status;
-        if (rc == VD_OK) rc = vd_bvh_build_lbvh_planned_dev(ctx, plan, n_tri ? reinterpret_cast<const uint32_t*>(d + o_cnt) : nullptr,
-                                                            reinterpret_cast<VdBvhLbvhResult*>(d + o_res));
-        if (rc == VD_OK) {
-            e = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = hipMemcpy(results, d + o_res, sizeof(VdBvhLbvhResult) * (size_t)n_items, hipMemcpyDeviceToHost);
-        }
-    }
-    if (rc == VD_OK && e == hipSuccess) {
-        for (uint32_t m = 0; m < n_items; ++m)
-            if (results[m].n_bad_indices != 0u) { rc = fail_item(ctx, items, m, "an index >= n_vert"); }
-            else if (results[m].n_nodes > items[m].node_cap) { rc = VD_ERR_HIP; snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build_lbvh_batch: implausible node count"); }
-    }
-    if (rc == VD_OK && e == hipSuccess) {
-        for (uint32_t m = 0; m < n_items && e == hipSuccess; ++m) {
-            const VdBvhLbvhBatchItem& it = items[m];
-            const uint32_t T = n_tri ? (n_tri[m] < it.tri_cap ? n_tri[m] : it.tri_cap) : it.tri_cap;
-            if (results[m].n_nodes) e = hipMemcpy(it.nodes, d + offs[4 * m + 2], sizeof(VdBvhNode) * (size_t)results[m].n_nodes, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && T) e = hipMemcpy(it.indices_inout, d + offs[4 * m + 1], 12 * (size_t)T, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && it.mesh_info) e = hipMemcpy(it.mesh_info, d + offs[4 * m + 3], sizeof(VdMeshInfo), hipMemcpyDeviceToHost);
-        }
-    }
-    if (plan) (void)vd_bvh_lbvh_plan_release(ctx, plan);
-    (void)hipFree(d);
-    if (rc != VD_OK) return rc;
-    if (e != hipSuccess) VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
-    return VD_OK;
+    rc = vd_bvh_lbvh_plan_dev(ctx, d_items.data(), n_items, &plan);
+    for (uint32_t m = 0; m < n_items; ++m) items[m].status = d_items[m].status;
+    if (rc) return rc;
+    rc = vd_bvh_build_lbvh_planned_dev(ctx, plan, n_tri ? static_cast<const uint32_t*>(counts[0].dev) : nullptr, static_cast<VdBvhLbvhResult*>(counts[1].dev));
+    if (rc == VD_OK) rc = vd_fetch_blob(ctx, results, &counts[1]);
+    if (rc == VD_OK) rc = batch_fetch(ctx, items, n_items, n_tri, results, blobs.data(), hosts.data());
+    (void)vd_bvh_lbvh_plan_release(ctx, plan);
+    return rc;
 }
 
 }  // extern "C"

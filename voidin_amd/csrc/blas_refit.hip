@@ -28,24 +28,20 @@
 //     (MeshPool::calculate_bounds, crates/pools/src/mesh/mod.rs:22-27), 4096 vertices per block, on the order-preserving
 //     integer image of the float bits (vd_key: -0 below +0, NaN mapped to the neutral element), integer atomic min / max
 //     across blocks; the block whose arrival completes an item writes MeshInfo.min / max and re-arms the item's words.
+//
+// The host side: vd_bvh_refit_plan_dev is judge and derive (plan_tables: the read-back of an item's nodes and indices, then
+// blas_refit_plan.hpp - pure host arithmetic, tested without a GPU by tests/cpp/blas_refit_plan_test.cpp) -> upload (plan_upload:
+// vd_plan_tables, ctx.hip - one allocation) -> the plan struct.  vd_bvh_refit stages in the context's one arena (vd_stage_blobs /
+// vd_fetch_blob, ctx.hip): the nodes go up and come back.  profiles/blas_lbvh_host_layer.md.
 #include "vd_common.hpp"
+#include "blas_refit_plan.hpp"
 
 #include <new>
 #include <vector>
 
 namespace {
 
-constexpr unsigned kNoParent = 0xffffffffu;
-constexpr unsigned kBlock = 256u;
-constexpr unsigned kVertChunk = kVdVertChunk;          // vertices per block of the MeshInfo fold (vd_common.hpp: vd_mesh_bounds_fold)
-constexpr int kKeyPosInf = kVdKeyPosInf, kKeyNegInf = kVdKeyNegInf;      // the neutral keys of its min / max
-
-struct RefitItemDev {
-    const float* verts; const unsigned* indices; VdBvhNode* nodes; VdMeshInfo* info;
-    unsigned n_vert, n_tri, n_nodes, node_base;        // node_base: where the item's links / counters start in the plan's arrays
-    unsigned n_chunks, _pad[3];
-};
-static_assert(sizeof(RefitItemDev) == 64, "one item record per cache-line half");
+constexpr unsigned kBlock = 256u;                      // (kNoParent, RefitItemDev: blas_refit_plan.hpp, which fills the plan's tables)
 
 }  // namespace
 
@@ -139,8 +135,50 @@ __global__ __launch_bounds__(kBlock) void blas_refit_kernel(const RefitItemDev* 
 
 int fail_item(VdCtx* ctx, VdBvhRefitItem* items, uint32_t m, const char* what) {
     items[m].status = VD_ERR_INVALID_ARG;
-    snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_refit_plan: item %u: %s", m, what);
+    if (ctx) snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_refit_plan: item %u: %s", m, what);
     return VD_ERR_INVALID_ARG;
+}
+
+// judge and derive: every item's nodes and indices are read back (into the caller's two buffers, one item at a time) and go
+// through blas_refit_plan.hpp
+int plan_tables(VdCtx* ctx, VdBvhRefitItem* items, uint32_t n_items, RefitPlanTables& t, std::vector<VdBvhNode>& nodes, std::vector<unsigned>& idx) {
+    t.items.reserve(n_items);
+    for (uint32_t m = 0; m < n_items; ++m) {
+        const VdBvhRefitItem& it = items[m];
+        if (const char* what = refit_judge_item(t, it)) return fail_item(ctx, items, m, what);
+        nodes.resize(it.n_nodes);
+        idx.resize(3 * (size_t)it.n_tri);
+        VD_HIP_CHECK(ctx, hipMemcpy(nodes.data(), it.nodes, sizeof(VdBvhNode) * (size_t)it.n_nodes, hipMemcpyDeviceToHost));
+        if (it.n_tri) VD_HIP_CHECK(ctx, hipMemcpy(idx.data(), it.indices, 12 * (size_t)it.n_tri, hipMemcpyDeviceToHost));
+        if (const char* what = refit_plan_item(t, m, it, nodes.data(), idx.data())) return fail_item(ctx, items, m, what);
+    }
+    return VD_OK;
+}
+
+// upload: the tables in ONE allocation, and the plan's pointers into it.  Arrival and done counters are not uploaded: they start
+// at 0 and come back to 0 after every refit.
+static_assert(sizeof(VdPair) == sizeof(uint2) && sizeof(VdQuad) == sizeof(uint4), "chunk and leaf records are uploaded where the kernel reads uint2 / uint4");
+int plan_upload(VdCtx* ctx, const RefitPlanTables& t, VdBvhRefitPlan* p) {
+    const size_t n = t.items.size();
+    const std::vector<int> keys = vd_fold_neutral_keys(n);
+    enum { kItems, kLeaves, kUp, kArrivals, kKeys, kDone, kChunks, kParts };
+    VdPlanPart part[kParts] = {{t.items.data(), sizeof(RefitItemDev) * n, nullptr},
+                               {t.leaves.data(), sizeof(VdQuad) * t.leaves.size(), nullptr},
+                               {t.up.data(), 4 * t.up.size(), nullptr},
+                               {nullptr, 4 * t.up.size(), nullptr},
+                               {keys.data(), 4 * keys.size(), nullptr},
+                               {nullptr, 4 * n, nullptr},
+                               {t.chunks.data(), sizeof(VdPair) * t.chunks.size(), nullptr}};
+    const int rc = vd_plan_tables(ctx, "vd_bvh_refit_plan", part, kParts, 0, &p->dev, nullptr);
+    if (rc) return rc;
+    p->d_items = static_cast<RefitItemDev*>(part[kItems].dev);
+    p->d_leaves = static_cast<uint4*>(part[kLeaves].dev);
+    p->d_up = static_cast<unsigned*>(part[kUp].dev);
+    p->d_arrivals = static_cast<unsigned*>(part[kArrivals].dev);
+    p->d_keys = static_cast<int*>(part[kKeys].dev);
+    p->d_done = static_cast<unsigned*>(part[kDone].dev);
+    p->d_chunks = static_cast<uint2*>(part[kChunks].dev);
+    return VD_OK;
 }
 
 }  // namespace
@@ -151,7 +189,7 @@ int vd_bvh_refit_plan_release(VdCtx* ctx, VdBvhRefitPlan* plan) {
     VdDeviceGuard vd_guard_(ctx);
     if (!ctx || !plan) return VD_ERR_INVALID_ARG;
     (void)hipStreamSynchronize(ctx->stream);           // a queued refit still reads the plan's arrays
-    if (plan->dev) (void)hipFree(plan->dev);
+    vd_plan_free(plan->dev);
     delete plan;
     return VD_OK;
 }
@@ -163,90 +201,21 @@ int vd_bvh_refit_plan_dev(VdCtx* ctx, VdBvhRefitItem* items, uint32_t n_items, V
     if (n_items && !items) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_refit_plan: null item array");
     for (uint32_t m = 0; m < n_items; ++m) items[m].status = VD_OK;
     VD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));      // the nodes / indices may come from work still queued
-    std::vector<RefitItemDev> h_items(n_items);
-    std::vector<uint4> h_leaves;
-    std::vector<unsigned> h_up;
-    std::vector<uint2> h_chunks;
-    std::vector<VdBvhNode> nodes;
-    std::vector<unsigned> idx;
+    VdBvhRefitPlan* p = nullptr;
     try {
-        for (uint32_t m = 0; m < n_items; ++m) {
-            const VdBvhRefitItem& it = items[m];
-            if (!it.verts_xyz || !it.indices || !it.nodes) return fail_item(ctx, items, m, "null vertices / indices / nodes");
-            if (it.n_nodes < 1u) return fail_item(ctx, items, m, "n_nodes < 1");
-            if (it.n_nodes > 0x7fffffffu || (size_t)h_up.size() + it.n_nodes > 0xfffffff0u) return fail_item(ctx, items, m, "too many nodes for one plan");
-            nodes.resize(it.n_nodes);
-            idx.resize(3 * (size_t)it.n_tri);
-            VD_HIP_CHECK(ctx, hipMemcpy(nodes.data(), it.nodes, sizeof(VdBvhNode) * (size_t)it.n_nodes, hipMemcpyDeviceToHost));
-            if (it.n_tri) VD_HIP_CHECK(ctx, hipMemcpy(idx.data(), it.indices, 12 * (size_t)it.n_tri, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < idx.size(); ++k)
-                if (idx[k] >= it.n_vert) return fail_item(ctx, items, m, "an index >= n_vert");
-            const size_t base = h_up.size();
-            h_up.resize(base + it.n_nodes, kNoParent);
-            unsigned* up = h_up.data() + base;
-            // children follow their parent (pre-order), so one ascending sweep knows every node's parent before it gets there
-            for (unsigned k = 0; k < it.n_nodes; ++k) {
-                if (k != 0u && up[k] == kNoParent) {
-                    if (k == 1u) continue;             // the reserved slot: whatever it holds, nobody reads or writes it
-                    return fail_item(ctx, items, m, "a node other than 0 and the reserved slot 1 has no parent");
-                }
-                const VdBvhNode& nd = nodes[k];
-                if (nd.count == 0u) {
-                    const uint64_t l = nd.left_first;
-                    if (l <= k || l + 1u >= it.n_nodes) return fail_item(ctx, items, m, "an interior node's children are not both in (own id, n_nodes)");
-                    if (up[l] != kNoParent || up[l + 1u] != kNoParent) return fail_item(ctx, items, m, "a node has two parents");
-                    up[l] = k << 1; up[l + 1u] = (k << 1) | 1u;
-                } else {
-                    if ((uint64_t)nd.left_first + nd.count > it.n_tri) return fail_item(ctx, items, m, "a leaf's triangle range leaves [0, n_tri)");
-                    if (h_leaves.size() >= 0xfffffff0u) return fail_item(ctx, items, m, "too many leaves for one plan");
-                    h_leaves.push_back(make_uint4(m, k, nd.left_first, nd.count));
-                }
-            }
-            RefitItemDev& d = h_items[m];
-            d = RefitItemDev{};
-            d.verts = it.verts_xyz; d.indices = it.indices; d.nodes = it.nodes; d.info = it.mesh_info;
-            d.n_vert = it.n_vert; d.n_tri = it.n_tri; d.n_nodes = it.n_nodes; d.node_base = (unsigned)base;
-            if (it.mesh_info) {
-                d.n_chunks = it.n_vert ? (unsigned)(((size_t)it.n_vert + kVertChunk - 1u) / kVertChunk) : 1u;      // an empty fold still writes (+inf, -inf)
-                for (unsigned c = 0; c < d.n_chunks; ++c) h_chunks.push_back(make_uint2(m, c * kVertChunk));
-            }
-        }
+        std::vector<VdBvhNode> nodes;                  // the read-back buffers live until the plan is uploaded, as they always did: a megabyte
+        std::vector<unsigned> idx;                     // freed in between costs every plan call its page faults again (profiles/blas_lbvh_host_layer.md, 5)
+        RefitPlanTables t;
+        int rc = plan_tables(ctx, items, n_items, t, nodes, idx);
+        if (rc) return rc;
+        p = new VdBvhRefitPlan();
+        p->n_items = n_items; p->n_leaves = (unsigned)t.leaves.size(); p->n_chunks = (unsigned)t.chunks.size();
+        if (n_items && (rc = plan_upload(ctx, t, p))) { delete p; return rc; }      // no plan is returned after a refusal
     } catch (const std::bad_alloc&) {
+        delete p;
         VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_refit_plan: host memory");
     }
-    VdBvhRefitPlan* p = new (std::nothrow) VdBvhRefitPlan();
-    if (!p) VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_refit_plan: host memory");
-    p->n_items = n_items; p->n_leaves = (unsigned)h_leaves.size(); p->n_chunks = (unsigned)h_chunks.size();
     *out = p;
-    if (n_items == 0) return VD_OK;
-    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_items = 0, o_leaves = up256(sizeof(RefitItemDev) * n_items), o_up = o_leaves + up256(16 * h_leaves.size()),
-                 o_arr = o_up + up256(4 * h_up.size()), o_keys = o_arr + up256(4 * h_up.size()), o_done = o_keys + up256(24 * (size_t)n_items),
-                 o_chunks = o_done + up256(4 * (size_t)n_items), total = o_chunks + up256(8 * h_chunks.size());
-    std::vector<int> h_keys(6 * (size_t)n_items);
-    for (size_t m = 0; m < n_items; ++m)
-        for (int q = 0; q < 6; ++q) h_keys[6 * m + q] = q < 3 ? kKeyPosInf : kKeyNegInf;
-    hipError_t e = hipMalloc(&p->dev, total);
-    if (e != hipSuccess) { delete p; *out = nullptr; VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_refit_plan: device memory"); }
-    char* base = reinterpret_cast<char*>(p->dev);
-    e = hipMemset(base, 0, total);                     // arrival and done counters start at 0 and come back to 0 after every refit
-    if (e == hipSuccess) e = hipMemcpy(base + o_items, h_items.data(), sizeof(RefitItemDev) * n_items, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !h_leaves.empty()) e = hipMemcpy(base + o_leaves, h_leaves.data(), 16 * h_leaves.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + o_up, h_up.data(), 4 * h_up.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + o_keys, h_keys.data(), 4 * h_keys.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !h_chunks.empty()) e = hipMemcpy(base + o_chunks, h_chunks.data(), 8 * h_chunks.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the uploads ran on the default stream; the refit runs on the context's
-    if (e != hipSuccess) {
-        (void)hipFree(p->dev); delete p; *out = nullptr;
-        VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
-    }
-    p->d_items = reinterpret_cast<RefitItemDev*>(base + o_items);
-    p->d_leaves = reinterpret_cast<uint4*>(base + o_leaves);
-    p->d_up = reinterpret_cast<unsigned*>(base + o_up);
-    p->d_arrivals = reinterpret_cast<unsigned*>(base + o_arr);
-    p->d_keys = reinterpret_cast<int*>(base + o_keys);
-    p->d_done = reinterpret_cast<unsigned*>(base + o_done);
-    p->d_chunks = reinterpret_cast<uint2*>(base + o_chunks);
     return VD_OK;
 }
 
@@ -274,32 +243,20 @@ int vd_bvh_refit(VdCtx* ctx, const float* verts_xyz, uint32_t n_vert, const uint
     if (!ctx) return VD_ERR_INVALID_ARG;
     if (!verts_xyz || !indices || !nodes_inout || n_vert == 0u || n_tri == 0u || n_nodes == 0u)
         VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_bvh_refit: null or empty vertices / indices / nodes");
-    const size_t bv = 12 * (size_t)n_vert, bi = 12 * (size_t)n_tri, bn = sizeof(VdBvhNode) * (size_t)n_nodes;
-    const size_t o_i = (bv + 255) & ~(size_t)255, o_n = o_i + ((bi + 255) & ~(size_t)255);
-    char* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), o_n + bn) != hipSuccess) VD_FAIL(ctx, VD_ERR_OOM, "vd_bvh_refit: staging");
+    VdBlob blobs[3] = {{verts_xyz, 12 * (size_t)n_vert, 256, nullptr}, {indices, 12 * (size_t)n_tri, 256, nullptr},
+                       {nodes_inout, sizeof(VdBvhNode) * (size_t)n_nodes, 256, nullptr}};      // the nodes go up and come back
+    int rc = vd_stage_blobs(ctx, blobs, 3);
+    if (rc) return rc;
+    VdBvhRefitItem it{};
+    it.verts_xyz = static_cast<const float*>(blobs[0].dev); it.indices = static_cast<const uint32_t*>(blobs[1].dev);
+    it.nodes = static_cast<VdBvhNode*>(blobs[2].dev); it.mesh_info = nullptr;
+    it.n_vert = n_vert; it.n_tri = n_tri; it.n_nodes = n_nodes;
     VdBvhRefitPlan* plan = nullptr;
-    int rc = VD_OK;
-    hipError_t e = hipMemcpy(d, verts_xyz, bv, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + o_i, indices, bi, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + o_n, nodes_inout, bn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        VdBvhRefitItem it{};
-        it.verts_xyz = reinterpret_cast<const float*>(d); it.indices = reinterpret_cast<const uint32_t*>(d + o_i);
-        it.nodes = reinterpret_cast<VdBvhNode*>(d + o_n); it.mesh_info = nullptr;
-        it.n_vert = n_vert; it.n_tri = n_tri; it.n_nodes = n_nodes;
-        rc = vd_bvh_refit_plan_dev(ctx, &it, 1u, &plan);
-        if (rc == VD_OK) rc = vd_bvh_refit_planned_dev(ctx, plan);
-        if (rc == VD_OK) {
-            e = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = hipMemcpy(nodes_inout, d + o_n, bn, hipMemcpyDeviceToHost);
-        }
-    }
-    if (plan) (void)vd_bvh_refit_plan_release(ctx, plan);
-    (void)hipFree(d);
-    if (rc != VD_OK) return rc;
-    if (e != hipSuccess) VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
-    return VD_OK;
+    if ((rc = vd_bvh_refit_plan_dev(ctx, &it, 1u, &plan))) return rc;
+    rc = vd_bvh_refit_planned_dev(ctx, plan);
+    if (rc == VD_OK) rc = vd_fetch_blob(ctx, nodes_inout, &blobs[2]);
+    (void)vd_bvh_refit_plan_release(ctx, plan);
+    return rc;
 }
 
 }  // extern "C"

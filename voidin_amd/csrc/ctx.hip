@@ -59,6 +59,38 @@ int vd_fetch_blobs(VdCtx* ctx, void* const* hosts, const VdBlob* blobs, unsigned
     return VD_OK;
 }
 
+// The device memory of a plan (vd_common.hpp).  The uploads run on the null stream and are drained here; what uses the plan runs
+// on the context's stream.
+int vd_plan_tables(VdCtx* ctx, const char* who, VdPlanPart* parts, unsigned n_parts, size_t work_bytes, void** base, void** work) {
+    Arena probe{nullptr, 0};
+    for (unsigned i = 0; i < n_parts; ++i) parts[i].dev = probe.take<char>(parts[i].bytes);      // (the offset, until the memory exists)
+    const size_t tables = (probe.off + 255) & ~(size_t)255;
+    *base = nullptr;
+    if (hipMalloc(base, tables + work_bytes) != hipSuccess) {
+        *base = nullptr;
+        snprintf(ctx->err, sizeof(ctx->err), "%s: device memory", who);
+        return VD_ERR_OOM;
+    }
+    char* b = reinterpret_cast<char*>(*base);
+    hipError_t e = hipMemset(b, 0, tables);            // counters start at 0 and come back to 0 after every launch that uses them
+    for (unsigned i = 0; i < n_parts; ++i) {
+        parts[i].dev = b + reinterpret_cast<size_t>(parts[i].dev);
+        if (e == hipSuccess && parts[i].host && parts[i].bytes) e = hipMemcpy(parts[i].dev, parts[i].host, parts[i].bytes, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipFree(*base);
+        *base = nullptr;
+        VD_FAIL(ctx, VD_ERR_HIP, hipGetErrorString(e));
+    }
+    if (work) *work = b + tables;
+    return VD_OK;
+}
+
+void vd_plan_free(void* base) {
+    if (base) (void)hipFree(base);
+}
+
 // grow-only pinned host staging
 int vd_ensure_host(VdCtx* ctx, size_t need) {
     if (need <= ctx->host_stage_bytes && ctx->host_stage) return VD_OK;

@@ -1451,39 +1451,60 @@ size_t lbvh_sort_bytes(uint32_t n) {
     const size_t n_units = (n + kSortUnit - 1u) / kSortUnit, m = 256 * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
     return 4 * lbvh_arr_bytes(n) + ((4 * (8 + m + n_parts) + 255) & ~(size_t)255);
 }
+// ... carved: `ext_words` words (the plain sort's extent) lie between the arrays and the table
+struct SortWork {
+    unsigned *k[2], *v[2];                                                          // the key and value arrays, ping and pong
+    unsigned *ext, *table, *totals;                                                 // table: m = 256 * n_units words; totals: the offsets of its n_parts parts
+    unsigned m, n_parts;
+};
+SortWork sort_carve(void* work, uint32_t n, unsigned n_units, unsigned ext_words) {
+    const size_t arr = lbvh_arr_bytes(n);
+    char* base = reinterpret_cast<char*>(work);
+    SortWork w;
+    for (int i = 0; i < 2; ++i) { w.k[i] = reinterpret_cast<unsigned*>(base + i * arr); w.v[i] = reinterpret_cast<unsigned*>(base + (2 + i) * arr); }
+    w.ext = reinterpret_cast<unsigned*>(base + 4 * arr);
+    w.table = w.ext + ext_words;
+    w.m = 256u * n_units; w.n_parts = (w.m + kScanPart - 1u) / kScanPart;
+    w.totals = w.table + w.m;
+    return w;
+}
+// The four passes of the stable radix sort, eight bits each, from the first pair of arrays and back into it.  The sorts differ in
+// their count and scatter kernels alone: count(keys, shift), scatter(keys, vals, shift, totals or null, keys_out, vals_out).
+template <typename Count, typename Scatter>
+void sort_passes(hipStream_t st, const SortWork& w, Count&& count, Scatter&& scatter) {
+    const bool parts = w.m > kScanSingle;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int x = pass & 1, y = x ^ 1;
+        count(w.k[x], 8u * pass);
+        if (parts) {
+            hipLaunchKernelGGL(rs_scan_part_kernel, dim3(w.n_parts), dim3(256), 0, st, w.table, w.m, w.totals);
+            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, w.totals, w.n_parts);
+        } else {
+            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, w.table, w.m);
+        }
+        scatter(w.k[x], w.v[x], 8u * pass, parts ? w.totals : (const unsigned*)nullptr, w.k[y], w.v[y]);
+    }
+}
 int lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work, unsigned** keys, unsigned** vals) {
     hipStream_t st = ctx->stream;
     const unsigned n_units = (n + kSortUnit - 1u) / kSortUnit;
-    const size_t arr = lbvh_arr_bytes(n);
-    char* base = reinterpret_cast<char*>(work);
-    unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
-    unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
-    unsigned* ext = reinterpret_cast<unsigned*>(base + 4 * arr);                    // 8 words
-    unsigned* table = ext + 8;                                                      // 256 * n_units words
-    const unsigned m = 256u * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
-    unsigned* totals = table + m;                                                   // n_parts words: the offsets of the table's parts
-    const bool parts = m > kScanSingle;
-    VD_HIP_CHECK(ctx, hipMemsetAsync(ext, 0xff, 12, st));
-    VD_HIP_CHECK(ctx, hipMemsetAsync(ext + 3, 0, 12, st));
+    const SortWork w = sort_carve(work, n, n_units, 8u);
+    VD_HIP_CHECK(ctx, hipMemsetAsync(w.ext, 0xff, 12, st));
+    VD_HIP_CHECK(ctx, hipMemsetAsync(w.ext + 3, 0, 12, st));
     const unsigned grid = (n + 255u) / 256u;
     const unsigned ext_grid = std::min((n + kExtentPerBlock - 1u) / kExtentPerBlock, kExtentBlocks);
-    hipLaunchKernelGGL(lbvh_extent_kernel, dim3(ext_grid), dim3(256), 0, st, d_boxes, n, ext);
-    hipLaunchKernelGGL(lbvh_keys_kernel, dim3(grid), dim3(256), 0, st, d_boxes, n, ext, k[0], v[0]);
+    hipLaunchKernelGGL(lbvh_extent_kernel, dim3(ext_grid), dim3(256), 0, st, d_boxes, n, w.ext);
+    hipLaunchKernelGGL(lbvh_keys_kernel, dim3(grid), dim3(256), 0, st, d_boxes, n, w.ext, w.k[0], w.v[0]);
     const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int x = pass & 1, y = x ^ 1;
-        hipLaunchKernelGGL(rs_count_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], n, 8u * pass, n_units, table);
-        if (parts) {
-            hipLaunchKernelGGL(rs_scan_part_kernel, dim3(n_parts), dim3(256), 0, st, table, m, totals);
-            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, totals, n_parts);
-        } else {
-            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, m);
-        }
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], n, 8u * pass, n_units, table,
-                           parts ? totals : (const unsigned*)nullptr, k[y], v[y]);
-    }
+    sort_passes(st, w,
+                [&](const unsigned* k, unsigned shift) {
+                    hipLaunchKernelGGL(rs_count_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k, n, shift, n_units, w.table);
+                },
+                [&](const unsigned* k, const unsigned* v, unsigned shift, const unsigned* totals, unsigned* k_out, unsigned* v_out) {
+                    hipLaunchKernelGGL(rs_scatter_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k, v, n, shift, n_units, w.table, totals, k_out, v_out);
+                });
     VD_HIP_CHECK(ctx, hipGetLastError());
-    *keys = k[0]; *vals = v[0];                                                     // four passes: back in the first pair
+    *keys = w.k[0]; *vals = w.v[0];                                                 // four passes: back in the first pair
     return VD_OK;
 }
 // ---- the same codes and sort for MANY box arrays side by side (blas_lbvh.hip: vd_bvh_build_lbvh_planned_dev) ----------------------
@@ -1613,31 +1634,20 @@ size_t lbvh_batch_sort_bytes(uint32_t n_slots) {
 int lbvh_batch_sort_boxes(VdCtx* ctx, const float* d_boxes, const VdLbvhBatchLayout& L, const unsigned* d_n_live, void* work, unsigned** keys, unsigned** vals) {
     hipStream_t st = ctx->stream;
     const unsigned n = L.n_slots, n_units = n / kBatchUnit;
-    const size_t arr = lbvh_arr_bytes(n);
-    char* base = reinterpret_cast<char*>(work);
-    unsigned* k[2] = {reinterpret_cast<unsigned*>(base), reinterpret_cast<unsigned*>(base + arr)};
-    unsigned* v[2] = {reinterpret_cast<unsigned*>(base + 2 * arr), reinterpret_cast<unsigned*>(base + 3 * arr)};
-    unsigned* table = reinterpret_cast<unsigned*>(base + 4 * arr);                  // 256 * n_units words
-    const unsigned m = 256u * n_units, n_parts = (m + kScanPart - 1u) / kScanPart;
-    unsigned* totals = table + m;
-    const bool parts = m > kScanSingle;
+    const SortWork w = sort_carve(work, n, n_units, 0u);                            // (the extent words are the layout's)
     hipLaunchKernelGGL(lbvh_extent_seg_kernel, dim3(L.n_chunks), dim3(256), 0, st, d_boxes, L.d_segs, d_n_live, L.d_chunks, L.d_ext);
-    hipLaunchKernelGGL(lbvh_keys_seg_kernel, dim3(n / 256u), dim3(256), 0, st, d_boxes, n, L.d_segs, d_n_live, L.d_unit_seg, L.d_ext, k[0], v[0]);
+    hipLaunchKernelGGL(lbvh_keys_seg_kernel, dim3(n / 256u), dim3(256), 0, st, d_boxes, n, L.d_segs, d_n_live, L.d_unit_seg, L.d_ext, w.k[0], w.v[0]);
     const unsigned blocks = (n_units + kSortWaves - 1u) / kSortWaves;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int x = pass & 1, y = x ^ 1;
-        hipLaunchKernelGGL(rs_count_seg_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], 8u * pass, n_units, L.d_segs, L.d_unit_seg, table);
-        if (parts) {
-            hipLaunchKernelGGL(rs_scan_part_kernel, dim3(n_parts), dim3(256), 0, st, table, m, totals);
-            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, totals, n_parts);
-        } else {
-            hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, st, table, m);
-        }
-        hipLaunchKernelGGL(rs_scatter_seg_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k[x], v[x], 8u * pass, n_units, L.d_segs, L.d_unit_seg, table,
-                           parts ? totals : (const unsigned*)nullptr, k[y], v[y]);
-    }
+    sort_passes(st, w,
+                [&](const unsigned* k, unsigned shift) {
+                    hipLaunchKernelGGL(rs_count_seg_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k, shift, n_units, L.d_segs, L.d_unit_seg, w.table);
+                },
+                [&](const unsigned* k, const unsigned* v, unsigned shift, const unsigned* totals, unsigned* k_out, unsigned* v_out) {
+                    hipLaunchKernelGGL(rs_scatter_seg_kernel, dim3(blocks), dim3(64 * kSortWaves), 0, st, k, v, shift, n_units, L.d_segs, L.d_unit_seg, w.table,
+                                       totals, k_out, v_out);
+                });
     VD_HIP_CHECK(ctx, hipGetLastError());
-    *keys = k[0]; *vals = v[0];
+    *keys = w.k[0]; *vals = w.v[0];
     return VD_OK;
 }
 // work memory of one build: the sort's, then parent links and arrival words for 2n + 2 nodes

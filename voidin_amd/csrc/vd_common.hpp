@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/voidin_abi.h"
+#include "vd_plan.hpp"
 
 // TLAS refit: epoch-tagged {parent, sibling} links + arrival words for ONE instance count at a time (tlas.hip: tlas_refit_impl).
 // The context has one for vd_tlas_refit*; a VdTraceAccel with a private top level has its own (vd_trace_accel_refit_dev), so
@@ -126,8 +127,7 @@ int vd_lbvh_sort_boxes(VdCtx* ctx, const float* d_boxes, uint32_t n, void* work,
 // slots behind them; *vals are positions INSIDE the segment.  d_ext (6 words per segment) must hold the neutral elements
 // (3 x 0xffffffff, 3 x 0) when the call starts.  The number of launches depends on n_slots alone (<= or > 16 384: the scan in
 // parts), never on the counts.  `work`: vd_lbvh_batch_sort_bytes(n_slots) bytes, 256-byte aligned.  Enqueues only.
-constexpr unsigned kVdLbvhBatchUnit = 256, kVdLbvhExtentChunk = 2048;
-struct VdLbvhSeg { unsigned slot0, cap, n_units, _pad; };
+// (kVdLbvhBatchUnit, kVdLbvhExtentChunk, VdLbvhSeg: vd_plan.hpp)
 struct VdLbvhBatchLayout {
     unsigned n_slots, n_chunks;            // n_slots: a multiple of kVdLbvhBatchUnit
     const VdLbvhSeg* d_segs;               // per segment
@@ -196,12 +196,34 @@ extern "C" __attribute__((visibility("hidden"))) int vd_fetch_lists(VdCtx* ctx, 
                                                                     int pad_tail, VdDrawIndexedIndirect* out, uint64_t out_stride, uint32_t* out_counts);
 
 // ctx.hip: the staged round trip of the host-pointer forms that are not draw lists (vd_trace*, vd_traverse*, vd_primary_rays,
-// vd_tlas_*).  vd_stage_blobs drains the stream, sizes ONE arena in ctx->stage_in, places every blob at its alignment (*dev) and
-// uploads those that have a host pointer - one without is room for a result; vd_fetch_blob copies a blob back and drains again.
-// vd_fetch_blobs: blob b to hosts[b] where that is not null, ONE drain behind them all (the SAH builder's forms: two results per mesh).
+// vd_tlas_*, vd_bvh_build*, vd_bvh_build_lbvh*, vd_bvh_refit).  vd_stage_blobs drains the stream, sizes ONE arena in
+// ctx->stage_in, places every blob at its alignment (*dev) and uploads those that have a host pointer - one without is room for
+// a result; vd_fetch_blob copies a blob back and drains again.  vd_fetch_blobs: blob b to hosts[b] where that is not null, ONE
+// drain behind them all (the SAH builder's forms: two results per mesh; the LBVH batch: nodes, indices, VdMeshInfo per mesh).
 extern "C" __attribute__((visibility("hidden"))) int vd_stage_blobs(VdCtx* ctx, VdBlob* blobs, unsigned n_blobs);
 extern "C" __attribute__((visibility("hidden"))) int vd_fetch_blob(VdCtx* ctx, void* host, const VdBlob* blob);
 extern "C" __attribute__((visibility("hidden"))) int vd_fetch_blobs(VdCtx* ctx, void* const* hosts, const VdBlob* blobs, unsigned n_blobs);
+
+// Carves 256-byte aligned arrays out of one block of memory, in the order they are taken (base == null: only sizes it).
+struct Arena {
+    char* base; size_t off;
+    template <typename T> T* take(size_t n) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = reinterpret_cast<T*>(base + off);
+        off += n * sizeof(T);
+        return p;
+    }
+};
+
+// ctx.hip: the device memory of a plan (vd_bvh_lbvh_plan_dev, vd_bvh_refit_plan_dev) - ONE allocation: the parts in order, each
+// 256-byte aligned (*dev = where it went), then `work_bytes` of work memory (*work; may be null when there is none).  The parts
+// are zeroed, those with a host pointer uploaded - blocking calls on the null stream - and the null stream is drained; the work
+// memory is left as it comes.  A failure frees the allocation: "<who>: device memory" -> VD_ERR_OOM, HIP's own text -> VD_ERR_HIP.
+// The caller owns *base and gives it back with vd_plan_free (null: nothing to free) once nothing queued uses the plan.
+struct VdPlanPart { const void* host; size_t bytes; void* dev; };
+extern "C" __attribute__((visibility("hidden"))) int vd_plan_tables(VdCtx* ctx, const char* who, VdPlanPart* parts, unsigned n_parts, size_t work_bytes,
+                                                                    void** base, void** work);
+extern "C" __attribute__((visibility("hidden"))) void vd_plan_free(void* base);
 
 // Calls f with a value of the mesh-id type of that width - unsigned char, unsigned short or unsigned: the one place
 // where an id width (1, 2 or 4 bytes; checked by the caller) picks a kernel instantiation.
@@ -325,9 +347,7 @@ __device__ __forceinline__ unsigned vd_lbvh_seg_count(const VdLbvhSeg& sg, const
 // on the order-preserving integer image of the float bits.  One 256-thread block folds kVdVertChunk vertices from `first` on and
 // sends six integer atomics to keys6; the block whose arrival completes the mesh (n_chunks of them) writes info->min / max and puts
 // keys6 and *done back to their neutral values: nothing is cleared between launches.
-constexpr unsigned kVdVertChunk = 4096u;
-constexpr int kVdKeyPosInf = 0x7f800000;               // vd_key(+inf): start (and re-armed value) of a min
-constexpr int kVdKeyNegInf = (int)0x807fffff;          // vd_key(-inf): of a max
+// (kVdVertChunk, kVdKeyPosInf, kVdKeyNegInf: vd_plan.hpp)
 __device__ __forceinline__ void vd_mesh_bounds_fold(const float* __restrict__ verts, unsigned n_vert, VdMeshInfo* info, unsigned n_chunks, unsigned first,
                                                     int* keys6, unsigned* done) {
     __shared__ int part[6][4];
