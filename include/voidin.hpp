@@ -755,6 +755,16 @@ class EmitDraws {
 
 }  // namespace pass
 
+// A ray with its interval: what the vd_trace* calls of a context under VD_OPT_TRACE_RAY_RANGE = 1 walk - the closest hit (or
+// any hit) with t_min < t < t_max, t in units of `dir` as given (voidin_abi.h "Ray intervals"; both ends exclusive, a NaN or negative
+// t_min reads as 0, a NaN or oversized t_max as VD_MAX_DIST).  Without the option the two fields are ignored.
+inline VdRay ray_segment(const float eye[3], const float dir[3], float t_min = 0.0f, float t_max = VD_MAX_DIST) {
+    VdRay r;
+    r.eye[0] = eye[0]; r.eye[1] = eye[1]; r.eye[2] = eye[2]; r._pad0 = t_min;
+    r.dir[0] = dir[0]; r.dir[1] = dir[1]; r.dir[2] = dir[2]; r._pad1 = t_max;
+    return r;
+}
+
 // `traverse_tlas(ray)` for a batch (shaders/utils/bvh.wgsl:89-123)
 inline std::vector<VdHit> traverse_tlas(const Gpu& gpu, const VdTraceScene& scene, const std::vector<VdRay>& rays) {
     std::vector<VdHit> out(rays.size());
@@ -909,6 +919,9 @@ class OcclusionState {
 
 // The shadow pass's occlusion test (src/bin/raytraced_shadows.wgsl:90-102) for one point light: one ray per G-buffer
 // point, `occluded[i]` = traverse_tlas(ray).hit.  Scene pointers, positions and normals are device memory.
+// By default that is the reference's test: the ray has no end, so geometry BEHIND the light shadows the point too.  Under
+// Gpu::set_option(VD_OPT_TRACE_RAY_RANGE, 1) the rays are written as the open segment from the offset point to the light
+// (t in (0, 1)) and the walk stops there: `occluded[i]` = something lies between point i and the light.
 inline void shadow_occlusion(const Gpu& gpu, const VdTraceScene& d_scene, const float* d_positions, const float* d_normals,
                              uint32_t n_points, const float light_position[3], VdRay* d_rays_scratch, uint32_t* d_occluded) {
     gpu.check(vd_shadow_rays_dev(gpu.ctx(), d_positions, d_normals, n_points, light_position, d_rays_scratch));

@@ -106,13 +106,13 @@ typedef struct VdTlasNodeWide {
     uint32_t _pad[3];
 } VdTlasNodeWide;
 
-/* Ray + hit records of the batch traversal entry point (the reference traces one ray per
- * fragment: shaders/utils/intersections.wgsl:3-11, shaders/utils/bvh.wgsl:18-28).        */
+/* Ray + hit records of the batch traversal entry point (intersections.wgsl:3-11, bvh.wgsl:18-28: one
+ * ray per fragment there).  _pad0 / _pad1: ignored unless VD_OPT_TRACE_RAY_RANGE ("Ray intervals"). */
 typedef struct VdRay {
     float eye[3];
-    float _pad0;
+    float _pad0;                 /* t_min under VD_OPT_TRACE_RAY_RANGE, else unused  */
     float dir[3];
-    float _pad1;
+    float _pad1;                 /* t_max under VD_OPT_TRACE_RAY_RANGE, else unused  */
 } VdRay;
 
 typedef struct VdHit {
@@ -217,8 +217,8 @@ typedef enum VdOption {
     VD_OPT_BLAS_REFIT_FENCES = 31,/* 1: vd_bvh_refit_planned_dev adds an agent-scope release / acquire fence pair around every arrival-counter
                                      add of its climb, on top of the write-through stores and L1-bypassing loads that carry the boxes
                                      (same bytes; A/B: profiles/blas_refit.md); default 0                                     */
-    /* 21, 22, 23 are unassigned: they switched on ray binning and the chunked ray supply, both measured slower and
-       removed.  Like every id below VD_OPT_COUNT_ they are still accepted, and change nothing.     */
+    VD_OPT_TRACE_RAY_RANGE = 20,  /* 1: vd_trace* read VdRay::_pad0 / _pad1 as (t_min, t_max): "Ray intervals" below; default 0   */
+    /* 21-23: unassigned (ray binning, chunked ray supply: removed); accepted like every id, change nothing  */
     VD_OPT_TRACE_YIELD = 24,      /* lanes of a wave that wait (at a BLAS leaf, or with a finished ray) before the wave
                                      leaves its stepping loop to serve them; default 16                          */
     VD_OPT_TRACE_WAVES = 25,      /* persistent waves per CU (1..24); default 24                                  */
@@ -1221,6 +1221,39 @@ int vd_cull_compact_lod(VdCtx* ctx, const VdCameraUniform* camera, VdLodParams p
                         const VdMeshInfo* meshes, uint32_t n_mesh,
                         const VdInstance* instances, uint32_t n_inst,
                         VdDrawIndexedIndirect* out, uint32_t* out_count, int pad_tail);
+
+/* ------------------------------------------------------------------------------------ */
+/* Ray intervals  (VD_OPT_TRACE_RAY_RANGE; no reference counterpart: its rays have no end) */
+/* ------------------------------------------------------------------------------------ */
+/* (This section stands behind the level-of-detail calls and not next to vd_trace*, and the notes at VdRay and at the
+ * option are kept to the lines that were there: tests/stream_order_cases.py quotes lines of this header by number.)
+ * vd_ctx_set_option(ctx, VD_OPT_TRACE_RAY_RANGE, 1): every vd_trace* call of the context - vd_trace, vd_trace_dev,
+ * vd_trace_any_dev, vd_trace_wide, vd_trace_wide_dev, vd_trace_any_wide_dev, vd_trace_prepared_dev and
+ * vd_trace_any_prepared_dev, with or without a private top level (VD_OPT_TRACE_TIGHT_TLAS) - reads VdRay::_pad0 as t_min
+ * and VdRay::_pad1 as t_max:
+ *     t_lo = fmaxf(_pad0, 0.0f)          a NaN or negative t_min reads as 0
+ *     t_hi = fminf(_pad1, VD_MAX_DIST)   a NaN or oversized t_max reads as 1e30; a negative or zero t_max stays as it
+ *                                        is, and the ray misses
+ * The record of a ray is what traverse_tlas (bvh.wgsl:89-123) returns when two things change: its result starts at
+ * dist = t_hi instead of MAX_DIST, and intersect_trig accepts t_lo < t && t < hit instead of 0 < t && t < hit.  That is
+ * the minimum over (t, visit order) of the triangles the ray truly intersects inside the OPEN interval (t_lo, t_hi) -
+ * both ends are exclusive.  The arithmetic, the box tests and the pruning by the distance found so far are the same;
+ * nothing is pruned by t_lo.
+ *   - A miss is the miss record of the default: dist = VD_MAX_DIST, hit = 0 and the instance / triangle words a miss has
+ *     without the option.  It never holds t_hi.
+ *   - The any-hit flag equals the closest-hit `hit` of the same interval.
+ *   - With t_lo = 0 and t_hi = VD_MAX_DIST every output is, byte for byte, the output with the option off.
+ *   - t stays the parameter of the ray as given: `dir` is not normalised, inside an instance neither.  So t_max = 1 on a
+ *     ray whose dir = light - origin is the light, whatever the instance scales.
+ * The option is read at each call and latched by nothing (vd_trace_prepare* included): one prepared scene serves calls
+ * of both kinds.  A call enqueues and blocks exactly where it does without the option - the same launches, over other
+ * instantiations of the same kernels - so what could be captured into a HIP graph still can.
+ * The ray generators follow the option: vd_shadow_rays_dev writes _pad0 = 0, _pad1 = 1 - the open segment from the
+ * offset surface point to the light, so geometry BEHIND the light no longer shadows the point (it does in the reference,
+ * raytraced_shadows.wgsl:90-102, and by default) and no box beyond the light is entered; vd_primary_rays_dev and
+ * vd_primary_rays write 0 and VD_MAX_DIST.  With the option off they write 0 and 0 as before, bit for bit, and the walk
+ * ignores both words whatever they hold.  The host forms copy whole 32-byte rays.  ray_segment() in voidin.hpp and
+ * set_ray_range() in voidin_amd/runtime.py fill the two fields.  Measured: profiles/trace_ray_range.md.              */
 
 /* ------------------------------------------------------------------------------------ */
 /* Instance animation  (SURVEY.md §8f N2 — the upstream mutator of the cull / TLAS input)  */

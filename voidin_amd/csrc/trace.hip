@@ -65,7 +65,9 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 }
 
 // intersections.wgsl:25-45 (Moeller-Trumbore, backface cull det < 1e-10)
-__device__ __forceinline__ bool intersect_trig(const Ray& r, const float* v0, const float* v1, const float* v2, float& hit) {
+// RANGE (VD_OPT_TRACE_RAY_RANGE): t is accepted above t_lo instead of above 0 - the lower end of the ray's interval, exclusive.
+template <bool RANGE = false>
+__device__ __forceinline__ bool intersect_trig(const Ray& r, const float* v0, const float* v1, const float* v2, float& hit, float t_lo = 0.0f) {
     const float e1x = v1[0] - v0[0], e1y = v1[1] - v0[1], e1z = v1[2] - v0[2];
     const float e2x = v2[0] - v0[0], e2y = v2[1] - v0[1], e2z = v2[2] - v0[2];
     // cross(dir, edge2)
@@ -81,7 +83,7 @@ __device__ __forceinline__ bool intersect_trig(const Ray& r, const float* v0, co
     const float v = inv_det * dot3(r.dx, r.dy, r.dz, vx, vy, vz);
     if (v < 0.0f || u + v > 1.0f) return false;
     const float t = inv_det * dot3(e2x, e2y, e2z, vx, vy, vz);
-    if (t > 0.0f && t < hit) {
+    if (t > (RANGE ? t_lo : 0.0f) && t < hit) {
         hit = t;
         return true;
     }
@@ -163,6 +165,10 @@ constexpr unsigned kWavesPerCu = 24;    // persistent grid = what is resident (6
 // bit 31 set for a leaf, and cn = {1 interior / 0 leaf, index}; the 64-byte record of an interior node sits at the node's
 // own index and holds both children's boxes with their cn words (records_wide_kernel), so a step is one line as before
 // and no record is shared between two parents.
+// RANGE (VD_OPT_TRACE_RAY_RANGE): a ray is the open interval (t_lo, t_hi) of its line instead of (0, 1e30): t_lo = max(_pad0, 0) is
+// one more per-lane value that lives through the walk (intersect_trig accepts above it), t_hi = min(_pad1, 1e30) is what res.dist
+// starts from instead of kMaxDist - the pruning, the visit order and the fan-out's keys are what they were (a job's `lim` is t_hi
+// until something is hit; its t_lo is read again from the ray) - and a ray that ends without a hit reports kMaxDist, not t_hi.
 // (The narrow forms stay written out where they are used, behind `WIDE ? ... :` - a constant the front end folds: moved
 // into functions like these, the narrow kernels came out with other register numbers.)
 __device__ __forceinline__ uint2 tl_node_wide(unsigned w) { return make_uint2((w >> 31) ^ 1u, w & 0x7fffffffu); }
@@ -171,7 +177,7 @@ template <bool WIDE, typename S> __device__ __forceinline__ unsigned tl_instance
     if constexpr (WIDE) return reinterpret_cast<const VdTlasNodeWide*>(s.tlas)[leaf].instance_idx;
     else return s.tlas[leaf].instance_idx;
 }
-template <bool ANY, bool PREP, bool FAN = false, bool DEEP = false, bool WIDE = false>
+template <bool ANY, bool PREP, bool FAN = false, bool DEEP = false, bool WIDE = false, bool RANGE = false>
 __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restrict__ rays, const RaySource& src, VdHit* __restrict__ out,
                                            unsigned* __restrict__ out_any, unsigned* __restrict__ overflow) {
     const unsigned lane = threadIdx.x & 63u;
@@ -190,6 +196,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
     const size_t deep_base = DEEP ? (size_t)blockIdx.x * s.deep_cap * 64u + lane : 0u;       // one wave per workgroup in the DEEP kernel
     Ray world, ray;                        // `ray` is the active one (object space inside an instance)
     VdHit res;
+    [[maybe_unused]] float t_lo = 0.0f;    // RANGE: the lower end of the ray's interval
     unsigned ray_id = 0;
     // ((st & kBusy) != 0u) / ((st & kDone) != 0u) / ((st & kInBlas) != 0u) live as bits of one per-lane word: as `bool`s they are lane masks in scalar registers, and every
     // assignment under divergent control flow is mask algebra (550 of the loop's 1060 instructions were s_and / s_or / s_andn2)
@@ -236,7 +243,11 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                 J->state = (res.hit && !ANY) ? FAN_HIT : FAN_MISS;
             } else
             if (ANY) out_any[ray_id] = res.hit;
-            else { if (res.hit) res.instance = tl_instance<WIDE>(s, res.instance); out[ray_id] = res; }   // hits carry the leaf node until here
+            else {
+                if (res.hit) res.instance = tl_instance<WIDE>(s, res.instance);      // hits carry the leaf node until here
+                if constexpr (RANGE) { if (!res.hit) res.dist = kMaxDist; }          // a miss is the miss record, whatever t_hi was
+                out[ray_id] = res;
+            }
             st &= ~kBusy;
         }
         const unsigned long long busy_mask = __ballot(((st & kBusy) != 0u));
@@ -272,6 +283,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                             const unsigned bd = (unsigned)(src.fan.best[j1.w] >> 32);
                             if (bd < 0x7f800000u && __uint_as_float(bd + 1u) < lim) lim = __uint_as_float(bd + 1u);      // next float above a positive distance
                         }
+                        if constexpr (RANGE) t_lo = fmaxf(rays[j1.w]._pad0, 0.0f);      // no room for it in the job: read again from the ray
                         res.dist = lim; res.hit = 0u; res.instance = 0xffffffffu; res.triangle = 0xffffffffu;
                         const unsigned w = j2.y;                       // the subtree, as the stack held it (pop)
                         cn = WIDE ? tl_node_wide(w) : ((w & 0xffffu) ? make_uint2(w, 0xffffffffu) : make_uint2(0u, w >> 16));
@@ -286,6 +298,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                     world.ix = 1.0f / world.dx; world.iy = 1.0f / world.dy; world.iz = 1.0f / world.dz;   // ray_new: inv_dir = 1. / dir
                     ray = world;
                     res.dist = kMaxDist; res.hit = 0u; res.instance = 0xffffffffu; res.triangle = 0xffffffffu;
+                    if constexpr (RANGE) { t_lo = fmaxf(a.w, 0.0f); res.dist = fminf(b.w, kMaxDist); }      // VdRay::_pad0, _pad1 of the two loads
                     if constexpr (WIDE) {
                         const VdTlasNodeWide* root = reinterpret_cast<const VdTlasNodeWide*>(s.tlas);
                         cn = make_uint2((root->left | root->right) != 0u ? 1u : 0u, 0u);
@@ -353,7 +366,11 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                         if (res.hit && !ANY) atomicMin(src.fan.best + rid, ((unsigned long long)limb << 32) | pkey);
                         if ((ray_id & 0x80000000u) == 0u) {         // a ray's first fan-out: its record so far (a miss unless a job says otherwise)
                             if (ANY) out_any[rid] = res.hit;
-                            else { VdHit h = res; h.instance = inst0; out[rid] = h; }
+                            else {
+                                VdHit h = res; h.instance = inst0;
+                                if constexpr (RANGE) { if (!res.hit) h.dist = kMaxDist; }      // limb above stays t_hi: the jobs start from it
+                                out[rid] = h;
+                            }
                         }
                         // digit 1: the node the ray is at; digits 2..: the stack, top first
                         O[3] = r0; O[4] = make_uint4(dyb, dzb, limb, rid);
@@ -438,7 +455,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
             if (PREP && leaf) {               // bvh.wgsl:48-55, one triangle per iteration, in leaf order
                 const float v0[3] = {a0.x, a0.y, a0.z}, v1[3] = {a0.w, a1.x, a1.y}, v2[3] = {a1.z, a1.w, b0.x};
                 float hit = res.dist;
-                if (intersect_trig(ray, v0, v1, v2, hit)) {
+                if (intersect_trig<RANGE>(ray, v0, v1, v2, hit, t_lo)) {
                     res.dist = hit; res.hit = 1u; res.instance = tl_leaf; res.triangle = cn.x;
                     if (ANY) { st |= kDone; continue; }
                 }
@@ -537,7 +554,7 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
                     a0[0] = v0[0]; a0[1] = v0[1]; a0[2] = v0[2]; a1[0] = v1[0]; a1[1] = v1[1]; a1[2] = v1[2]; a2[0] = v2[0]; a2[1] = v2[1]; a2[2] = v2[2];
                 }
                 float hit = res.dist;
-                if (intersect_trig(ray, a0, a1, a2, hit)) {
+                if (intersect_trig<RANGE>(ray, a0, a1, a2, hit, t_lo)) {
                     res.dist = hit; res.hit = 1u; res.instance = tl_leaf; res.triangle = idx;
                     if (ANY) break;
                 }
@@ -620,6 +637,63 @@ void trace_deep_wide_kernel(Scene s, const VdRay* __restrict__ rays, const unsig
     const RaySource src{list, n, next_ray};
     trace_body<ANY, PREP, false, true, true>(s, rays, src, out, out_any, overflow);
 }
+// VD_OPT_TRACE_RAY_RANGE: the same five kernels with RANGE as one more template parameter - overloads by the length of the
+// template parameter list, so the kernels above keep their symbols as well as their code (tests/test_trace_wide_abi.py finds
+// them by symbol) and the inventory of tests/test_isa_protocols.py, which goes by name, sees no new kernel.  Same arguments.  Only
+// RANGE = true is ever instantiated (launch_first_pass, trace_deep_pass).
+// Launch bounds: t_lo is one more VGPR that lives through the stepping loop, and four narrow instantiations cannot hold their
+// sibling's bound with it (1 - 4 dwords spilled and reloaded in the loop): they get one wave per SIMD less, as the fan-out's kernels
+// did (kFanWps) - 5 (96 registers) for the closest-hit kernels without the fan-out's code, 4 (128) for the two with it that spilled
+// at 5.  Every other RANGE instantiation fits its sibling's bound and keeps it.  No RANGE instantiation spills a VGPR
+// (profiles/trace_ray_range.md has the table).
+constexpr int range_wps(bool any, bool prep, bool fan) {
+    if (!fan) return any ? 6 : 5;                                      // trace_single_kernel<0, 0>, trace_single_prep_kernel<0, 0>
+    return ((!any && !prep) || (any && prep)) ? kFanWps - 1 : kFanWps;     // trace_single_kernel<0, 1>, trace_single_prep_kernel<1, 1>
+}
+template <bool ANY, bool FAN, bool RANGE>
+__global__ __launch_bounds__(64, range_wps(ANY, false, FAN))
+void trace_single_kernel(SceneArgs a, const VdRay* __restrict__ rays, unsigned n_rays, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
+                         unsigned* __restrict__ overflow, unsigned* next_ray, const unsigned* __restrict__ gate, Fan fan) {
+    if (gate && *gate == 0u) return;
+    const Scene s{a.tlas, a.inst, a.meshes, a.bvh, a.verts, a.indices, a.n_meshes, nullptr, a.irec, a.tpair, a.mrec, a.yield, a.ovf_bits};
+    const RaySource src{nullptr, n_rays, next_ray, fan};
+    trace_body<ANY, false, FAN, false, false, RANGE>(s, rays, src, out, out_any, overflow);
+}
+template <bool ANY, bool FAN, bool RANGE>
+__global__ __launch_bounds__(64, range_wps(ANY, true, FAN))
+void trace_single_prep_kernel(SceneArgs a, const VdRay* __restrict__ rays, unsigned n_rays, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
+                              unsigned* __restrict__ overflow, unsigned* next_ray, const float* __restrict__ tris,
+                              const unsigned* __restrict__ gate, Fan fan) {
+    if (gate && *gate != 0u) return;
+    const Scene s{a.tlas, a.inst, a.meshes, a.bvh, a.verts, a.indices, a.n_meshes, tris, a.irec, a.tpair, a.mrec, a.yield, a.ovf_bits};
+    const RaySource src{nullptr, n_rays, next_ray, fan};
+    trace_body<ANY, true, FAN, false, false, RANGE>(s, rays, src, out, out_any, overflow);
+}
+template <bool ANY, bool PREP, bool RANGE>
+__global__ __launch_bounds__(64, 4)
+void trace_deep_kernel(Scene s, const VdRay* __restrict__ rays, const unsigned* __restrict__ list, const unsigned* __restrict__ n_list,
+                       VdHit* __restrict__ out, unsigned* __restrict__ out_any, unsigned* __restrict__ overflow, unsigned* next_ray) {
+    const unsigned n = *n_list;
+    const RaySource src{list, n, next_ray};
+    trace_body<ANY, PREP, false, true, false, RANGE>(s, rays, src, out, out_any, overflow);
+}
+template <bool ANY, bool PREP, bool FAN, bool RANGE>
+__global__ __launch_bounds__(64, FAN ? kFanWps : 6)
+void trace_wide_kernel(SceneArgs a, const VdRay* __restrict__ rays, unsigned n_rays, VdHit* __restrict__ out, unsigned* __restrict__ out_any,
+                       unsigned* __restrict__ overflow, unsigned* next_ray, const float* __restrict__ tris, const unsigned* __restrict__ gate, Fan fan) {
+    if (gate && (*gate != 0u) == PREP) return;
+    const Scene s{a.tlas, a.inst, a.meshes, a.bvh, a.verts, a.indices, a.n_meshes, PREP ? tris : nullptr, a.irec, a.tpair, a.mrec, a.yield, a.ovf_bits};
+    const RaySource src{nullptr, n_rays, next_ray, fan};
+    trace_body<ANY, PREP, FAN, false, true, RANGE>(s, rays, src, out, out_any, overflow);
+}
+template <bool ANY, bool PREP, bool RANGE>
+__global__ __launch_bounds__(64, 4)
+void trace_deep_wide_kernel(Scene s, const VdRay* __restrict__ rays, const unsigned* __restrict__ list, const unsigned* __restrict__ n_list,
+                            VdHit* __restrict__ out, unsigned* __restrict__ out_any, unsigned* __restrict__ overflow, unsigned* next_ray) {
+    const unsigned n = *n_list;
+    const RaySource src{list, n, next_ray};
+    trace_body<ANY, PREP, false, true, true, RANGE>(s, rays, src, out, out_any, overflow);
+}
 // bitmap of the first pass -> list of ray ids (any order: a ray's record depends on the ray alone).  n_words = ceil(n_rays / 32);
 // bits of the last word that name no ray of this call are dropped: the list holds n_rays ids, rays[] and out[] n_rays records.
 __global__ __launch_bounds__(256) void ovf_list_kernel(const unsigned* __restrict__ bits, unsigned n_words, unsigned n_rays, unsigned* __restrict__ list,
@@ -653,15 +727,15 @@ __global__ __launch_bounds__(256) void fan_resolve_kernel(const FanJob* __restri
 // Shadow rays of the reference's deferred pass (src/bin/raytraced_shadows.wgsl:97): origin = pos + nor * 0.0001,
 // dir = light.position - pos (not normalised: t is in units of the light vector, and the pass ignores it).
 __global__ __launch_bounds__(256) void shadow_rays_kernel(const float* __restrict__ pos, const float* __restrict__ nor, unsigned n,
-                                                          float lx, float ly, float lz, VdRay* __restrict__ rays) {
+                                                          float lx, float ly, float lz, float t_min, float t_max, VdRay* __restrict__ rays) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float px = pos[3u * i], py = pos[3u * i + 1u], pz = pos[3u * i + 2u];
     VdRay r;
     r.eye[0] = px + nor[3u * i] * 0.0001f; r.eye[1] = py + nor[3u * i + 1u] * 0.0001f; r.eye[2] = pz + nor[3u * i + 2u] * 0.0001f;
-    r._pad0 = 0.0f;
+    r._pad0 = t_min;
     r.dir[0] = lx - px; r.dir[1] = ly - py; r.dir[2] = lz - pz;
-    r._pad1 = 0.0f;
+    r._pad1 = t_max;
     rays[i] = r;
 }
 
@@ -669,7 +743,8 @@ __global__ __launch_bounds__(256) void shadow_rays_kernel(const float* __restric
 // y = (i / H) / H (the source divides by HEIGHT for the row; W == H == 640 there), ((x, y) - 0.5) * (2, -2),
 // eye = (clip_to_world * (x, y, 1, 1)).xyz / .w, dir = normalize((clip_to_world * (x, y, 0, 1)).xyz).
 struct Mat4 { float m[16]; };
-__global__ __launch_bounds__(256) void primary_rays_kernel(Mat4 c2w, unsigned width, unsigned height, unsigned n, VdRay* __restrict__ rays) {
+__global__ __launch_bounds__(256) void primary_rays_kernel(Mat4 c2w, unsigned width, unsigned height, unsigned n, float t_min, float t_max,
+                                                                  VdRay* __restrict__ rays) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float* M = c2w.m;
@@ -685,8 +760,8 @@ __global__ __launch_bounds__(256) void primary_rays_kernel(Mat4 c2w, unsigned wi
     }
     const float rl = 1.0f / sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
     VdRay r;
-    r.eye[0] = p[0] / p[3]; r.eye[1] = p[1] / p[3]; r.eye[2] = p[2] / p[3]; r._pad0 = 0.0f;
-    r.dir[0] = t[0] * rl; r.dir[1] = t[1] * rl; r.dir[2] = t[2] * rl; r._pad1 = 0.0f;
+    r.eye[0] = p[0] / p[3]; r.eye[1] = p[1] / p[3]; r.eye[2] = p[2] / p[3]; r._pad0 = t_min;
+    r.dir[0] = t[0] * rl; r.dir[1] = t[1] * rl; r.dir[2] = t[2] * rl; r._pad1 = t_max;
     rays[i] = r;
 }
 
@@ -1089,6 +1164,7 @@ struct TracePlan {
     bool auto_prep;                        // the call de-indexes the leaves itself, into [tris_at, tris_at + tris_bytes)
     unsigned waves, phases, fan_cap;       // the persistent grid, launches of the call (1: no fan-out), job slots
     unsigned yield, ovf_words;             // Scene::yield; words of the overflow bitmap
+    bool range;                            // VD_OPT_TRACE_RAY_RANGE: the RANGE instantiations walk (read at every call)
 };
 template <bool WIDE>
 TracePlan trace_plan(VdCtx* ctx, const SceneOf<WIDE>* sc, bool prepared, uint32_t n_rays) {
@@ -1125,6 +1201,7 @@ TracePlan trace_plan(VdCtx* ctx, const SceneOf<WIDE>* sc, bool prepared, uint32_
     p.total = p.fan_at + (p.phases > 1u ? 256 + p.best_bytes + (size_t)p.fan_cap * sizeof(FanJob) : 0);
     p.yield = (unsigned)std::max<long long>(1, ctx->option(VD_OPT_TRACE_YIELD, kYieldDefault));
     p.ovf_words = (n_rays + 31u) / 32u;
+    p.range = ctx->option(VD_OPT_TRACE_RAY_RANGE, 0) == 1;
     return p;
 }
 // the fan-out's part of the arena (nothing behind these pointers when plan.phases == 1)
@@ -1182,6 +1259,13 @@ template <typename F> void with_bools(bool x, bool y, F&& f) {
     else { if (y) f(N{}, T{}); else f(N{}, N{}); }
 }
 
+// ... and a third one, behind the two: g(a, b, std::integral_constant<bool, z>{})
+template <typename G> void with_bools(bool x, bool y, bool z, G&& g) {
+    with_bools(x, y, [&](auto a, auto b) {
+        if (z) g(a, b, std::integral_constant<bool, true>{}); else g(a, b, std::integral_constant<bool, false>{});
+    });
+}
+
 // What a walk reads and writes besides the scene; flag: the arena's first words - [0] 1 = some ray overflowed, 2 / 4 = refusals, [1] the ray counter, [2] the gate
 struct TraceIo { const VdRay* rays; uint32_t n_rays; VdHit* out; uint32_t* any; unsigned* flag; };
 
@@ -1201,18 +1285,22 @@ void launch_first_pass(VdCtx* ctx, const TracePlan& p, const Scene& s, const uns
         }
         if (ph) hipLaunchKernelGGL(fan_snapshot_kernel, dim3(1), dim3(64), 0, ctx->stream, fm.ctl, p.fan_cap, fm.ctl + 8 + ph);
         unsigned* next = ph == 0 ? io.flag + 1 : fm.ctl + ph;
-        with_bools(io.any != nullptr, p.phases > 1u, [&](auto any, auto fanned) {
-            constexpr bool A = decltype(any)::value, F = decltype(fanned)::value;
+        with_bools(io.any != nullptr, p.phases > 1u, p.range, [&](auto any, auto fanned, auto ranged) {
+            constexpr bool A = decltype(any)::value, F = decltype(fanned)::value, R = decltype(ranged)::value;
             if constexpr (WIDE) {
-                if (d_tris) hipLaunchKernelGGL((trace_wide_kernel<A, true, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any, io.flag,
+                const auto wide_prep = R ? &trace_wide_kernel<A, true, F, true> : &trace_wide_kernel<A, true, F>;
+                const auto wide_indexed = R ? &trace_wide_kernel<A, false, F, true> : &trace_wide_kernel<A, false, F>;
+                if (d_tris) hipLaunchKernelGGL(wide_prep, dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any, io.flag,
                                                next, d_tris, gate, fan);
-                if (!d_tris || gate) hipLaunchKernelGGL((trace_wide_kernel<A, false, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any,
+                if (!d_tris || gate) hipLaunchKernelGGL(wide_indexed, dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any,
                                                         io.flag, next, d_tris, gate, fan);
                 return;
             }
-            if (d_tris) hipLaunchKernelGGL((trace_single_prep_kernel<A, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any, io.flag,
+            const auto prep = R ? &trace_single_prep_kernel<A, F, true> : &trace_single_prep_kernel<A, F>;
+            const auto indexed = R ? &trace_single_kernel<A, F, true> : &trace_single_kernel<A, F>;
+            if (d_tris) hipLaunchKernelGGL(prep, dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any, io.flag,
                                            next, d_tris, gate, fan);
-            if (!d_tris || gate) hipLaunchKernelGGL((trace_single_kernel<A, F>), dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any,
+            if (!d_tris || gate) hipLaunchKernelGGL(indexed, dim3(p.waves), dim3(64), 0, ctx->stream, a, io.rays, io.n_rays, io.out, io.any,
                                                     io.flag, next, gate, fan);
         });
     }
@@ -1264,11 +1352,13 @@ int trace_deep_pass(VdCtx* ctx, const TracePlan& p, const Scene& s, bool prep_wa
         sd.ovf_bits = nullptr;
         sd.deep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(list) + list_bytes);
         sd.deep_cap = (unsigned)cap;
-        with_bools(io.any != nullptr, prep_walked, [&](auto any, auto prep) {
-            constexpr bool A = decltype(any)::value, P = decltype(prep)::value;
-            if constexpr (WIDE) hipLaunchKernelGGL((trace_deep_wide_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, io.rays, list, ctl, io.out,
+        with_bools(io.any != nullptr, prep_walked, p.range, [&](auto any, auto prep, auto ranged) {
+            constexpr bool A = decltype(any)::value, P = decltype(prep)::value, R = decltype(ranged)::value;
+            const auto deep_wide = R ? &trace_deep_wide_kernel<A, P, true> : &trace_deep_wide_kernel<A, P>;
+            const auto deep = R ? &trace_deep_kernel<A, P, true> : &trace_deep_kernel<A, P>;
+            if constexpr (WIDE) hipLaunchKernelGGL(deep_wide, dim3(waves_d), dim3(64), 0, ctx->stream, sd, io.rays, list, ctl, io.out,
                                                    io.any, io.flag, ctl + 1);
-            else hipLaunchKernelGGL((trace_deep_kernel<A, P>), dim3(waves_d), dim3(64), 0, ctx->stream, sd, io.rays, list, ctl, io.out, io.any, io.flag, ctl + 1);
+            else hipLaunchKernelGGL(deep, dim3(waves_d), dim3(64), 0, ctx->stream, sd, io.rays, list, ctl, io.out, io.any, io.flag, ctl + 1);
         });
         vd_time_end(ctx);                                                              // vd_last_gpu_ms covers the second pass too
         VD_HIP_CHECK(ctx, hipGetLastError());
@@ -1684,8 +1774,9 @@ int vd_shadow_rays_dev(VdCtx* ctx, const float* d_positions, const float* d_norm
     if (!ctx) return VD_ERR_INVALID_ARG;
     if (n_points == 0) return VD_OK;
     if (!d_positions || !d_normals || !light_position || !d_rays) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_shadow_rays: null pointer");
+    const bool range = ctx->option(VD_OPT_TRACE_RAY_RANGE, 0) == 1;      // the open segment from the offset point to the light: t in (0, 1)
     hipLaunchKernelGGL(shadow_rays_kernel, dim3((n_points + 255) / 256), dim3(256), 0, ctx->stream, d_positions, d_normals, n_points,
-                       light_position[0], light_position[1], light_position[2], d_rays);
+                       light_position[0], light_position[1], light_position[2], 0.0f, range ? 1.0f : 0.0f, d_rays);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
@@ -1700,7 +1791,8 @@ int vd_primary_rays_dev(VdCtx* ctx, const VdCameraUniform* camera, uint32_t widt
     if (n > 0xffffff00ull) VD_FAIL(ctx, VD_ERR_INVALID_ARG, "vd_primary_rays: width * height does not fit 32 bits");
     Mat4 c2w;
     for (int k = 0; k < 16; ++k) c2w.m[k] = camera->clip_to_world[k];
-    hipLaunchKernelGGL(primary_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, c2w, width, height, (unsigned)n, d_rays);
+    hipLaunchKernelGGL(primary_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, c2w, width, height, (unsigned)n, 0.0f,
+                       ctx->option(VD_OPT_TRACE_RAY_RANGE, 0) == 1 ? VD_MAX_DIST : 0.0f, d_rays);      // under the option: the whole half-line
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }

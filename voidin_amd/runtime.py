@@ -35,6 +35,17 @@ def to_numpy(t, dtype: np.dtype) -> np.ndarray:
     return t.detach().cpu().numpy().view(dtype)
 
 
+def set_ray_range(rays: np.ndarray, t_min, t_max) -> np.ndarray:
+    """Fill the interval fields of a RAY array in place (scalars or one value per ray) and return it: `_pad0` = t_min, `_pad1` = t_max,
+    which every trace call reads under the option "trace.ray_range" (VD_OPT_TRACE_RAY_RANGE, include/voidin_abi.h, "Ray intervals") and
+    ignores without it.  (0, abi.MAX_DIST) is the whole half-line: the bytes a call without the option gives."""
+    if rays.dtype != abi.RAY:
+        raise TypeError("set_ray_range takes an array of abi.RAY")
+    rays["_pad0"] = t_min
+    rays["_pad1"] = t_max
+    return rays
+
+
 class Context:
     """One VdCtx bound to a device and (by default) torch's current HIP stream."""
 
