@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "voidin_abi.h"
+#include "voidin_shadow.h"
 
 namespace voidin {
 
@@ -797,6 +798,13 @@ class TraceScene {
     void trace_any(const VdRay* d_rays, uint32_t n_rays, uint32_t* d_hit) const {
         gpu_.check(vd_trace_any_prepared_dev(gpu_.ctx(), accel_, d_rays, n_rays, d_hit));
     }
+    // the whole shadow loop (raytraced_shadows.wgsl:87-115) for n_lights lights: shadow_pass below, over this prepared scene
+    VdShadowPassInfo shadow_pass(const float* d_positions, const float* d_normals, uint32_t n_points, const VdLight* d_lights, uint32_t n_lights,
+                                 uint32_t* d_occluded, uint32_t* d_in_range = nullptr, uint32_t max_chunk_rays = 0) const {
+        VdShadowPassInfo i{};
+        gpu_.check(vd_shadow_pass_prepared_dev(gpu_.ctx(), accel_, d_positions, d_normals, n_points, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
+        return i;
+    }
     // Opt-in (Gpu::set_option(VD_OPT_TRACE_TIGHT_TLAS, 1 or 2) before construction): the scene walks a private top level over
     // tight world boxes - same hits, distances within 1e-5 (bit-equal in every test), not the reference's visit order.
     // `info().tight_tlas` says whether it does (every instance must have inv_transform = transform^-1); `update()` rebuilds it
@@ -926,6 +934,18 @@ inline void shadow_occlusion(const Gpu& gpu, const VdTraceScene& d_scene, const 
                              uint32_t n_points, const float light_position[3], VdRay* d_rays_scratch, uint32_t* d_occluded) {
     gpu.check(vd_shadow_rays_dev(gpu.ctx(), d_positions, d_normals, n_points, light_position, d_rays_scratch));
     gpu.check(vd_trace_any_dev(gpu.ctx(), &d_scene, d_rays_scratch, n_points, d_occluded));
+}
+
+// The shadow loop of that pass (raytraced_shadows.wgsl:87-115) for ALL point lights in one call (voidin_shadow.h): a point is tested
+// against every light's radius on the device, only the pairs in range become rays and are walked, and with W = (n_lights + 31) / 32
+// bit l & 31 of d_occluded[p * W + (l >> 5)] = point p is in range of light l and shadow_occlusion would report it occluded
+// (d_in_range, optional: in range at all).  The lights are the reference's Light records (crates/pools/src/light.rs:55-62) on the device.
+inline VdShadowPassInfo shadow_pass(const Gpu& gpu, const VdTraceScene& d_scene, const float* d_positions, const float* d_normals, uint32_t n_points,
+                                    const VdLight* d_lights, uint32_t n_lights, uint32_t* d_occluded, uint32_t* d_in_range = nullptr,
+                                    uint32_t max_chunk_rays = 0) {
+    VdShadowPassInfo i{};
+    gpu.check(vd_shadow_pass_dev(gpu.ctx(), &d_scene, d_positions, d_normals, n_points, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
+    return i;
 }
 
 }  // namespace voidin

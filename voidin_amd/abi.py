@@ -48,6 +48,10 @@ assert INSTANCE.itemsize == 144 and MESH_INFO.itemsize == 48 and DRAW.itemsize =
 assert CAMERA.itemsize == 320 and BVH_NODE.itemsize == 32 and TLAS_NODE.itemsize == 32
 assert TLAS_NODE_WIDE.itemsize == 48 and RAY.itemsize == 32 and HIT.itemsize == 16
 assert LOD_GROUP.itemsize == 64 and LOD_PARAMS.itemsize == 16
+# shadow pass (include/voidin_shadow.h): VdLight, the reference's Light record (crates/pools/src/light.rs:55-62)
+LIGHT = np.dtype([("position", "<f4", (3,)), ("radius", "<f4"), ("color", "<f4", (3,)), ("_pad", "<u4")])
+SHADOW_MAX_LIGHTS = 1024  # VD_SHADOW_MAX_LIGHTS: lights per vd_shadow_pass* call
+assert LIGHT.itemsize == 32
 
 MAX_DIST = np.float32(1e30)
 CULL_SPLIT_MIN = 2 << 20   # VdCtx default: vd_cull_compact / vd_cull_emit run their split form from this many instances
@@ -143,6 +147,11 @@ class TraceAccelInfoWide(C.Structure):
     """VdTraceAccelInfoWide (include/voidin_abi.h): the info of an accel made by vd_trace_prepare_wide_dev."""
     _fields_ = [("tight_tlas", C.c_uint32), ("n_tlas_nodes", C.c_uint32), ("tight_fallback_instances", C.c_uint32), ("refits_since_build", C.c_uint32),
                 ("triangle_bytes", C.c_uint64), ("d_tlas_nodes", C.c_void_p)]
+
+
+class ShadowPassInfo(C.Structure):
+    """VdShadowPassInfo (include/voidin_shadow.h)."""
+    _fields_ = [("n_rays", C.c_uint32), ("n_chunks", C.c_uint32), ("words_per_point", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class BvhBatchItem(C.Structure):
@@ -290,6 +299,13 @@ PROTOTYPES = {
     "vd_dist_allgather_dev": (_I, [_P, _P, _P, C.c_uint64]),
 }
 
+# name -> (restype, argtypes); every symbol include/voidin_shadow.h declares.  A table of its own: PROTOTYPES is the mirror of
+# include/voidin_abi.h alone.  load() binds both.
+SHADOW_PROTOTYPES = {
+    "vd_shadow_pass_dev": (_I, [_P, C.POINTER(TraceScene), _P, _P, _U, _P, _U, _U, _P, _P, C.POINTER(ShadowPassInfo)]),
+    "vd_shadow_pass_prepared_dev": (_I, [_P, _P, _P, _P, _U, _P, _U, _U, _P, _P, C.POINTER(ShadowPassInfo)]),
+}
+
 _lib = None
 
 
@@ -317,7 +333,7 @@ def load(path: str | None = None, strict: bool = True) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES}.items():
         if not strict and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol

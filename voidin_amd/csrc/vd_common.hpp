@@ -22,6 +22,16 @@ struct VdRefitArena {
     unsigned n = 0;                     // instance count the arena's layout was last used with
 };
 
+// The shadow pass's grow-only device buffer (shadow.hip).  It frees itself where ctx.hip deletes the context (vd_ctx_destroy has
+// drained the stream and made the context's device current by then).
+struct VdShadowArena {
+    void* state = nullptr; size_t bytes = 0;
+    VdShadowArena() = default;
+    ~VdShadowArena() { if (state) (void)hipFree(state); }
+    VdShadowArena(const VdShadowArena&) = delete;
+    VdShadowArena& operator=(const VdShadowArena&) = delete;
+};
+
 struct VdCtx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -51,6 +61,7 @@ struct VdCtx {
     void* trace_wide = nullptr;  size_t trace_wide_bytes = 0;     // vd_trace_wide*: the per-call records of a wide top level (64 B per node), mesh records, triangles, fan-out
     void* lbvh_state = nullptr;  size_t lbvh_state_bytes = 0;     // vd_tlas_build_lbvh*: leaf boxes, codes, the sort's tables, parent links, arrival words
     void* blas_lbvh_state = nullptr; size_t blas_lbvh_state_bytes = 0;   // vd_bvh_build_lbvh*: triangle boxes, the index copy, the sort's work memory, the radix tree
+    VdShadowArena shadow;                                         // vd_shadow_pass*: cell counts and offsets, then the rays and hit flags of one chunk (not `scratch`: the walk's arena)
     VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene
@@ -66,7 +77,7 @@ struct VdCtx {
     void* stage_aux = nullptr;   size_t stage_aux_bytes = 0;
     uint32_t* host_pinned = nullptr;                           // 64 u32 of pinned host memory
     unsigned* fault_dev = nullptr;                             // device address of host_pinned[kScanFaultWord] (vd_scan_check_fault)
-    void* host_stage = nullptr;  size_t host_stage_bytes = 0;  // grow-only pinned staging (BLAS top tree)
+    void* host_stage = nullptr;  size_t host_stage_bytes = 0;  // grow-only pinned staging (BLAS top tree; vd_shadow_pass*: the cell offsets)
     void* lvl_pinned = nullptr; hipEvent_t ev_lvl[2] = {nullptr, nullptr};   // BLAS level loop: control words of the last two levels (pinned) + their events
     hipStream_t aux_stream = nullptr;                          // copies that overlap a kernel on `stream`
     VdBvhBuildStats bvh_stats = {};                            // vd_bvh_last_build_stats

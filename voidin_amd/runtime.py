@@ -627,6 +627,27 @@ class Context:
         lp = (C.c_float * 3)(*[float(x) for x in light_position])
         self._chk(self.lib.vd_shadow_rays_dev(self.h, abi.ptr(d_positions), abi.ptr(d_normals), n_points, lp, abi.ptr(d_rays)))
 
+    def shadow_pass_dev(self, scene: "Context.DeviceScene", d_positions, d_normals, n_points, d_lights, n_lights, d_occluded, d_in_range=None,
+                        max_chunk_rays=0) -> dict:
+        """vd_shadow_pass_dev (include/voidin_shadow.h): the shadow loop of raytraced_shadows.wgsl:87-115 for n_points points and
+        n_lights lights (abi.LIGHT records on the device).  Bit l & 31 of word p * W + (l >> 5), W = (n_lights + 31) // 32, of
+        d_in_range (may be None) = point p is in range of light l; of d_occluded = it is, and its shadow ray hits something.
+        Blocks.  -> {"n_rays", "n_chunks", "words_per_point"}."""
+        if scene.wide:
+            raise TypeError("a scene whose top level is TLAS_NODE_WIDE goes through trace_prepare and shadow_pass_prepared_dev")
+        info = abi.ShadowPassInfo()
+        self._chk(self.lib.vd_shadow_pass_dev(self.h, C.byref(scene.struct), abi.ptr(d_positions), abi.ptr(d_normals), n_points, abi.ptr(d_lights), n_lights,
+                                              max_chunk_rays, abi.ptr(d_occluded), abi.ptr(d_in_range), C.byref(info)))
+        return {"n_rays": int(info.n_rays), "n_chunks": int(info.n_chunks), "words_per_point": int(info.words_per_point)}
+
+    def shadow_pass_prepared_dev(self, accel: "Context.TraceAccel", d_positions, d_normals, n_points, d_lights, n_lights, d_occluded, d_in_range=None,
+                                 max_chunk_rays=0) -> dict:
+        """vd_shadow_pass_prepared_dev: the same over a prepared scene - narrow, wide or with a private top level."""
+        info = abi.ShadowPassInfo()
+        self._chk(self.lib.vd_shadow_pass_prepared_dev(self.h, accel.h, abi.ptr(d_positions), abi.ptr(d_normals), n_points, abi.ptr(d_lights), n_lights,
+                                                       max_chunk_rays, abi.ptr(d_occluded), abi.ptr(d_in_range), C.byref(info)))
+        return {"n_rays": int(info.n_rays), "n_chunks": int(info.n_chunks), "words_per_point": int(info.words_per_point)}
+
     def primary_rays_dev(self, camera, width, height, d_rays):
         """One ray per pixel from camera.clip_to_world (src/bin/bvh_cpu.rs:71-83); d_rays: width*height rays."""
         cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
