@@ -28,6 +28,7 @@
 
 #include "voidin_abi.h"
 #include "voidin_shadow.h"
+#include "voidin_gbuffer.h"
 
 namespace voidin {
 
@@ -805,6 +806,13 @@ class TraceScene {
         gpu_.check(vd_shadow_pass_prepared_dev(gpu_.ctx(), accel_, d_positions, d_normals, n_points, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
         return i;
     }
+    // ... straight from the G-buffer's three images, the bits per PIXEL: shadow_gbuffer below, over this prepared scene
+    VdShadowGBufferInfo shadow_gbuffer(const VdCameraUniform& camera, const VdGBuffer& gb, const VdLight* d_lights, uint32_t n_lights, uint32_t* d_occluded,
+                                       uint32_t* d_in_range = nullptr, uint32_t max_chunk_rays = 0) const {
+        VdShadowGBufferInfo i{};
+        gpu_.check(vd_shadow_gbuffer_prepared_dev(gpu_.ctx(), accel_, &camera, &gb, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
+        return i;
+    }
     // Opt-in (Gpu::set_option(VD_OPT_TRACE_TIGHT_TLAS, 1 or 2) before construction): the scene walks a private top level over
     // tight world boxes - same hits, distances within 1e-5 (bit-equal in every test), not the reference's visit order.
     // `info().tight_tlas` says whether it does (every instance must have inv_transform = transform^-1); `update()` rebuilds it
@@ -945,6 +953,28 @@ inline VdShadowPassInfo shadow_pass(const Gpu& gpu, const VdTraceScene& d_scene,
                                     uint32_t max_chunk_rays = 0) {
     VdShadowPassInfo i{};
     gpu.check(vd_shadow_pass_dev(gpu.ctx(), &d_scene, d_positions, d_normals, n_points, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
+    return i;
+}
+
+// Lines 62-89 of that pass for a whole image (voidin_gbuffer.h): the pixels whose material is neither 0 nor LIGHT_MATERIAL, in pixel
+// order, as points - world position from the depth image under camera.clip_to_world, normal from the octahedral word, pixel id
+// y * width + x.  The arrays take width * height entries at most; d_n_points takes the count, which is also returned (the call
+// blocks; vd_gbuffer_points_dev with out_n_points == NULL is the form that only enqueues).
+inline uint32_t gbuffer_points(const Gpu& gpu, const VdCameraUniform& camera, const VdGBuffer& gb, float* d_positions, float* d_normals, uint32_t* d_pixels,
+                               uint32_t* d_n_points) {
+    uint32_t n = 0;
+    gpu.check(vd_gbuffer_points_dev(gpu.ctx(), &camera, &gb, d_positions, d_normals, d_pixels, d_n_points, &n));
+    return n;
+}
+
+// The shadow loop for every pixel of a G-buffer in one call: gbuffer_points, shadow_pass over the points, and the bits back per
+// PIXEL - with W = (n_lights + 31) / 32, bit l & 31 of d_occluded[i * W + (l >> 5)] is what shadow_pass gives the point of pixel i for
+// light l, and zero for a pixel that is no receiver (d_in_range, optional, likewise).  What the shader binds in place of its light
+// loop's traverse_tlas: INTEGRATION.md.
+inline VdShadowGBufferInfo shadow_gbuffer(const Gpu& gpu, const VdTraceScene& d_scene, const VdCameraUniform& camera, const VdGBuffer& gb, const VdLight* d_lights,
+                                          uint32_t n_lights, uint32_t* d_occluded, uint32_t* d_in_range = nullptr, uint32_t max_chunk_rays = 0) {
+    VdShadowGBufferInfo i{};
+    gpu.check(vd_shadow_gbuffer_dev(gpu.ctx(), &d_scene, &camera, &gb, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
     return i;
 }
 

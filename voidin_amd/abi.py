@@ -154,6 +154,24 @@ class ShadowPassInfo(C.Structure):
     _fields_ = [("n_rays", C.c_uint32), ("n_chunks", C.c_uint32), ("words_per_point", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class GBuffer(C.Structure):
+    """VdGBuffer (include/voidin_gbuffer.h): the three images of voidin's GBuffer as device pointers with a pitch in bytes each."""
+    _fields_ = [("depth", C.c_void_p), ("depth_pitch", C.c_uint32),
+                ("normal_uv", C.c_void_p), ("normal_uv_pitch", C.c_uint32),
+                ("material", C.c_void_p), ("material_pitch", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class ShadowGBufferInfo(C.Structure):
+    """VdShadowGBufferInfo (include/voidin_gbuffer.h)."""
+    _fields_ = [("n_points", C.c_uint32), ("n_rays", C.c_uint32), ("n_chunks", C.c_uint32), ("words_per_point", C.c_uint32)]
+
+
+GBUFFER_NO_MATERIAL = 0     # VD_GBUFFER_NO_MATERIAL
+GBUFFER_LIGHT_MATERIAL = 2  # VD_GBUFFER_LIGHT_MATERIAL
+assert C.sizeof(GBuffer) == 56 and C.sizeof(ShadowGBufferInfo) == 16
+
+
 class BvhBatchItem(C.Structure):
     """VdBvhBatchItem (include/voidin_abi.h, "Batched BLAS build")."""
     _fields_ = [("verts_xyz", C.c_void_p), ("indices_inout", C.c_void_p), ("out_nodes", C.c_void_p),
@@ -300,10 +318,17 @@ PROTOTYPES = {
 }
 
 # name -> (restype, argtypes); every symbol include/voidin_shadow.h declares.  A table of its own: PROTOTYPES is the mirror of
-# include/voidin_abi.h alone.  load() binds both.
+# include/voidin_abi.h alone.  load() binds every table.
 SHADOW_PROTOTYPES = {
     "vd_shadow_pass_dev": (_I, [_P, C.POINTER(TraceScene), _P, _P, _U, _P, _U, _U, _P, _P, C.POINTER(ShadowPassInfo)]),
     "vd_shadow_pass_prepared_dev": (_I, [_P, _P, _P, _P, _U, _P, _U, _U, _P, _P, C.POINTER(ShadowPassInfo)]),
+}
+
+# ... and every symbol include/voidin_gbuffer.h declares, likewise apart from the other two.
+GBUFFER_PROTOTYPES = {
+    "vd_gbuffer_points_dev": (_I, [_P, _P, C.POINTER(GBuffer), _P, _P, _P, _P, C.POINTER(_U)]),
+    "vd_shadow_gbuffer_dev": (_I, [_P, C.POINTER(TraceScene), _P, C.POINTER(GBuffer), _P, _U, _U, _P, _P, C.POINTER(ShadowGBufferInfo)]),
+    "vd_shadow_gbuffer_prepared_dev": (_I, [_P, _P, _P, C.POINTER(GBuffer), _P, _U, _U, _P, _P, C.POINTER(ShadowGBufferInfo)]),
 }
 
 _lib = None
@@ -333,7 +358,7 @@ def load(path: str | None = None, strict: bool = True) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES, **GBUFFER_PROTOTYPES}.items():
         if not strict and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol

@@ -32,6 +32,18 @@ struct VdShadowArena {
     VdShadowArena& operator=(const VdShadowArena&) = delete;
 };
 
+// The G-buffer front end's grow-only device buffers (gbuffer.hip), freed the same way: the tile tables of an image, and the points of
+// a vd_shadow_gbuffer* call with their per-point words.  Two buffers, so that sizing the second by the count the first gave never
+// moves the tables.
+struct VdGBufferArena {
+    void* tables = nullptr; size_t tables_bytes = 0;
+    void* points = nullptr; size_t points_bytes = 0;
+    VdGBufferArena() = default;
+    ~VdGBufferArena() { if (tables) (void)hipFree(tables); if (points) (void)hipFree(points); }
+    VdGBufferArena(const VdGBufferArena&) = delete;
+    VdGBufferArena& operator=(const VdGBufferArena&) = delete;
+};
+
 struct VdCtx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -62,6 +74,7 @@ struct VdCtx {
     void* lbvh_state = nullptr;  size_t lbvh_state_bytes = 0;     // vd_tlas_build_lbvh*: leaf boxes, codes, the sort's tables, parent links, arrival words
     void* blas_lbvh_state = nullptr; size_t blas_lbvh_state_bytes = 0;   // vd_bvh_build_lbvh*: triangle boxes, the index copy, the sort's work memory, the radix tree
     VdShadowArena shadow;                                         // vd_shadow_pass*: cell counts and offsets, then the rays and hit flags of one chunk (not `scratch`: the walk's arena)
+    VdGBufferArena gbuffer;                                       // vd_gbuffer_points_dev / vd_shadow_gbuffer*: tile counts and offsets; points, normals, pixel ids, per-point words
     VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene

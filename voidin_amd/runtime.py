@@ -648,6 +648,49 @@ class Context:
                                                        max_chunk_rays, abi.ptr(d_occluded), abi.ptr(d_in_range), C.byref(info)))
         return {"n_rays": int(info.n_rays), "n_chunks": int(info.n_chunks), "words_per_point": int(info.words_per_point)}
 
+    @staticmethod
+    def gbuffer(d_depth, d_normal_uv, d_material, width, height, depth_pitch=None, normal_uv_pitch=None, material_pitch=None) -> "abi.GBuffer":
+        """VdGBuffer (include/voidin_gbuffer.h) over three device images; a pitch (bytes per row) left out is the packed one."""
+        return abi.GBuffer(abi.ptr(d_depth), 4 * width if depth_pitch is None else depth_pitch,
+                           abi.ptr(d_normal_uv), 8 * width if normal_uv_pitch is None else normal_uv_pitch,
+                           abi.ptr(d_material), width if material_pitch is None else material_pitch, width, height)
+
+    def gbuffer_points_dev(self, camera, gb: "abi.GBuffer", d_positions, d_normals, d_pixels, d_n_points, read_back=True):
+        """vd_gbuffer_points_dev: the receivers of a G-buffer (material neither 0 nor 2) in pixel order - world position from the
+        depth image, normal from the octahedral word, pixel id - and their count in d_n_points.  read_back: the call blocks and
+        returns the count; without it the call only enqueues and returns None."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        n = C.c_uint32(0)
+        self._chk(self.lib.vd_gbuffer_points_dev(self.h, cam.ctypes.data, C.byref(gb), abi.ptr(d_positions), abi.ptr(d_normals), abi.ptr(d_pixels),
+                                                 abi.ptr(d_n_points), C.byref(n) if read_back else None))
+        return int(n.value) if read_back else None
+
+    @staticmethod
+    def _gbuffer_info(info) -> dict:
+        return {"n_points": int(info.n_points), "n_rays": int(info.n_rays), "n_chunks": int(info.n_chunks), "words_per_point": int(info.words_per_point)}
+
+    def shadow_gbuffer_dev(self, scene: "Context.DeviceScene", camera, gb: "abi.GBuffer", d_lights, n_lights, d_occluded, d_in_range=None,
+                           max_chunk_rays=0) -> dict:
+        """vd_shadow_gbuffer_dev (include/voidin_gbuffer.h): the shadow loop for every pixel of a G-buffer.  W = (n_lights + 31) // 32
+        words per PIXEL in d_occluded and d_in_range (may be None): a receiver's are those of shadow_pass_dev for its point, every other
+        pixel's are zero.  Blocks.  -> {"n_points", "n_rays", "n_chunks", "words_per_point"}."""
+        if scene.wide:
+            raise TypeError("a scene whose top level is TLAS_NODE_WIDE goes through trace_prepare and shadow_gbuffer_prepared_dev")
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        info = abi.ShadowGBufferInfo()
+        self._chk(self.lib.vd_shadow_gbuffer_dev(self.h, C.byref(scene.struct), cam.ctypes.data, C.byref(gb), abi.ptr(d_lights), n_lights, max_chunk_rays,
+                                                 abi.ptr(d_occluded), abi.ptr(d_in_range), C.byref(info)))
+        return self._gbuffer_info(info)
+
+    def shadow_gbuffer_prepared_dev(self, accel: "Context.TraceAccel", camera, gb: "abi.GBuffer", d_lights, n_lights, d_occluded, d_in_range=None,
+                                    max_chunk_rays=0) -> dict:
+        """vd_shadow_gbuffer_prepared_dev: the same over a prepared scene - narrow, wide or with a private top level."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        info = abi.ShadowGBufferInfo()
+        self._chk(self.lib.vd_shadow_gbuffer_prepared_dev(self.h, accel.h, cam.ctypes.data, C.byref(gb), abi.ptr(d_lights), n_lights, max_chunk_rays,
+                                                          abi.ptr(d_occluded), abi.ptr(d_in_range), C.byref(info)))
+        return self._gbuffer_info(info)
+
     def primary_rays_dev(self, camera, width, height, d_rays):
         """One ray per pixel from camera.clip_to_world (src/bin/bvh_cpu.rs:71-83); d_rays: width*height rays."""
         cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
