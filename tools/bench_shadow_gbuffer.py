@@ -8,12 +8,12 @@ and 0 elsewhere, rows at the 256-byte pitches a copy_texture_to_buffer gives.  p
 
   A/B   the two calls alternated in one process on one context, wall clock around each (both block), median and spread of --reps
         after a warm-up of both.  During the warm-up the per-pixel words are compared with the bare pass's per-point words at the
-        points' pixels, and every other pixel's words with zero - under --fan 1 by default, because the fanned-out any-hit walk is not
-        reproducible on this scene (profiles/shadow_pass.md, section 3).
+        points' pixels, and every other pixel's words with zero - under the library's own fan-out unless --fan says otherwise (the
+        fanned-out any-hit walk is reproducible since the supply rule: profiles/shadow_pass.md, section 3; profiles/trace_fan_supply.md).
   --gbuffer-only   the new call alone, a few times per share, and the bytes each of its kernels must move, computed from the
         shapes: for a run under `rocprofv3 --kernel-trace --stats`.
 
-    python tools/bench_shadow_gbuffer.py [--rays 1024] [--reps 21] [--gbuffer-only] [--fan 1]"""
+    python tools/bench_shadow_gbuffer.py [--rays 1024] [--reps 21] [--gbuffer-only] [--fan N]"""
 import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,8 +26,8 @@ ap.add_argument("--reps", type=int, default=21, help="timed repetitions of each 
 ap.add_argument("--lights", type=int, default=64)
 ap.add_argument("--shares", type=float, nargs="+", default=(1.0, 0.25, 0.05))
 ap.add_argument("--gbuffer-only", action="store_true")
-ap.add_argument("--fan", type=int, default=1, help="VD_OPT_TRACE_FAN for the whole run (1 = the one-launch walk, whose flags are reproducible on this scene; "
-                "0 = the library's default, as the tables of profiles/shadow_pass.md were taken)")
+ap.add_argument("--fan", type=int, default=0, help="VD_OPT_TRACE_FAN for the whole run (0 = the library's default, as the tables of profiles/shadow_pass.md "
+                "were taken; 1 = the one-launch walk)")
 args = ap.parse_args()
 assert args.reps >= 20 or args.gbuffer_only
 ctx = Context(0)

@@ -312,7 +312,18 @@ __device__ __forceinline__ void trace_body(const Scene& s, const VdRay* __restri
             }
             if (done) exhausted = true;     // wave-uniform
         }
-        if (!__ballot(((st & kBusy) != 0u))) break;
+        // The supply rule: a wave ends only when its launch's supply is exhausted.  For fresh rays "nobody busy after a draw" can only
+        // mean that; for jobs it also happens when every job just drawn was skipped (fillers, finished slots, any-hit rays already
+        // known to be occluded) - the wave then goes round once more with nobody stepping and draws again (the counter advances with
+        // every draw, so this ends).  Ending there left the positions behind it to the other waves, and when all of them ended so,
+        // to nobody: those jobs were never walked and an any-hit ray kept the 0 of its first fan-out (profiles/trace_fan_supply.md).
+        // (Written as part of this one condition: a `continue` of its own here cost the fan-out's kernels 9 - 30 spilled VGPRs.)
+        if (!__ballot(((st & kBusy) != 0u)) && (exhausted || !(FAN && from_jobs))) {
+#ifdef VD_TUNING
+            if (!exhausted && lane == 0) atomicAdd(overflow + 3, 1u);      // must stay 0 (vd_debug_trace_fan)
+#endif
+            break;
+        }
         if (FAN && exhausted && src.fan.below != 0u && !fan_off) {
             // nothing left to draw and few rays alive here: every ray that is between instances (its stack holds TLAS entries
             // only) becomes jobs and leaves; rays inside an instance go on and are looked at again when the wave next gets here
@@ -1205,7 +1216,7 @@ TracePlan trace_plan(VdCtx* ctx, const SceneOf<WIDE>* sc, bool prepared, uint32_
     return p;
 }
 // the fan-out's part of the arena (nothing behind these pointers when plan.phases == 1)
-struct FanMem { unsigned* ctl; unsigned long long* best; FanJob* jobs; };      // ctl: [0] append, [1 + p] supply counter of launch p, [8 + p] end of launch p's supply
+struct FanMem { unsigned* ctl; unsigned long long* best; FanJob* jobs; };      // ctl: [0] append, [p] supply counter of launch p >= 1, [8 + p] end of launch p's supply (it begins at [8 + p - 1])
 FanMem fan_mem(const TracePlan& p, char* arena) {
     char* const at = arena + p.fan_at;
     return {reinterpret_cast<unsigned*>(at), reinterpret_cast<unsigned long long*>(at + 256), reinterpret_cast<FanJob*>(at + 256 + p.best_bytes)};
@@ -1393,6 +1404,10 @@ int launch_trace(VdCtx* ctx, const SceneOf<WIDE>* sc, const float* d_tris, const
     VD_HIP_CHECK(ctx, hipMemsetAsync(io.flag, 0, 64, ctx->stream));
 #endif
     const FanMem fm = fan_mem(p, arena);
+#ifdef VD_TUNING
+    ctx->dbg_fan_wide = WIDE; ctx->dbg_fan_at = p.fan_at;      // vd_debug_trace_fan: where this call's words lie
+    ctx->dbg_fan_phases = p.phases; ctx->dbg_fan_waves = p.waves; ctx->dbg_fan_cap = p.fan_cap;
+#endif
     if (p.phases > 1u) {
         VD_HIP_CHECK(ctx, hipMemsetAsync(fm.ctl, 0, 256, ctx->stream));
         if (!d_any) VD_HIP_CHECK(ctx, hipMemsetAsync(fm.best, 0xff, p.best_bytes, ctx->stream));
@@ -1674,6 +1689,28 @@ int vd_debug_trace_counters(VdCtx* ctx, uint64_t* out /*[11]*/) {
     unsigned h[16];
     if (hipMemcpy(h, ctx->scratch, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return VD_ERR_HIP;
     out[0] = h[4]; out[1] = h[5]; out[2] = (uint64_t)h[6] | ((uint64_t)h[7] << 32); out[3] = h[8]; out[4] = h[9]; out[5] = h[10]; out[6] = h[11]; out[7] = h[12]; out[8] = h[13]; out[9] = h[14]; out[10] = h[15];
+    return VD_OK;
+}
+// tuning build only: the job supply of the last trace call (narrow or wide).  out[0] = waves that left the outer loop with nobody
+// busy while their launch's supply was not exhausted (the supply rule: always 0), out[1] = launches the call ran as, out[2] = waves
+// of the grid, out[3] = job slots, out[4] = jobs appended (ctl[0]; may exceed the slots when the list filled up), and for launch
+// p = 1 .. 3: out[4 + p] = its supply counter (ctl[p]: positions drawn, the draws past the end included), out[8 + p] = the end of its
+// supply (ctl[8 + p]; it begins at out[8 + p - 1], out[8] = 0).  A call of one launch leaves out[3..] zero.
+int vd_debug_trace_fan(VdCtx* ctx, uint32_t* out /*[16]*/) {
+    VdDeviceGuard vd_guard_(ctx);
+    if (!ctx || !out || ctx->dbg_fan_phases == 0u) return VD_ERR_INVALID_ARG;
+    const char* arena = reinterpret_cast<const char*>(ctx->dbg_fan_wide ? ctx->trace_wide : ctx->scratch);
+    const size_t arena_bytes = ctx->dbg_fan_wide ? ctx->trace_wide_bytes : ctx->scratch_bytes;
+    if (!arena || arena_bytes < 256 || (ctx->dbg_fan_phases > 1u && arena_bytes < ctx->dbg_fan_at + 256)) return VD_ERR_INVALID_ARG;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return VD_ERR_HIP;
+    memset(out, 0, 16 * sizeof(uint32_t));
+    unsigned h[16];
+    if (hipMemcpy(h, arena, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return VD_ERR_HIP;
+    out[0] = h[3]; out[1] = ctx->dbg_fan_phases; out[2] = ctx->dbg_fan_waves;
+    if (ctx->dbg_fan_phases == 1u) return VD_OK;
+    if (hipMemcpy(h, arena + ctx->dbg_fan_at, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return VD_ERR_HIP;
+    out[3] = ctx->dbg_fan_cap; out[4] = h[0];
+    for (unsigned p = 1; p < 4u; ++p) { out[4 + p] = h[p]; out[8 + p] = h[8 + p]; }
     return VD_OK;
 }
 #endif

@@ -85,6 +85,10 @@ struct VdCtx {
     void fan_remember(const void* tlas, unsigned nodes, unsigned inst, bool few_jobs) { fan_tlas = tlas; fan_nodes = nodes; fan_inst = inst; fan_idle_calls = few_jobs ? 15u : 0u; }
     unsigned long long scan_launches = 0;
     void* dbg_ptr = nullptr; unsigned dbg_count = 0; void* dbg_ptr2 = nullptr;   // tuning hooks
+#ifdef VD_TUNING
+    bool dbg_fan_wide = false; size_t dbg_fan_at = 0;                                // vd_debug_trace_fan: the last trace call's arena (scratch / trace_wide) and where its fan-out block lay
+    unsigned dbg_fan_phases = 0, dbg_fan_waves = 0, dbg_fan_cap = 0;                 // ... its launches (0: no trace call yet), grid and job slots
+#endif
     void* stage_in = nullptr;    size_t stage_in_bytes = 0;    // host-pointer API staging
     void* stage_out = nullptr;   size_t stage_out_bytes = 0;
     void* stage_aux = nullptr;   size_t stage_aux_bytes = 0;
