@@ -656,7 +656,8 @@ int vd_bvh_build_lbvh_batch(VdCtx* ctx, VdBvhLbvhBatchItem* items /* host pointe
  *   out_packed_end one past the last packed node written (host pointer, may be NULL)
  * _dev: every pointer inside the items and packed_nodes are device pointers; blocks like
  * vd_bvh_build_dev.  An error fails the whole batch (nothing is to be used); items[m].status names the
- * mesh when the error has one (bad index, capacity).                                              */
+ * mesh when the error has one (bad index, capacity, VD_ERR_DEGENERATE: of several degenerate meshes
+ * the first in the batch among those found when the build stopped; vd_last_error says "mesh M" too). */
 typedef struct VdBvhBatchItem {
     const float* verts_xyz;        /* n_vert * 3 floats                                     */
     uint32_t*    indices_inout;    /* n_tri * 3 u32, mesh-local                             */

@@ -123,4 +123,5 @@ def tree_depth(nodes):
 
 
 FIXTURES = ["blas_plane.npz", "blas_sphere_1_1.npz", "blas_soup64.npz", "blas_knot_2k.npz", "blas_sphere_1_10.npz",
-            "blas_plane_rot.npz", "blas_cube_obj.npz", "blas_soup_nan.npz"]
+            "blas_plane_rot.npz", "blas_cube_obj.npz", "blas_soup_nan.npz",
+            "blas_grid_24.npz", "blas_voxel_6.npz"]      # lattice meshes (tests/blas_lattice_cases.py): flat boxes, shared vertices

@@ -84,6 +84,21 @@ def blas_cases():
         print("blas", name, "tris", len(i) // 3, "nodes", len(n_np))
 
 
+def lattice_cases():
+    """Two of the lattice meshes of tests/blas_lattice_cases.py - vertices on a grid of spacing 3, so costs tie between
+    different splits and centroids lie exactly on split planes in nodes of every size: the 24 x 24 flat grid (1152
+    triangles) and the boundary of a 6^3 occupancy grid."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import blas_lattice_cases as lattice
+    for out, name in (("grid_24", "grid_24x24"), ("voxel_6", "voxel_6")):
+        v, i = lattice.case(name)
+        n_np, i_np = npr.bvh_build(v, i)
+        n_c, i_c = ref.bvh_build(v, i)
+        assert same_bits(n_np, n_c) and np.array_equal(i_np, i_c), name
+        np.savez_compressed(os.path.join(OUT, f"blas_{out}.npz"), vertices=v, indices=i, nodes=n_np, indices_out=i_np)
+        print("blas", out, "tris", len(i) // 3, "nodes", len(n_np))
+
+
 def nan_soup(n_tri=200):
     """A soup with NaN vertices: Rust's f32::min/max (glam scalar Vec3::min/max, blas.rs:190-198) IGNORE a NaN operand,
     so the reference builds a tree - the NaN vertex drops out of every box, its triangle's centroid fails every `<`
@@ -458,6 +473,7 @@ if __name__ == "__main__":
     model_scene_cases()
     cull_cases()
     blas_cases()
+    lattice_cases()
     builtin_pool_case()
     tlas_trace_cases()
     nan_cases()

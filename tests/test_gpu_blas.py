@@ -11,7 +11,8 @@ pytestmark = pytest.mark.gpu
 
 BLAS = ["blas_plane.npz", "blas_sphere_1_1.npz", "blas_soup64.npz", "blas_knot_2k.npz", "blas_sphere_1_10.npz",
         "blas_plane_rot.npz", "blas_cube_obj.npz",   # reference-held inputs: mesh/mod.rs:269-272, assets/cube/cube.obj
-        "blas_soup_nan.npz"]                         # NaN vertices build (f32::min/max ignore a NaN: blas.rs:190-198)
+        "blas_soup_nan.npz",                         # NaN vertices build (f32::min/max ignore a NaN: blas.rs:190-198)
+        "blas_grid_24.npz", "blas_voxel_6.npz"]      # lattice meshes: tied costs, centroids on split planes (tests/blas_lattice_cases.py)
 
 
 def diff_report(got, want):
@@ -178,10 +179,12 @@ def test_degenerate_and_bad_input(ctx):
     with pytest.raises(VoidinError) as e:
         ctx.bvh_build(v, np.array([0, 1, 7], np.uint32))
     assert e.value.code == abi.VD_ERR_INVALID_ARG
-    # big degenerate: 2000 identical triangles -> phase A rejects every candidate
-    with pytest.raises(VoidinError) as e:
-        ctx.bvh_build(v, np.tile(np.array([0, 1, 2], np.uint32), 2000))
-    assert e.value.code == abi.VD_ERR_DEGENERATE
+    # big degenerate: 2000 identical triangles -> the mid tier (segments of 513..2048) rejects every candidate of the root;
+    # 2304 -> phase A does (segments above 2048)
+    for n in (2000, 2304):
+        with pytest.raises(VoidinError) as e:
+            ctx.bvh_build(v, np.tile(np.array([0, 1, 2], np.uint32), n))
+        assert e.value.code == abi.VD_ERR_DEGENERATE
 
 
 def test_device_entry_point_and_determinism(ctx, oracle):

@@ -10,7 +10,8 @@ from voidin_amd import abi, synth
 BLAS = ["blas_plane.npz", "blas_sphere_1_1.npz", "blas_sphere_1_10.npz", "blas_soup64.npz", "blas_knot_2k.npz",
         "blas_plane_rot.npz",    # the X-rotated built-in plane, crates/pools/src/mesh/mod.rs:269-272
         "blas_cube_obj.npz",     # the reference's own asset assets/cube/cube.obj through ObjModel::load
-        "blas_soup_nan.npz"]     # NaN vertices: f32::min/max ignore them (blas.rs:190-198), the reference builds a tree
+        "blas_soup_nan.npz",     # NaN vertices: f32::min/max ignore them (blas.rs:190-198), the reference builds a tree
+        "blas_grid_24.npz", "blas_voxel_6.npz"]    # lattice meshes: tied costs, centroids on split planes (tests/blas_lattice_cases.py)
 
 
 @pytest.mark.parametrize("name", BLAS)

@@ -629,7 +629,7 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
                        const unsigned* __restrict__ ids32, ArrSet set0, ArrSet set1,
                        TmpNode* __restrict__ subnodes, unsigned short* __restrict__ submap,
                        unsigned* __restrict__ sub_interior, unsigned* __restrict__ final_ids, unsigned* __restrict__ err,
-                       unsigned* __restrict__ dbg_cycles, const unsigned* __restrict__ order
+                       unsigned* __restrict__ deg_at, unsigned* __restrict__ dbg_cycles, const unsigned* __restrict__ order
 #ifdef VD_TUNING
                        , unsigned long long* __restrict__ cls_prof
 #endif
@@ -1206,7 +1206,10 @@ void blas_small_kernel(const SmallRoot* __restrict__ roots, const unsigned* __re
     __threadfence_block();   // node records written by all lanes are re-read below, by this workgroup only (an agent-scope
                              // fence would write back the whole L2 of the XCD, once per subtree)
     __syncthreads();
-    if (Q.bad) { if (tid == 0) atomicOr(err, Q.bad == 2u ? ERR_INTERNAL : ERR_DEGENERATE); return; }
+    if (Q.bad) {
+        if (tid == 0) { if (Q.bad != 2u) atomicMax(deg_at, ~base); atomicOr(err, Q.bad == 2u ? ERR_INTERNAL : ERR_DEGENERATE); }
+        return;
+    }
     const unsigned pool = Q.pool;
     const unsigned n_interior = pool / 2u;
 
@@ -1275,6 +1278,8 @@ struct LevelCtl {                     // device-side counters
     unsigned n_seg, n_seg_next, n_items, n_top, n_small, err, n_mid, arrived;   // arrived: workgroups of a_boundary_kernel that have emitted their children
     unsigned max_count, max_count_next;       // largest segment of this / the next level (the host picks the round kernels by it)
     unsigned active, active_next;             // triangles in the segments of this / the next level
+    unsigned deg_at;                          // with ERR_DEGENERATE: ~(the first batch position of a segment or subtree holding a node
+                                              // that no candidate splits), the largest seen - so the smallest position; 0: none
 };
 
 // Item geometry: item -> (segment, first relative position, valid count).  Lane order inside an
@@ -1865,7 +1870,7 @@ __global__ __launch_bounds__(64) void a_eval_kernel(Seg* segs, LevelCtl* ctl, co
     }
     key = wave_min_u64(key);
     if (lane == 0) {
-        if (key == ~0ull) { atomicOr(&ctl->err, ERR_DEGENERATE); sg.best = 0; sg.Lst = 1; }
+        if (key == ~0ull) { atomicMax(&ctl->deg_at, ~sg.start); atomicOr(&ctl->err, ERR_DEGENERATE); sg.best = 0; sg.Lst = 1; }
         else { sg.best = (unsigned)key; sg.Lst = sg.ttot[sg.best] - sg.u_p[sg.best]; }
     }
 }
@@ -2320,7 +2325,7 @@ __global__ __launch_bounds__(kMidThreads, (VD_MID_WGS * kMidThreads / 64 + 3) / 
             }
             key = wave_min_u64(key);
             if (lane == 0u) {
-                if (key == ~0ull) { atomicOr(&ctl->err, ERR_DEGENERATE); L.best = 0; L.Lst = 1; }
+                if (key == ~0ull) { atomicMax(&ctl->deg_at, ~root.start); atomicOr(&ctl->err, ERR_DEGENERATE); L.best = 0; L.Lst = 1; }
                 else { L.best = (unsigned)key; L.Lst = L.ttot[L.best] - L.u_p[L.best]; }
             }
         }
@@ -2619,6 +2624,25 @@ int ctl_refusal(VdCtx* ctx, unsigned err, unsigned internal_bits, const char* in
     return VD_OK;
 }
 
+// A VD_ERR_DEGENERATE refusal names its mesh: the one that owns the batch position LevelCtl::deg_at holds (of several
+// degenerate meshes: the first in the batch among those found when the build stopped).
+int name_degenerate(const Build& B, const BuildMesh* hm, uint32_t* out_failed_mesh) {
+    VdCtx* ctx = B.ctx;
+    if (!B.h_ctl.deg_at) return VD_ERR_DEGENERATE;
+    const uint64_t at = ~B.h_ctl.deg_at;
+    uint64_t end = 0;
+    for (uint32_t m = 0; m < B.K; ++m) {
+        end += hm[m].n_tri;
+        if (at < end) {
+            if (out_failed_mesh) *out_failed_mesh = m;
+            if (B.K > 1u)     // (a build of one mesh keeps the text as it was)
+                snprintf(ctx->err, sizeof(ctx->err), "vd_bvh_build: every split candidate rejected (the reference builder crashes on this input): mesh %u of the build", m);
+            break;
+        }
+    }
+    return VD_ERR_DEGENERATE;
+}
+
 // The mesh table: every mesh's arrays and where its triangles and chunks start in the batch.  d_packed == nullptr: before
 // place_nodes, a packed mesh has no node array yet (nothing before phase C looks at it).
 void fill_mesh_table(MeshDesc* desc, const BuildMesh* hm, uint32_t K, VdBvhNode* d_packed) {
@@ -2830,7 +2854,7 @@ int phase_b(Build& B, PinnedTop* h, unsigned* ord_end) {
     if (n_small) {
         hipLaunchKernelGGL(b_order_kernel, dim3(1), dim3(1024), 0, st, P.small, &P.ctl->n_small, P.root_pair);   // root_pair is free until phase C
         hipLaunchKernelGGL(blas_small_kernel, dim3(n_small), dim3(64 * kSubWaves), sizeof(WaveLds) + sizeof(WaveQueues), st, P.small, &P.ctl->n_small, P.ids32,
-                           B.sets[0], B.sets[1], P.subnodes, P.submap, P.sub_interior, P.final_ids, &P.ctl->err, P.stack, P.root_pair
+                           B.sets[0], B.sets[1], P.subnodes, P.submap, P.sub_interior, P.final_ids, &P.ctl->err, &P.ctl->deg_at, P.stack, P.root_pair
 #ifdef VD_TUNING
                            , P.cls_prof
 #endif
@@ -2897,15 +2921,15 @@ int bvh_build_batch_impl(VdCtx* ctx, BuildMesh* hm, uint32_t K, VdBvhNode* d_pac
     vd_time_begin(ctx);
     if ((rc = precompute(B, hm, out_failed_mesh))) return rc;
     lap(stats.ms_precompute);
-    if ((rc = phase_a(B))) return rc;
+    if ((rc = phase_a(B))) return rc == VD_ERR_DEGENERATE ? name_degenerate(B, hm, out_failed_mesh) : rc;
     lap(stats.ms_phase_a);
-    if ((rc = mid_tier(B))) return rc;
+    if ((rc = mid_tier(B))) return rc == VD_ERR_DEGENERATE ? name_degenerate(B, hm, out_failed_mesh) : rc;
     lap(stats.ms_mid);
     B.n_small = B.h_ctl.n_small; B.n_top = B.h_ctl.n_top;
     stats.n_top_nodes = B.n_top; stats.n_small_roots = B.n_small; stats.n_mid_roots = B.h_ctl.n_mid;
     PinnedTop h;
     std::vector<unsigned> ord_end(K);
-    if ((rc = phase_b(B, &h, ord_end.data()))) return rc;
+    if ((rc = phase_b(B, &h, ord_end.data()))) return rc == VD_ERR_DEGENERATE ? name_degenerate(B, hm, out_failed_mesh) : rc;
     lap(stats.ms_phase_b);
     number_top(h.top, h.sub, K, h.ord, ord_end.data(), h.out, h.root_pair, hm);
     uint32_t failed = kNone;
