@@ -29,6 +29,7 @@
 #include "voidin_abi.h"
 #include "voidin_shadow.h"
 #include "voidin_gbuffer.h"
+#include "voidin_gbuffer_trace.h"
 
 namespace voidin {
 
@@ -813,6 +814,11 @@ class TraceScene {
         gpu_.check(vd_shadow_gbuffer_prepared_dev(gpu_.ctx(), accel_, &camera, &gb, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
         return i;
     }
+    // The G-buffer itself from primary rays over this prepared scene (voidin_gbuffer_trace.h): gbuffer_trace below.  `geometry`: the
+    // buffers the scene was prepared from, with MeshPool's normals / tex_coords (either may be null).
+    void gbuffer_trace(const VdGBufferGeometry& geometry, const VdCameraUniform& camera, const VdGBufferTarget& target) const {
+        gpu_.check(vd_gbuffer_trace_prepared_dev(gpu_.ctx(), accel_, &geometry, &camera, &target));
+    }
     // Opt-in (Gpu::set_option(VD_OPT_TRACE_TIGHT_TLAS, 1 or 2) before construction): the scene walks a private top level over
     // tight world boxes - same hits, distances within 1e-5 (bit-equal in every test), not the reference's visit order.
     // `info().tight_tlas` says whether it does (every instance must have inv_transform = transform^-1); `update()` rebuilds it
@@ -976,6 +982,26 @@ inline VdShadowGBufferInfo shadow_gbuffer(const Gpu& gpu, const VdTraceScene& d_
     VdShadowGBufferInfo i{};
     gpu.check(vd_shadow_gbuffer_dev(gpu.ctx(), &d_scene, &camera, &gb, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, &i));
     return i;
+}
+
+// The producer of those three images without a rasteriser (voidin_gbuffer_trace.h): the ray-traced equivalent of the raster pass, as
+// src/bin/bvh_trace.wgsl:223-248 does it.  gbuffer_rays: one ray through every pixel centre; gbuffer_resolve: width * height hit
+// records (pixel i = y * width + x) into depth = clip z / w of the hit point, word 0 = the octahedral normal (interpolated vertex
+// normals, or the triangle's facing the eye when geometry.normals is null), word 1 = pack2x16float of the interpolated uv, material =
+// the instance's low 8 bits; a miss is all zero.  Both only enqueue.  gbuffer_trace: rays -> vd_trace_dev -> resolve in one call.
+inline void gbuffer_rays(const Gpu& gpu, const VdCameraUniform& camera, uint32_t width, uint32_t height, VdRay* d_rays) {
+    gpu.check(vd_gbuffer_rays_dev(gpu.ctx(), &camera, width, height, d_rays));
+}
+inline void gbuffer_resolve(const Gpu& gpu, const VdCameraUniform& camera, const VdGBufferGeometry& geometry, const VdHit* d_hits, const VdGBufferTarget& target) {
+    gpu.check(vd_gbuffer_resolve_dev(gpu.ctx(), &camera, &geometry, d_hits, &target));
+}
+inline void gbuffer_trace(const Gpu& gpu, const VdTraceScene& d_scene, const float* d_normals, const float* d_tex_coords, const VdCameraUniform& camera,
+                          const VdGBufferTarget& target) {
+    gpu.check(vd_gbuffer_trace_dev(gpu.ctx(), &d_scene, d_normals, d_tex_coords, &camera, &target));
+}
+// The images a VdGBufferTarget was written into, as the consumers above take them.
+inline VdGBuffer gbuffer_of(const VdGBufferTarget& t) {
+    return VdGBuffer{t.depth, t.depth_pitch, t.normal_uv, t.normal_uv_pitch, t.material, t.material_pitch, t.width, t.height};
 }
 
 }  // namespace voidin

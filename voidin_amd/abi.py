@@ -172,6 +172,23 @@ GBUFFER_LIGHT_MATERIAL = 2  # VD_GBUFFER_LIGHT_MATERIAL
 assert C.sizeof(GBuffer) == 56 and C.sizeof(ShadowGBufferInfo) == 16
 
 
+class GBufferTarget(C.Structure):
+    """VdGBufferTarget (include/voidin_gbuffer_trace.h): VdGBuffer's layout with writable images."""
+    _fields_ = list(GBuffer._fields_)
+
+
+class GBufferGeometry(C.Structure):
+    """VdGBufferGeometry (include/voidin_gbuffer_trace.h): what the resolve step gathers from; normals / tex_coords may be null."""
+    _fields_ = [("instances", C.c_void_p), ("n_instances", C.c_uint32),
+                ("meshes", C.c_void_p), ("n_meshes", C.c_uint32),
+                ("vertices", C.c_void_p), ("n_vertices", C.c_uint32),
+                ("indices", C.c_void_p), ("n_indices", C.c_uint32),
+                ("normals", C.c_void_p), ("tex_coords", C.c_void_p)]
+
+
+assert C.sizeof(GBufferTarget) == 56 and C.sizeof(GBufferGeometry) == 80
+
+
 class BvhBatchItem(C.Structure):
     """VdBvhBatchItem (include/voidin_abi.h, "Batched BLAS build")."""
     _fields_ = [("verts_xyz", C.c_void_p), ("indices_inout", C.c_void_p), ("out_nodes", C.c_void_p),
@@ -331,6 +348,14 @@ GBUFFER_PROTOTYPES = {
     "vd_shadow_gbuffer_prepared_dev": (_I, [_P, _P, _P, C.POINTER(GBuffer), _P, _U, _U, _P, _P, C.POINTER(ShadowGBufferInfo)]),
 }
 
+# ... and every symbol include/voidin_gbuffer_trace.h declares: a fourth table.
+GBUFFER_TRACE_PROTOTYPES = {
+    "vd_gbuffer_rays_dev": (_I, [_P, _P, _U, _U, _P]),
+    "vd_gbuffer_resolve_dev": (_I, [_P, _P, C.POINTER(GBufferGeometry), _P, C.POINTER(GBufferTarget)]),
+    "vd_gbuffer_trace_dev": (_I, [_P, C.POINTER(TraceScene), _P, _P, _P, C.POINTER(GBufferTarget)]),
+    "vd_gbuffer_trace_prepared_dev": (_I, [_P, _P, C.POINTER(GBufferGeometry), _P, C.POINTER(GBufferTarget)]),
+}
+
 _lib = None
 
 
@@ -358,7 +383,7 @@ def load(path: str | None = None, strict: bool = True) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES, **GBUFFER_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES, **GBUFFER_PROTOTYPES, **GBUFFER_TRACE_PROTOTYPES}.items():
         if not strict and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol

@@ -75,6 +75,7 @@ struct VdCtx {
     void* blas_lbvh_state = nullptr; size_t blas_lbvh_state_bytes = 0;   // vd_bvh_build_lbvh*: triangle boxes, the index copy, the sort's work memory, the radix tree
     VdShadowArena shadow;                                         // vd_shadow_pass*: cell counts and offsets, then the rays and hit flags of one chunk (not `scratch`: the walk's arena)
     VdGBufferArena gbuffer;                                       // vd_gbuffer_points_dev / vd_shadow_gbuffer*: tile counts and offsets; points, normals, pixel ids, per-point words
+    VdShadowArena gbuffer_trace;                                  // vd_gbuffer_trace*: the rays and hit records of one image (gbuffer_trace.hip; the same self-freeing buffer)
     VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene

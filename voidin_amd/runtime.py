@@ -691,6 +691,43 @@ class Context:
                                                           abi.ptr(d_occluded), abi.ptr(d_in_range), C.byref(info)))
         return self._gbuffer_info(info)
 
+    @staticmethod
+    def gbuffer_target(d_depth, d_normal_uv, d_material, width, height, depth_pitch=None, normal_uv_pitch=None, material_pitch=None) -> "abi.GBufferTarget":
+        """VdGBufferTarget (include/voidin_gbuffer_trace.h) over three writable device images; a pitch left out is the packed one."""
+        return abi.GBufferTarget(abi.ptr(d_depth), 4 * width if depth_pitch is None else depth_pitch,
+                                 abi.ptr(d_normal_uv), 8 * width if normal_uv_pitch is None else normal_uv_pitch,
+                                 abi.ptr(d_material), width if material_pitch is None else material_pitch, width, height)
+
+    @staticmethod
+    def gbuffer_geometry(scene: "Context.DeviceScene", d_normals=None, d_tex_coords=None) -> "abi.GBufferGeometry":
+        """VdGBufferGeometry: the instances, meshes, vertices and indices of a DeviceScene (narrow or wide) with per-vertex normals
+        (3 floats) and uvs (2 floats) on the device, either of which may be None."""
+        s = scene.struct
+        return abi.GBufferGeometry(s.instances, s.n_instances, s.meshes, s.n_meshes, s.vertices, s.n_vertices, s.indices, s.n_indices,
+                                   abi.ptr(d_normals), abi.ptr(d_tex_coords))
+
+    def gbuffer_rays_dev(self, camera, width, height, d_rays):
+        """vd_gbuffer_rays_dev: one ray through every pixel centre (bvh_trace.wgsl:227-231), the whole half-line.  Enqueues only."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_gbuffer_rays_dev(self.h, cam.ctypes.data, width, height, abi.ptr(d_rays)))
+
+    def gbuffer_resolve_dev(self, camera, geometry: "abi.GBufferGeometry", d_hits, target: "abi.GBufferTarget"):
+        """vd_gbuffer_resolve_dev: width * height hit records into depth, normal + uv and material.  Enqueues only."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_gbuffer_resolve_dev(self.h, cam.ctypes.data, C.byref(geometry), abi.ptr(d_hits), C.byref(target)))
+
+    def gbuffer_trace_dev(self, scene: "Context.DeviceScene", camera, target: "abi.GBufferTarget", d_normals=None, d_tex_coords=None):
+        """vd_gbuffer_trace_dev: rays -> trace_dev -> resolve over a narrow scene, the rays and records in the context's arena."""
+        if scene.wide:
+            raise TypeError("a scene whose top level is TLAS_NODE_WIDE goes through trace_prepare and gbuffer_trace_prepared_dev")
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_gbuffer_trace_dev(self.h, C.byref(scene.struct), abi.ptr(d_normals), abi.ptr(d_tex_coords), cam.ctypes.data, C.byref(target)))
+
+    def gbuffer_trace_prepared_dev(self, accel: "Context.TraceAccel", geometry: "abi.GBufferGeometry", camera, target: "abi.GBufferTarget"):
+        """vd_gbuffer_trace_prepared_dev: the same over a prepared scene - narrow, wide or with a private top level."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_gbuffer_trace_prepared_dev(self.h, accel.h, C.byref(geometry), cam.ctypes.data, C.byref(target)))
+
     def primary_rays_dev(self, camera, width, height, d_rays):
         """One ray per pixel from camera.clip_to_world (src/bin/bvh_cpu.rs:71-83); d_rays: width*height rays."""
         cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
