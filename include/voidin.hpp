@@ -30,6 +30,7 @@
 #include "voidin_shadow.h"
 #include "voidin_gbuffer.h"
 #include "voidin_gbuffer_trace.h"
+#include "voidin_lighting.h"
 
 namespace voidin {
 
@@ -819,6 +820,13 @@ class TraceScene {
     void gbuffer_trace(const VdGBufferGeometry& geometry, const VdCameraUniform& camera, const VdGBufferTarget& target) const {
         gpu_.check(vd_gbuffer_trace_prepared_dev(gpu_.ctx(), accel_, &geometry, &camera, &target));
     }
+    // The pass and the light loop in one call over this prepared scene (voidin_lighting.h): shade_gbuffer below.
+    VdShadowGBufferInfo shade_gbuffer(const VdCameraUniform& camera, const VdGBuffer& gb, const VdLight* d_lights, uint32_t n_lights,
+                                      const VdFlatMaterial* d_materials, const VdColorTarget& target, uint32_t max_chunk_rays = 0) const {
+        VdShadowGBufferInfo i{};
+        gpu_.check(vd_shade_gbuffer_prepared_dev(gpu_.ctx(), accel_, &camera, &gb, d_lights, n_lights, max_chunk_rays, d_materials, &target, &i));
+        return i;
+    }
     // Opt-in (Gpu::set_option(VD_OPT_TRACE_TIGHT_TLAS, 1 or 2) before construction): the scene walks a private top level over
     // tight world boxes - same hits, distances within 1e-5 (bit-equal in every test), not the reference's visit order.
     // `info().tight_tlas` says whether it does (every instance must have inv_transform = transform^-1); `update()` rebuilds it
@@ -1002,6 +1010,22 @@ inline void gbuffer_trace(const Gpu& gpu, const VdTraceScene& d_scene, const flo
 // The images a VdGBufferTarget was written into, as the consumers above take them.
 inline VdGBuffer gbuffer_of(const VdGBufferTarget& t) {
     return VdGBuffer{t.depth, t.depth_pitch, t.normal_uv, t.normal_uv_pitch, t.material, t.material_pitch, t.width, t.height};
+}
+
+// What the shader does with those bits (voidin_lighting.h; raytraced_shadows.wgsl:79-117): the base colour of the pixel's material, then
+// (diff + spec) * occlusion * atten added for every light whose in-range bit is set, in ascending order, and the clamp - four floats a
+// pixel, one texel for the shader to read in place of its light loop.  d_materials: VD_LIGHTING_MATERIALS rows, one per value of the
+// material image.  lighting: the step alone over the W words per pixel shadow_gbuffer wrote; it only enqueues (n_lights == 0: the base
+// colours, the arrays may be null).  shade_gbuffer: shadow_gbuffer and lighting in one call, the bits in the context's arena; blocks.
+inline void lighting(const Gpu& gpu, const VdCameraUniform& camera, const VdGBuffer& gb, const VdLight* d_lights, uint32_t n_lights, const uint32_t* d_occluded,
+                     const uint32_t* d_in_range, const VdFlatMaterial* d_materials, const VdColorTarget& target) {
+    gpu.check(vd_lighting_dev(gpu.ctx(), &camera, &gb, d_lights, n_lights, d_occluded, d_in_range, d_materials, &target));
+}
+inline VdShadowGBufferInfo shade_gbuffer(const Gpu& gpu, const VdTraceScene& d_scene, const VdCameraUniform& camera, const VdGBuffer& gb, const VdLight* d_lights,
+                                         uint32_t n_lights, const VdFlatMaterial* d_materials, const VdColorTarget& target, uint32_t max_chunk_rays = 0) {
+    VdShadowGBufferInfo i{};
+    gpu.check(vd_shade_gbuffer_dev(gpu.ctx(), &d_scene, &camera, &gb, d_lights, n_lights, max_chunk_rays, d_materials, &target, &i));
+    return i;
 }
 
 }  // namespace voidin

@@ -189,6 +189,18 @@ class GBufferGeometry(C.Structure):
 assert C.sizeof(GBufferTarget) == 56 and C.sizeof(GBufferGeometry) == 80
 
 
+FLAT_MATERIAL = np.dtype([("albedo", "<f4", (3,)), ("specular", "<f4"), ("emissive", "<f4", (3,)), ("_pad", "<u4")])   # VdFlatMaterial
+LIGHTING_MATERIALS = 256  # VD_LIGHTING_MATERIALS: rows of the material table, one per value of the R8Uint material image
+
+
+class ColorTarget(C.Structure):
+    """VdColorTarget (include/voidin_lighting.h): the lit image, four floats a pixel, as a device pointer with a pitch in bytes."""
+    _fields_ = [("rgba", C.c_void_p), ("pitch", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+assert FLAT_MATERIAL.itemsize == 32 and C.sizeof(ColorTarget) == 24
+
+
 class BvhBatchItem(C.Structure):
     """VdBvhBatchItem (include/voidin_abi.h, "Batched BLAS build")."""
     _fields_ = [("verts_xyz", C.c_void_p), ("indices_inout", C.c_void_p), ("out_nodes", C.c_void_p),
@@ -356,6 +368,13 @@ GBUFFER_TRACE_PROTOTYPES = {
     "vd_gbuffer_trace_prepared_dev": (_I, [_P, _P, C.POINTER(GBufferGeometry), _P, C.POINTER(GBufferTarget)]),
 }
 
+# ... and every symbol include/voidin_lighting.h declares: a fifth table.
+LIGHTING_PROTOTYPES = {
+    "vd_lighting_dev": (_I, [_P, _P, C.POINTER(GBuffer), _P, _U, _P, _P, _P, C.POINTER(ColorTarget)]),
+    "vd_shade_gbuffer_dev": (_I, [_P, C.POINTER(TraceScene), _P, C.POINTER(GBuffer), _P, _U, _U, _P, C.POINTER(ColorTarget), C.POINTER(ShadowGBufferInfo)]),
+    "vd_shade_gbuffer_prepared_dev": (_I, [_P, _P, _P, C.POINTER(GBuffer), _P, _U, _U, _P, C.POINTER(ColorTarget), C.POINTER(ShadowGBufferInfo)]),
+}
+
 _lib = None
 
 
@@ -383,7 +402,7 @@ def load(path: str | None = None, strict: bool = True) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES, **GBUFFER_PROTOTYPES, **GBUFFER_TRACE_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **SHADOW_PROTOTYPES, **GBUFFER_PROTOTYPES, **GBUFFER_TRACE_PROTOTYPES, **LIGHTING_PROTOTYPES}.items():
         if not strict and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol

@@ -76,6 +76,7 @@ struct VdCtx {
     VdShadowArena shadow;                                         // vd_shadow_pass*: cell counts and offsets, then the rays and hit flags of one chunk (not `scratch`: the walk's arena)
     VdGBufferArena gbuffer;                                       // vd_gbuffer_points_dev / vd_shadow_gbuffer*: tile counts and offsets; points, normals, pixel ids, per-point words
     VdShadowArena gbuffer_trace;                                  // vd_gbuffer_trace*: the rays and hit records of one image (gbuffer_trace.hip; the same self-freeing buffer)
+    VdShadowArena lighting;                                       // vd_shade_gbuffer*: the two per-pixel bit arrays between the pass and the lighting step (lighting.hip)
     VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene

@@ -728,6 +728,41 @@ class Context:
         cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
         self._chk(self.lib.vd_gbuffer_trace_prepared_dev(self.h, accel.h, C.byref(geometry), cam.ctypes.data, C.byref(target)))
 
+    @staticmethod
+    def color_target(d_rgba, width, height, pitch=None) -> "abi.ColorTarget":
+        """VdColorTarget (include/voidin_lighting.h) over a writable device image of four floats a pixel; a pitch left out is the
+        packed one."""
+        return abi.ColorTarget(abi.ptr(d_rgba), 16 * width if pitch is None else pitch, width, height)
+
+    def lighting_dev(self, camera, gb: "abi.GBuffer", d_lights, n_lights, d_occluded, d_in_range, d_materials, target: "abi.ColorTarget"):
+        """vd_lighting_dev: the shader's light loop summed per pixel over the set in-range bits, in ascending order, from the W words
+        per pixel vd_shadow_gbuffer_dev writes; d_materials: abi.LIGHTING_MATERIALS rows of abi.FLAT_MATERIAL.  n_lights == 0: the
+        base colours (the light and bit arrays may be None).  Enqueues only."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        self._chk(self.lib.vd_lighting_dev(self.h, cam.ctypes.data, C.byref(gb), abi.ptr(d_lights), n_lights, abi.ptr(d_occluded), abi.ptr(d_in_range),
+                                           abi.ptr(d_materials), C.byref(target)))
+
+    def shade_gbuffer_dev(self, scene: "Context.DeviceScene", camera, gb: "abi.GBuffer", d_lights, n_lights, d_materials, target: "abi.ColorTarget",
+                          max_chunk_rays=0) -> dict:
+        """vd_shade_gbuffer_dev: shadow_gbuffer_dev followed by lighting_dev, the bits in the context's arena.  Blocks.
+        -> {"n_points", "n_rays", "n_chunks", "words_per_point"}, as the pass reports."""
+        if scene.wide:
+            raise TypeError("a scene whose top level is TLAS_NODE_WIDE goes through trace_prepare and shade_gbuffer_prepared_dev")
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        info = abi.ShadowGBufferInfo()
+        self._chk(self.lib.vd_shade_gbuffer_dev(self.h, C.byref(scene.struct), cam.ctypes.data, C.byref(gb), abi.ptr(d_lights), n_lights, max_chunk_rays,
+                                                abi.ptr(d_materials), C.byref(target), C.byref(info)))
+        return self._gbuffer_info(info)
+
+    def shade_gbuffer_prepared_dev(self, accel: "Context.TraceAccel", camera, gb: "abi.GBuffer", d_lights, n_lights, d_materials, target: "abi.ColorTarget",
+                                   max_chunk_rays=0) -> dict:
+        """vd_shade_gbuffer_prepared_dev: the same over a prepared scene - narrow, wide or with a private top level."""
+        cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
+        info = abi.ShadowGBufferInfo()
+        self._chk(self.lib.vd_shade_gbuffer_prepared_dev(self.h, accel.h, cam.ctypes.data, C.byref(gb), abi.ptr(d_lights), n_lights, max_chunk_rays,
+                                                         abi.ptr(d_materials), C.byref(target), C.byref(info)))
+        return self._gbuffer_info(info)
+
     def primary_rays_dev(self, camera, width, height, d_rays):
         """One ray per pixel from camera.clip_to_world (src/bin/bvh_cpu.rs:71-83); d_rays: width*height rays."""
         cam = np.ascontiguousarray(camera, dtype=abi.CAMERA).reshape(1)
