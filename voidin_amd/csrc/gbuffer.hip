@@ -15,7 +15,10 @@
 //   gbuffer_scatter_kernel  the material test again; the W words of every pixel: its point's, or zero.  The 64 W words of one k
 //                           are one contiguous run, stored 64 words at a time (lane j of a step owns word j of the run and
 //                           fetches its pixel's rank from the lane that holds it), so every store is a full 256-byte line.
-#include "vd_common.hpp"
+//
+// What a pixel IS - receiver or not, its world position, its normal - is stated once, in vd_shade.hpp, for this file and for the step
+// that shades the pixels afterwards; so are the view of the three images, their checks and the scan.
+#include "vd_shade.hpp"
 #include "../../include/voidin_gbuffer.h"
 
 namespace {
@@ -23,20 +26,6 @@ namespace {
 constexpr unsigned kPerLane = 8u;                       // pixels per lane
 constexpr unsigned kTilePixels = 64u * kPerLane;        // pixels per tile = per wave
 constexpr unsigned kTileWaves = 4u;                     // waves (tiles) per workgroup
-constexpr unsigned kScanThreads = 1024u, kScanItems = 4u;
-constexpr unsigned kMaxPixels = 1u << 30;
-
-// The images as the kernels take them: the pitches in bytes (size_t: a row offset may pass 4 GiB), the sizes.
-struct Images {
-    const float* depth; const uint32_t* normal_uv; const uint8_t* material;
-    size_t depth_pitch, normal_uv_pitch, material_pitch;
-    unsigned width, n_pixels;
-};
-struct ClipToWorld { float m[16]; };                    // column-major, as VdCameraUniform holds it
-
-__device__ __forceinline__ bool gbuffer_receiver(unsigned material) {
-    return material != VD_GBUFFER_NO_MATERIAL && material != VD_GBUFFER_LIGHT_MATERIAL;      // raytraced_shadows.wgsl:80
-}
 
 // The tile skeleton: this wave's tile and which of its pixels receive.
 struct GBufferTile {
@@ -55,11 +44,11 @@ struct GBufferTile {
         for (unsigned k = 0; k < kPerLane; ++k) {
             const unsigned i = pixel(k);
             y[k] = i / im.width; x[k] = i - y[k] * im.width;
-            mat[k] = i < im.n_pixels ? im.material[(size_t)y[k] * im.material_pitch + x[k]] : VD_GBUFFER_NO_MATERIAL;
+            mat[k] = i < im.n_pixels ? *im.material_at(x[k], y[k]) : VD_GBUFFER_NO_MATERIAL;
         }
         total = 0u;
 #pragma unroll
-        for (unsigned k = 0; k < kPerLane; ++k) { m[k] = __ballot(gbuffer_receiver(mat[k])); total += (unsigned)__popcll(m[k]); }
+        for (unsigned k = 0; k < kPerLane; ++k) { m[k] = __ballot(receives_light(mat[k])); total += (unsigned)__popcll(m[k]); }
         return true;
     }
     __device__ __forceinline__ unsigned pixel(unsigned k) const { return tile * kTilePixels + k * 64u + lane; }
@@ -72,42 +61,15 @@ __global__ __launch_bounds__(64 * kTileWaves) void gbuffer_count_kernel(Images i
     if (t.lane == 0u) count[t.tile] = t.total;
 }
 
-// offsets[i] = count[0] + ... + count[i - 1] for i in [0, n], *total = offsets[n]: ONE workgroup, kScanThreads * kScanItems counts
-// per round.
+// offsets[i] = count[0] + ... + count[i - 1] for i in [0, n], *total = offsets[n]: ONE workgroup (vd_block_scan).
 __global__ __launch_bounds__(kScanThreads) void gbuffer_scan_kernel(const unsigned* __restrict__ count, unsigned n, unsigned* __restrict__ offsets,
                                                                       unsigned* __restrict__ total_out) {
-    __shared__ unsigned wave_sum[kScanThreads / 64u];
-    const unsigned lane = vd_lane(), wave = threadIdx.x >> 6;
-    unsigned carry = 0u;
-    for (unsigned base = 0; base < n; base += kScanThreads * kScanItems) {
-        const unsigned i0 = base + threadIdx.x * kScanItems;
-        unsigned v[kScanItems], mine = 0u;
-#pragma unroll
-        for (unsigned q = 0; q < kScanItems; ++q) { v[q] = i0 + q < n ? count[i0 + q] : 0u; mine += v[q]; }
-        unsigned incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned o = __shfl_up(incl, off);
-            if (lane >= (unsigned)off) incl += o;
-        }
-        if (lane == 63u) wave_sum[wave] = incl;
-        __syncthreads();
-        unsigned before = carry, total = 0u;
-#pragma unroll
-        for (unsigned w = 0; w < kScanThreads / 64u; ++w) { const unsigned s = wave_sum[w]; before += w < wave ? s : 0u; total += s; }
-        unsigned run = before + incl - mine;
-#pragma unroll
-        for (unsigned q = 0; q < kScanItems; ++q) { if (i0 + q < n) offsets[i0 + q] = run; run += v[q]; }
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u) { offsets[n] = carry; *total_out = carry; }
+    const unsigned total = vd_block_scan(count, n, offsets);
+    if (threadIdx.x == 0u) { offsets[n] = total; *total_out = total; }
 }
 
-struct F3 { float x, y, z; };
-
-__global__ __launch_bounds__(64 * kTileWaves) void gbuffer_write_kernel(Images im, ClipToWorld c2w, unsigned n_tiles, const unsigned* __restrict__ offsets,
-                                                                          unsigned cap, F3* __restrict__ positions, F3* __restrict__ normals,
+__global__ __launch_bounds__(64 * kTileWaves) void gbuffer_write_kernel(Images im, Mat4 c2w, unsigned n_tiles, const unsigned* __restrict__ offsets,
+                                                                          unsigned cap, V3* __restrict__ positions, V3* __restrict__ normals,
                                                                           unsigned* __restrict__ pixels) {
     GBufferTile t;
     if (!t.load(im, n_tiles)) return;
@@ -116,32 +78,16 @@ __global__ __launch_bounds__(64 * kTileWaves) void gbuffer_write_kernel(Images i
 #pragma unroll
     for (unsigned k = 0; k < kPerLane; ++k) {           // all loads of the tile in flight before the first is used
         const bool r = t.receives(k);
-        depth[k] = r ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(im.depth) + (size_t)t.y[k] * im.depth_pitch + 4u * (size_t)t.x[k]) : 0.0f;
-        n32[k] = r ? *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(im.normal_uv) + (size_t)t.y[k] * im.normal_uv_pitch + 8u * (size_t)t.x[k]) : 0u;
+        depth[k] = r ? *im.depth_at(t.x[k], t.y[k]) : 0.0f;
+        n32[k] = r ? *im.normal_uv_at(t.x[k], t.y[k]) : 0u;
     }
     const float fw = (float)im.width, fh = (float)(im.n_pixels / im.width);
-    const float* M = c2w.m;
     unsigned at = offsets[t.tile];
 #pragma unroll
     for (unsigned k = 0; k < kPerLane; ++k) {
         if (t.receives(k)) {
-            // uv.wgsl:1-3, 13-22
-            const float ux = ((float)t.x[k] + 0.5f) / fw, uy = ((float)t.y[k] + 0.5f) / fh;
-            const float nx = ux * 2.0f - 1.0f, ny = (1.0f - uy) * 2.0f - 1.0f, nz = depth[k];
-            float w4[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w4[r] = ((M[r] * nx + M[4 + r] * ny) + M[8 + r] * nz) + M[12 + r];
-            F3 p; p.x = w4[0] / w4[3]; p.y = w4[1] / w4[3]; p.z = w4[2] / w4[3];
-            // encoding.wgsl:17-28
-            float vx = (float)(n32[k] & 0xffffu) / 65535.0f, vy = (float)((n32[k] >> 16) & 0xffffu) / 65535.0f;
-            vx = vx * 2.0f - 1.0f; vy = vy * 2.0f - 1.0f;
-            float ax = vx, ay = vy;
-            const float az = (1.0f - fabsf(vx)) - fabsf(vy);
-            const float tt = (-az > 0.0f) ? -az : 0.0f;
-            ax += (ax > 0.0f) ? -tt : tt;
-            ay += (ay > 0.0f) ? -tt : tt;
-            const float len = sqrtf((ax * ax + ay * ay) + az * az);
-            F3 n; n.x = ax / len; n.y = ay / len; n.z = az / len;
+            const V3 p = position_from_depth(c2w, t.x[k], t.y[k], fw, fh, depth[k]);
+            const V3 n = decode_octahedral(n32[k]);
             const unsigned i = at + vd_mbcnt(t.m[k]);
             if (i < cap) { positions[i] = p; normals[i] = n; pixels[i] = t.pixel(k); }      // (cap: images that change under the call cannot make it write outside the arrays)
         }
@@ -180,38 +126,14 @@ __global__ __launch_bounds__(64 * kTileWaves) void gbuffer_scatter_kernel(Images
     }
 }
 
-int gbuffer_fail(VdCtx* ctx, const char* name, const char* what) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
-    return VD_ERR_INVALID_ARG;
-}
-
-// The checks of the images that every entry point shares; gb is not null and neither size is zero.
-int gbuffer_check(VdCtx* ctx, const char* name, const VdGBuffer* gb) {
-    if (!gb->depth || !gb->normal_uv || !gb->material) return gbuffer_fail(ctx, name, "null pointer");
-    if ((uint64_t)gb->width * gb->height > kMaxPixels) return gbuffer_fail(ctx, name, "width * height exceeds 2^30");
-    if (gb->depth_pitch % 4u || (uint64_t)gb->depth_pitch < 4ull * gb->width) return gbuffer_fail(ctx, name, "depth_pitch is below 4 * width or not a multiple of 4");
-    if (gb->normal_uv_pitch % 8u || (uint64_t)gb->normal_uv_pitch < 8ull * gb->width)
-        return gbuffer_fail(ctx, name, "normal_uv_pitch is below 8 * width or not a multiple of 8");
-    if (gb->material_pitch < gb->width) return gbuffer_fail(ctx, name, "material_pitch is below width");
-    return VD_OK;
-}
-
-Images gbuffer_images(const VdGBuffer* gb) {
-    return Images{gb->depth, gb->normal_uv, gb->material, gb->depth_pitch, gb->normal_uv_pitch, gb->material_pitch, gb->width, gb->width * gb->height};
-}
-
-// The tile tables of an image in ctx->gbuffer.tables: counts, offsets (n_tiles + 1), and one word for a count nobody else takes.
+// The tile tables of an image in ctx->gbuffer_tables: counts, offsets (n_tiles + 1), and one word for a count nobody else takes.
 struct Tables { unsigned n_tiles, blocks; unsigned* count; unsigned* offsets; unsigned* n_points; };
 int gbuffer_tables(VdCtx* ctx, const Images& im, Tables* t) {
     t->n_tiles = (im.n_pixels + kTilePixels - 1u) / kTilePixels;
     t->blocks = (t->n_tiles + kTileWaves - 1u) / kTileWaves;
-    Arena a{nullptr, 0};
-    a.take<unsigned>(t->n_tiles); a.take<unsigned>((size_t)t->n_tiles + 1u); a.take<unsigned>(1);
-    const int rc = vd_ensure(ctx, &ctx->gbuffer.tables, &ctx->gbuffer.tables_bytes, a.off);
-    if (rc) return rc;
-    a = Arena{static_cast<char*>(ctx->gbuffer.tables), 0};
-    t->count = a.take<unsigned>(t->n_tiles); t->offsets = a.take<unsigned>((size_t)t->n_tiles + 1u); t->n_points = a.take<unsigned>(1);
-    return VD_OK;
+    return vd_carve(ctx, &ctx->gbuffer_tables, [&](Arena& a) {
+        t->count = a.take<unsigned>(t->n_tiles); t->offsets = a.take<unsigned>((size_t)t->n_tiles + 1u); t->n_points = a.take<unsigned>(1);
+    });
 }
 
 // count -> scan: the offsets of the tiles, the total into *d_n_points.  Enqueues only.
@@ -224,10 +146,10 @@ int gbuffer_count(VdCtx* ctx, const Images& im, const Tables& t, unsigned* d_n_p
 
 // cap: the entries the three arrays take
 int gbuffer_write(VdCtx* ctx, const Images& im, const VdCameraUniform* camera, const Tables& t, unsigned cap, float* d_pos, float* d_nor, uint32_t* d_pix) {
-    ClipToWorld c2w;
+    Mat4 c2w;
     memcpy(c2w.m, camera->clip_to_world, sizeof(c2w.m));
-    hipLaunchKernelGGL(gbuffer_write_kernel, dim3(t.blocks), dim3(64 * kTileWaves), 0, ctx->stream, im, c2w, t.n_tiles, t.offsets, cap, reinterpret_cast<F3*>(d_pos),
-                       reinterpret_cast<F3*>(d_nor), d_pix);
+    hipLaunchKernelGGL(gbuffer_write_kernel, dim3(t.blocks), dim3(64 * kTileWaves), 0, ctx->stream, im, c2w, t.n_tiles, t.offsets, cap, reinterpret_cast<V3*>(d_pos),
+                       reinterpret_cast<V3*>(d_nor), d_pix);
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
 }
@@ -246,19 +168,19 @@ int shadow_gbuffer(VdCtx* ctx, const char* name, const VdTraceScene* scene, cons
                    const VdLight* d_lights, uint32_t n_lights, uint32_t max_chunk_rays, uint32_t* d_occluded, uint32_t* d_in_range, VdShadowGBufferInfo* out_info) {
     if (out_info) memset(out_info, 0, sizeof(*out_info));
     if (n_lights == 0) return VD_OK;
-    if (!gb) return gbuffer_fail(ctx, name, "null pointer");
+    if (!gb) return vd_fail_arg(ctx, name, "null pointer");
     if (gb->width == 0 || gb->height == 0) return VD_OK;
-    if (!camera || !d_lights || !d_occluded) return gbuffer_fail(ctx, name, "null pointer");
-    int rc = gbuffer_check(ctx, name, gb);
+    if (!camera || !d_lights || !d_occluded) return vd_fail_arg(ctx, name, "null pointer");
+    int rc = vd_check_images(ctx, name, gb);
     if (rc) return rc;
-    if (n_lights > VD_SHADOW_MAX_LIGHTS) return gbuffer_fail(ctx, name, "more than VD_SHADOW_MAX_LIGHTS lights");
-    if ((uint64_t)gb->width * gb->height * n_lights > 0xf0000000ull) return gbuffer_fail(ctx, name, "width * height * n_lights exceeds 0xf0000000");
+    if (n_lights > VD_SHADOW_MAX_LIGHTS) return vd_fail_arg(ctx, name, "more than VD_SHADOW_MAX_LIGHTS lights");
+    if ((uint64_t)gb->width * gb->height * n_lights > kMaxPairs) return vd_fail_arg(ctx, name, "width * height * n_lights exceeds 0xf0000000");
     // what the walk refuses it refuses now, before anything is launched (the pass itself would not look at the scene of a call
     // without receivers): a call without rays checks the scene and does nothing else
     rc = scene ? vd_trace_any_dev(ctx, scene, nullptr, 0u, nullptr) : vd_trace_any_prepared_dev(ctx, accel, nullptr, 0u, nullptr);
     if (rc) return rc;
 
-    const Images im = gbuffer_images(gb);
+    const Images im = vd_images<const char>(gb);
     const unsigned words = (n_lights + 31u) / 32u;
     Tables t;
     if ((rc = gbuffer_tables(ctx, im, &t))) return rc;
@@ -269,15 +191,12 @@ int shadow_gbuffer(VdCtx* ctx, const char* name, const VdTraceScene* scene, cons
     float* d_pos = nullptr; float* d_nor = nullptr; uint32_t* d_pix = nullptr; unsigned* d_pocc = nullptr; unsigned* d_pinr = nullptr;
     VdShadowPassInfo pass = {};
     if (n_points) {
-        Arena a{nullptr, 0};
-        for (int sized = 0; sized < 2; ++sized) {
+        rc = vd_carve(ctx, &ctx->gbuffer_points, [&](Arena& a) {
             d_pos = a.take<float>(3u * (size_t)n_points); d_nor = a.take<float>(3u * (size_t)n_points); d_pix = a.take<uint32_t>(n_points);
             d_pocc = a.take<unsigned>((size_t)n_points * words);
             d_pinr = d_in_range ? a.take<unsigned>((size_t)n_points * words) : nullptr;
-            if (sized) break;
-            if ((rc = vd_ensure(ctx, &ctx->gbuffer.points, &ctx->gbuffer.points_bytes, a.off))) return rc;
-            a = Arena{static_cast<char*>(ctx->gbuffer.points), 0};
-        }
+        });
+        if (rc) return rc;
         if ((rc = gbuffer_write(ctx, im, camera, t, n_points, d_pos, d_nor, d_pix))) return rc;
         rc = scene ? vd_shadow_pass_dev(ctx, scene, d_pos, d_nor, n_points, d_lights, n_lights, max_chunk_rays, d_pocc, d_pinr, &pass)
                    : vd_shadow_pass_prepared_dev(ctx, accel, d_pos, d_nor, n_points, d_lights, n_lights, max_chunk_rays, d_pocc, d_pinr, &pass);
@@ -300,12 +219,12 @@ int vd_gbuffer_points_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdGBu
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
     const char* name = "vd_gbuffer_points";
-    if (!gb) return gbuffer_fail(ctx, name, "null pointer");
+    if (!gb) return vd_fail_arg(ctx, name, "null pointer");
     if (gb->width == 0 || gb->height == 0) { if (out_n_points) *out_n_points = 0; return VD_OK; }
-    if (!camera || !d_positions || !d_normals || !d_pixels || !d_n_points) return gbuffer_fail(ctx, name, "null pointer");
-    int rc = gbuffer_check(ctx, name, gb);
+    if (!camera || !d_positions || !d_normals || !d_pixels || !d_n_points) return vd_fail_arg(ctx, name, "null pointer");
+    int rc = vd_check_images(ctx, name, gb);
     if (rc) return rc;
-    const Images im = gbuffer_images(gb);
+    const Images im = vd_images<const char>(gb);
     Tables t;
     if ((rc = gbuffer_tables(ctx, im, &t))) return rc;
     if ((rc = gbuffer_count(ctx, im, t, d_n_points))) return rc;
@@ -317,7 +236,7 @@ int vd_shadow_gbuffer_dev(VdCtx* ctx, const VdTraceScene* d_scene, const VdCamer
                           uint32_t n_lights, uint32_t max_chunk_rays, uint32_t* d_occluded, uint32_t* d_in_range, VdShadowGBufferInfo* out_info) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!d_scene) return gbuffer_fail(ctx, "vd_shadow_gbuffer", "null scene");
+    if (!d_scene) return vd_fail_arg(ctx, "vd_shadow_gbuffer", "null scene");
     return shadow_gbuffer(ctx, "vd_shadow_gbuffer", d_scene, nullptr, camera, gb, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, out_info);
 }
 
@@ -325,7 +244,7 @@ int vd_shadow_gbuffer_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const 
                                    uint32_t n_lights, uint32_t max_chunk_rays, uint32_t* d_occluded, uint32_t* d_in_range, VdShadowGBufferInfo* out_info) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!accel) return gbuffer_fail(ctx, "vd_shadow_gbuffer_prepared", "null accel");
+    if (!accel) return vd_fail_arg(ctx, "vd_shadow_gbuffer_prepared", "null accel");
     return shadow_gbuffer(ctx, "vd_shadow_gbuffer_prepared", nullptr, accel, camera, gb, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range, out_info);
 }
 

@@ -14,19 +14,16 @@
 //                           attributes), and a pixel that is a miss leaves the chain at the level that says so - its lanes issue
 //                           nothing further.
 // No atomics, no LDS, no scratch.
-#include "vd_common.hpp"
+//
+// The pixel centre in NDC, the octahedral encoder (beside the decoder that reads its codes back), the view of the three images and
+// their checks are vd_shade.hpp's: the one copy that gbuffer.hip reads the images with.
+#include "vd_shade.hpp"
 #include "../../include/voidin_gbuffer_trace.h"
 
 namespace {
 
 constexpr unsigned kBlock = 256u;
-constexpr unsigned kMaxPixels = 1u << 30;
 
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross3(V3 a, V3 b) { return V3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
-__device__ __forceinline__ V3 over(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
 // rows 0..2 of M * (p, w), M column-major: ((c0 * x + c1 * y) + c2 * z) + c3 * w
 __device__ __forceinline__ V3 mul43(const float* M, V3 p, float w) {
     return V3{((M[0] * p.x + M[4] * p.y) + M[8] * p.z) + M[12] * w, ((M[1] * p.x + M[5] * p.y) + M[9] * p.z) + M[13] * w,
@@ -36,13 +33,12 @@ __device__ __forceinline__ float mul_row(const float* M, int r, float x, float y
     return ((M[r] * x + M[4 + r] * y) + M[8 + r] * z) + M[12 + r] * w;
 }
 
-struct Mat4 { float m[16]; };                           // column-major, as VdCameraUniform holds it
 struct Camera { Mat4 clip_to_world, view, projection; };
 
 // The ray of pixel (x, y): the header's definition.
 __device__ __forceinline__ void pixel_ray(const Mat4& c2w, unsigned x, unsigned y, float fw, float fh, V3& eye, V3& dir) {
-    const float ux = ((float)x + 0.5f) / fw, uy = ((float)y + 0.5f) / fh;
-    const float nx = ux * 2.0f - 1.0f, ny = (1.0f - uy) * 2.0f - 1.0f;
+    float nx, ny;
+    pixel_ndc(x, y, fw, fh, nx, ny);
     const float* M = c2w.m;
     const float pw = mul_row(M, 3, nx, ny, 1.0f, 1.0f);
     eye = V3{mul_row(M, 0, nx, ny, 1.0f, 1.0f) / pw, mul_row(M, 1, nx, ny, 1.0f, 1.0f) / pw, mul_row(M, 2, nx, ny, 1.0f, 1.0f) / pw};
@@ -60,33 +56,15 @@ __global__ __launch_bounds__(kBlock) void gbuffer_rays_kernel(Mat4 c2w, unsigned
     rays[2u * (size_t)i + 1u] = make_float4(dir.x, dir.y, dir.z, VD_MAX_DIST);
 }
 
-// What the resolve kernel gathers from and writes to: the pitches in bytes (size_t: a row offset may pass 4 GiB).
+// What the resolve kernel gathers from (it writes to vd_shade.hpp's Target).
 struct Geometry {
     const VdInstance* instances; const VdMeshInfo* meshes; const float* vertices; const uint32_t* indices; const float* normals; const float* tex_coords;
     unsigned n_instances, n_meshes, n_vertices, n_indices;
-};
-struct Target {
-    char* depth; char* normal_uv; uint8_t* material;
-    size_t depth_pitch, normal_uv_pitch, material_pitch;
-    unsigned width, n_pixels;
 };
 
 __device__ __forceinline__ V3 load3(const float* p, unsigned id) { const float* q = p + 3u * (size_t)id; return V3{q[0], q[1], q[2]}; }
 // (a * ((1 - u) - v) + b * u) + c * v
 __device__ __forceinline__ float bary(float a, float b, float c, float w, float u, float v) { return (a * w + b * u) + c * v; }
-__device__ __forceinline__ float sign1(float a) { return a < 0.0f ? -1.0f : 1.0f; }      // the fold's sign: 0 (and a NaN) count as +1
-// floor((q * 0.5 + 0.5) * 65535 + 0.5) as a 16-bit code: a NaN -> 0, clamped to [0, 65535]
-__device__ __forceinline__ unsigned oct_code(float q) {
-    const float d = floorf((q * 0.5f + 0.5f) * 65535.0f + 0.5f);
-    return (unsigned)fminf(fmaxf(d, 0.0f), 65535.0f);      // fmaxf(NaN, 0) = 0
-}
-// encode_octahedral_32 (encoding.wgsl:4-15) with the header's two departures
-__device__ __forceinline__ unsigned encode_octahedral(V3 n) {
-    const V3 q = over(n, (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z));
-    float ox = q.x, oy = q.y;
-    if (q.z < 0.0f) { ox = (1.0f - fabsf(q.y)) * sign1(q.x); oy = (1.0f - fabsf(q.x)) * sign1(q.y); }
-    return (oct_code(oy) << 16) | oct_code(ox);
-}
 // one half of pack2x16float: the round-to-nearest-even convert (v_cvt_f16_f32 under the default mode; f16 subnormals are kept)
 __device__ __forceinline__ unsigned half_bits(float f) {
     const _Float16 h = (_Float16)f;
@@ -171,35 +149,13 @@ __global__ __launch_bounds__(kBlock) void gbuffer_resolve_kernel(Camera cam, Geo
             }
         }
     }
-    *reinterpret_cast<float*>(t.depth + (size_t)y * t.depth_pitch + 4u * (size_t)x) = depth;
-    *reinterpret_cast<uint2*>(t.normal_uv + (size_t)y * t.normal_uv_pitch + 8u * (size_t)x) = words;
-    t.material[(size_t)y * t.material_pitch + x] = (uint8_t)material;
-}
-
-int fail(VdCtx* ctx, const char* name, const char* what) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
-    return VD_ERR_INVALID_ARG;
-}
-
-// The pixel count of an image that is not empty: width * height <= 2^30.
-int check_size(VdCtx* ctx, const char* name, uint32_t width, uint32_t height) {
-    return (uint64_t)width * height > kMaxPixels ? fail(ctx, name, "width * height exceeds 2^30") : VD_OK;
-}
-
-// The checks of the images: tg is not null and neither size is zero.  VdGBuffer's rules.
-int check_target(VdCtx* ctx, const char* name, const VdGBufferTarget* tg) {
-    if (!tg->depth || !tg->normal_uv || !tg->material) return fail(ctx, name, "null pointer");
-    int rc = check_size(ctx, name, tg->width, tg->height);
-    if (rc) return rc;
-    if (tg->depth_pitch % 4u || (uint64_t)tg->depth_pitch < 4ull * tg->width) return fail(ctx, name, "depth_pitch is below 4 * width or not a multiple of 4");
-    if (tg->normal_uv_pitch % 8u || (uint64_t)tg->normal_uv_pitch < 8ull * tg->width)
-        return fail(ctx, name, "normal_uv_pitch is below 8 * width or not a multiple of 8");
-    if (tg->material_pitch < tg->width) return fail(ctx, name, "material_pitch is below width");
-    return VD_OK;
+    *t.depth_at(x, y) = depth;
+    *reinterpret_cast<uint2*>(t.normal_uv_at(x, y)) = words;      // the pair in one store
+    *t.material_at(x, y) = (uint8_t)material;
 }
 
 int check_geometry(VdCtx* ctx, const char* name, const VdGBufferGeometry* g) {
-    return !g->instances || !g->meshes || !g->vertices || !g->indices ? fail(ctx, name, "null pointer") : VD_OK;
+    return !g->instances || !g->meshes || !g->vertices || !g->indices ? vd_fail_arg(ctx, name, "null pointer") : VD_OK;
 }
 
 Mat4 mat4(const float* m) { Mat4 r; memcpy(r.m, m, sizeof(r.m)); return r; }
@@ -217,9 +173,7 @@ int launch_resolve(VdCtx* ctx, const VdCameraUniform* camera, const VdGBufferGeo
     const unsigned n = tg->width * tg->height;
     const Camera cam = {mat4(camera->clip_to_world), mat4(camera->view), mat4(camera->projection)};
     const Geometry geo = {g->instances, g->meshes, g->vertices, g->indices, g->normals, g->tex_coords, g->n_instances, g->n_meshes, g->n_vertices, g->n_indices};
-    const Target t = {reinterpret_cast<char*>(tg->depth), reinterpret_cast<char*>(tg->normal_uv), tg->material, tg->depth_pitch, tg->normal_uv_pitch, tg->material_pitch,
-                      tg->width, n};
-    hipLaunchKernelGGL(gbuffer_resolve_kernel, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, ctx->stream, cam, geo, t, (float)tg->width, (float)tg->height,
+    hipLaunchKernelGGL(gbuffer_resolve_kernel, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, ctx->stream, cam, geo, vd_images<char>(tg), (float)tg->width, (float)tg->height,
                        reinterpret_cast<const uint4*>(d_hits));
     VD_HIP_CHECK(ctx, hipGetLastError());
     return VD_OK;
@@ -228,18 +182,14 @@ int launch_resolve(VdCtx* ctx, const VdCameraUniform* camera, const VdGBufferGeo
 // Both composed forms: exactly one of scene / accel is given (the entry points have checked that it is not null).
 int gbuffer_trace(VdCtx* ctx, const char* name, const VdTraceScene* scene, const VdTraceAccel* accel, const VdGBufferGeometry* g, const VdCameraUniform* camera,
                   const VdGBufferTarget* tg) {
-    if (!tg) return fail(ctx, name, "null pointer");
+    if (!tg) return vd_fail_arg(ctx, name, "null pointer");
     if (tg->width == 0 || tg->height == 0) return VD_OK;
-    if (!camera) return fail(ctx, name, "null pointer");
-    int rc = check_target(ctx, name, tg);
+    if (!camera) return vd_fail_arg(ctx, name, "null pointer");
+    int rc = vd_check_images(ctx, name, tg);
     if (rc || (rc = check_geometry(ctx, name, g))) return rc;
     const unsigned n = tg->width * tg->height;
-    Arena a{nullptr, 0};
-    a.take<VdRay>(n); a.take<VdHit>(n);
-    if ((rc = vd_ensure(ctx, &ctx->gbuffer_trace.state, &ctx->gbuffer_trace.bytes, a.off))) return rc;
-    a = Arena{static_cast<char*>(ctx->gbuffer_trace.state), 0};
-    VdRay* d_rays = a.take<VdRay>(n);
-    VdHit* d_hits = a.take<VdHit>(n);
+    VdRay* d_rays = nullptr; VdHit* d_hits = nullptr;
+    if ((rc = vd_carve(ctx, &ctx->gbuffer_trace, [&](Arena& a) { d_rays = a.take<VdRay>(n); d_hits = a.take<VdHit>(n); }))) return rc;
     if ((rc = launch_rays(ctx, camera, tg->width, tg->height, d_rays))) return rc;
     rc = scene ? vd_trace_dev(ctx, scene, d_rays, n, d_hits) : vd_trace_prepared_dev(ctx, accel, d_rays, n, d_hits);
     if (rc) return rc;
@@ -255,8 +205,8 @@ int vd_gbuffer_rays_dev(VdCtx* ctx, const VdCameraUniform* camera, uint32_t widt
     if (!ctx) return VD_ERR_INVALID_ARG;
     const char* name = "vd_gbuffer_rays";
     if (width == 0 || height == 0) return VD_OK;
-    if (!camera || !d_rays) return fail(ctx, name, "null pointer");
-    const int rc = check_size(ctx, name, width, height);
+    if (!camera || !d_rays) return vd_fail_arg(ctx, name, "null pointer");
+    const int rc = vd_check_pixels(ctx, name, width, height);
     return rc ? rc : launch_rays(ctx, camera, width, height, d_rays);
 }
 
@@ -264,10 +214,10 @@ int vd_gbuffer_resolve_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdGB
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
     const char* name = "vd_gbuffer_resolve";
-    if (!target) return fail(ctx, name, "null pointer");
+    if (!target) return vd_fail_arg(ctx, name, "null pointer");
     if (target->width == 0 || target->height == 0) return VD_OK;
-    if (!camera || !geometry || !d_hits) return fail(ctx, name, "null pointer");
-    int rc = check_target(ctx, name, target);
+    if (!camera || !geometry || !d_hits) return vd_fail_arg(ctx, name, "null pointer");
+    int rc = vd_check_images(ctx, name, target);
     if (rc || (rc = check_geometry(ctx, name, geometry))) return rc;
     return launch_resolve(ctx, camera, geometry, d_hits, target);
 }
@@ -276,7 +226,7 @@ int vd_gbuffer_trace_dev(VdCtx* ctx, const VdTraceScene* d_scene, const float* d
                          const VdGBufferTarget* target) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!d_scene) return fail(ctx, "vd_gbuffer_trace", "null scene");
+    if (!d_scene) return vd_fail_arg(ctx, "vd_gbuffer_trace", "null scene");
     const VdGBufferGeometry g = {d_scene->instances, d_scene->n_instances, d_scene->meshes, d_scene->n_meshes, d_scene->vertices, d_scene->n_vertices,
                                  d_scene->indices, d_scene->n_indices, d_normals, d_tex_coords};
     return gbuffer_trace(ctx, "vd_gbuffer_trace", d_scene, nullptr, &g, camera, target);
@@ -286,8 +236,8 @@ int vd_gbuffer_trace_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const V
                                   const VdGBufferTarget* target) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!accel) return fail(ctx, "vd_gbuffer_trace_prepared", "null accel");
-    if (!geometry) return fail(ctx, "vd_gbuffer_trace_prepared", "null pointer");
+    if (!accel) return vd_fail_arg(ctx, "vd_gbuffer_trace_prepared", "null accel");
+    if (!geometry) return vd_fail_arg(ctx, "vd_gbuffer_trace_prepared", "null pointer");
     return gbuffer_trace(ctx, "vd_gbuffer_trace_prepared", nullptr, accel, geometry, camera, target);
 }
 

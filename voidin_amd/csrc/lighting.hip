@@ -1,8 +1,9 @@
 // lighting.hip — the lighting pass (include/voidin_lighting.h): lines 79-117 of src/bin/raytraced_shadows.wgsl for a whole image -
 // the base colour, attenuation(), the diffuse and the specular term summed over the lights whose in-range bit is set, in ascending
 // order, the occlusion bit halving a term, the final clamp - and the composed calls, which run the pass of gbuffer.hip through its
-// exported entry points in front of it.  The decode of `pos` and `nor` is voidin_gbuffer.h's, restated here: gbuffer.hip does not
-// change.
+// exported entry points in front of it.  `pos`, `nor` and "this pixel receives" are voidin_gbuffer.h's, and the kernel calls the same
+// functions of vd_shade.hpp that gbuffer.hip makes its points with (pixel_ndc, decode_octahedral, receives_light): one copy of each.
+// The one exception is the matrix step of the position, kept as text in the kernel for a measured reason stated there.
 //
 //   lighting_kernel   ONE PIXEL PER LANE, lane -> pixel i = block * 128 + thread; one 16-byte store a pixel.
 //
@@ -17,27 +18,16 @@
 // stride keeps the per-lane reads of the walk (lane * stride + w) off each other's banks.  The region belongs to the wave alone,
 // so there is no barrier - DS operations of one wave execute in order.  2 * 64 * (W | 1) words a wave: 33 KiB a workgroup at W = 32.
 // No atomics, no scratch.
-#include "vd_common.hpp"
+#include "vd_shade.hpp"
 #include "../../include/voidin_lighting.h"
 
 namespace {
 
 constexpr unsigned kBlock = 128u;                       // two waves: at W = 32 their bit words take 33 KiB of LDS
-constexpr unsigned kMaxPixels = 1u << 30;
 constexpr unsigned kStageSteps = 4u;                    // loads of 64 words in flight per array while a run is staged
 
-// The images as the kernel takes them: the pitches in bytes (size_t: a row offset may pass 4 GiB), the sizes.
-struct Images {
-    const char* depth; const char* normal_uv; const uint8_t* material;
-    size_t depth_pitch, normal_uv_pitch, material_pitch;
-    unsigned width, n_pixels;
-};
-struct View { float c2w[16]; float eye[3]; };           // clip_to_world, column-major; view_position.xyz
+struct View { Mat4 c2w; float eye[3]; };                // clip_to_world; view_position.xyz
 
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 over(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
 __device__ __forceinline__ float pos0(float x) { return x > 0.0f ? x : 0.0f; }      // a NaN gives 0
 
 typedef float StoreF4 __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes in one store at the alignment of a float
@@ -69,9 +59,9 @@ __global__ __launch_bounds__(kBlock) void lighting_kernel(Images im, View view, 
     unsigned material = VD_GBUFFER_NO_MATERIAL, n32 = 0u, in01[2] = {0u, 0u}, oc01[2] = {0u, 0u};
     float depth = 0.0f;
     if (valid) {
-        material = im.material[(size_t)y * im.material_pitch + x];
-        depth = *reinterpret_cast<const float*>(im.depth + (size_t)y * im.depth_pitch + 4u * (size_t)x);
-        n32 = *reinterpret_cast<const uint32_t*>(im.normal_uv + (size_t)y * im.normal_uv_pitch + 8u * (size_t)x);
+        material = *im.material_at(x, y);
+        depth = *im.depth_at(x, y);
+        n32 = *im.normal_uv_at(x, y);
         if (words == 1u) { in01[0] = in_range[i]; oc01[0] = occluded[i]; }
         if (words == 2u) { in01[0] = in_range[2u * (size_t)i]; in01[1] = in_range[2u * (size_t)i + 1u]; oc01[0] = occluded[2u * (size_t)i]; oc01[1] = occluded[2u * (size_t)i + 1u]; }
     }
@@ -105,26 +95,22 @@ __global__ __launch_bounds__(kBlock) void lighting_kernel(Images im, View view, 
         vd_wave_lds_sync();
     }
 
-    // voidin_gbuffer.h's pos and nor (uv.wgsl:1-3, 13-22; encoding.wgsl:17-28)
-    const float fw = (float)im.width, fh = (float)(im.n_pixels / im.width);
-    const float ux = ((float)x + 0.5f) / fw, uy = ((float)y + 0.5f) / fh;
-    const float nx = ux * 2.0f - 1.0f, ny = (1.0f - uy) * 2.0f - 1.0f, nz = depth;
-    const float* C = view.c2w;
+    // voidin_gbuffer.h's pos and nor.  The matrix step is position_from_depth's (vd_shade.hpp), spelled out: through the function - by
+    // reference, by value, split from the NDC step or with its components returned through references, all the same code - the compiler
+    // fetches the matrix at the kernel's start and keeps it (70 SGPRs for 62), and at 64 lights all in range the kernel's median was
+    // 204.9 / 206.4 us against the parent's 201.6 / 200.0 (profiles/shading_shared.md, section 2).  As written here the kernel is the
+    // parent's instruction for instruction.
+    float nx, ny;
+    pixel_ndc(x, y, (float)im.width, (float)(im.n_pixels / im.width), nx, ny);
+    const float* C = view.c2w.m;
     float w4[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) w4[r] = ((C[r] * nx + C[4 + r] * ny) + C[8 + r] * nz) + C[12 + r];
+    for (int r = 0; r < 4; ++r) w4[r] = ((C[r] * nx + C[4 + r] * ny) + C[8 + r] * depth) + C[12 + r];
     const V3 pos = V3{w4[0] / w4[3], w4[1] / w4[3], w4[2] / w4[3]};
-    float vx = (float)(n32 & 0xffffu) / 65535.0f, vy = (float)((n32 >> 16) & 0xffffu) / 65535.0f;
-    vx = vx * 2.0f - 1.0f; vy = vy * 2.0f - 1.0f;
-    float ax = vx, ay = vy;
-    const float az = (1.0f - fabsf(vx)) - fabsf(vy);
-    const float tt = (-az > 0.0f) ? -az : 0.0f;
-    ax += (ax > 0.0f) ? -tt : tt;
-    ay += (ay > 0.0f) ? -tt : tt;
-    const V3 nor = over(V3{ax, ay, az}, sqrtf((ax * ax + ay * ay) + az * az));
+    const V3 nor = decode_octahedral(n32);
 
     // lines 79-86: the base colour and the specular factor of the pixel
-    const bool lit = material != VD_GBUFFER_NO_MATERIAL && material != VD_GBUFFER_LIGHT_MATERIAL;
+    const bool lit = receives_light(material);
     V3 c;
     if (lit) c = V3{M.albedo[0] * 0.3f + M.emissive[0], M.albedo[1] * 0.3f + M.emissive[1], M.albedo[2] * 0.3f + M.emissive[2]};
     else c = V3{M.albedo[0] + M.emissive[0], M.albedo[1] + M.emissive[1], M.albedo[2] + M.emissive[2]};
@@ -166,28 +152,18 @@ __global__ __launch_bounds__(kBlock) void lighting_kernel(Images im, View view, 
     if (valid) *reinterpret_cast<StoreF4*>(rgba + (size_t)y * pitch + 16u * (size_t)x) = out;
 }
 
-int fail(VdCtx* ctx, const char* name, const char* what) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
-    return VD_ERR_INVALID_ARG;
-}
-
 // Everything the step refuses but the two bit arrays.  *empty: the image has no pixel - VD_OK, nothing to do.
 int check(VdCtx* ctx, const char* name, const VdCameraUniform* camera, const VdGBuffer* gb, const VdLight* d_lights, uint32_t n_lights,
           const VdFlatMaterial* d_materials, const VdColorTarget* tg, bool* empty) {
     *empty = false;
-    if (!gb || !tg) return fail(ctx, name, "null pointer");
-    if (tg->width != gb->width || tg->height != gb->height) return fail(ctx, name, "the target's size is not the G-buffer's");
+    if (!gb || !tg) return vd_fail_arg(ctx, name, "null pointer");
+    if (tg->width != gb->width || tg->height != gb->height) return vd_fail_arg(ctx, name, "the target's size is not the G-buffer's");
     if (gb->width == 0 || gb->height == 0) { *empty = true; return VD_OK; }
-    if (!camera || !d_materials || !tg->rgba || (n_lights && !d_lights)) return fail(ctx, name, "null pointer");
-    // VdGBuffer's rules (voidin_gbuffer.h)
-    if (!gb->depth || !gb->normal_uv || !gb->material) return fail(ctx, name, "null pointer");
-    if ((uint64_t)gb->width * gb->height > kMaxPixels) return fail(ctx, name, "width * height exceeds 2^30");
-    if (gb->depth_pitch % 4u || (uint64_t)gb->depth_pitch < 4ull * gb->width) return fail(ctx, name, "depth_pitch is below 4 * width or not a multiple of 4");
-    if (gb->normal_uv_pitch % 8u || (uint64_t)gb->normal_uv_pitch < 8ull * gb->width)
-        return fail(ctx, name, "normal_uv_pitch is below 8 * width or not a multiple of 8");
-    if (gb->material_pitch < gb->width) return fail(ctx, name, "material_pitch is below width");
-    if (tg->pitch % 16u || (uint64_t)tg->pitch < 16ull * tg->width) return fail(ctx, name, "the target's pitch is below 16 * width or not a multiple of 16");
-    if (n_lights > VD_SHADOW_MAX_LIGHTS) return fail(ctx, name, "more than VD_SHADOW_MAX_LIGHTS lights");
+    if (!camera || !d_materials || !tg->rgba || (n_lights && !d_lights)) return vd_fail_arg(ctx, name, "null pointer");
+    const int rc = vd_check_images(ctx, name, gb);
+    if (rc) return rc;
+    if (tg->pitch % 16u || (uint64_t)tg->pitch < 16ull * tg->width) return vd_fail_arg(ctx, name, "the target's pitch is below 16 * width or not a multiple of 16");
+    if (n_lights > VD_SHADOW_MAX_LIGHTS) return vd_fail_arg(ctx, name, "more than VD_SHADOW_MAX_LIGHTS lights");
     return VD_OK;
 }
 
@@ -195,10 +171,9 @@ int check(VdCtx* ctx, const char* name, const VdCameraUniform* camera, const VdG
 int launch(VdCtx* ctx, const VdCameraUniform* camera, const VdGBuffer* gb, const VdLight* d_lights, uint32_t n_lights, const uint32_t* d_occluded,
            const uint32_t* d_in_range, const VdFlatMaterial* d_materials, const VdColorTarget* tg) {
     const unsigned n = gb->width * gb->height, words = (n_lights + 31u) / 32u;
-    const Images im = {reinterpret_cast<const char*>(gb->depth), reinterpret_cast<const char*>(gb->normal_uv), gb->material, gb->depth_pitch, gb->normal_uv_pitch,
-                       gb->material_pitch, gb->width, n};
+    const Images im = vd_images<const char>(gb);
     View view;
-    memcpy(view.c2w, camera->clip_to_world, sizeof(view.c2w));
+    memcpy(view.c2w.m, camera->clip_to_world, sizeof(view.c2w.m));
     memcpy(view.eye, camera->view_position, sizeof(view.eye));
     const size_t lds = words > 2u ? (size_t)(kBlock / 64u) * 128u * (words | 1u) * sizeof(unsigned) : 0;
     hipLaunchKernelGGL(lighting_kernel, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), lds, ctx->stream, im, view, d_lights, n_lights, words, d_occluded, d_in_range,
@@ -218,13 +193,9 @@ int shade_gbuffer(VdCtx* ctx, const char* name, const VdTraceScene* scene, const
     uint32_t* d_occ = nullptr; uint32_t* d_inr = nullptr;
     if (n_lights) {
         // (the pass would refuse this itself, but only after the arena below had been sized by it)
-        if ((uint64_t)gb->width * gb->height * n_lights > 0xf0000000ull) return fail(ctx, name, "width * height * n_lights exceeds 0xf0000000");
+        if ((uint64_t)gb->width * gb->height * n_lights > kMaxPairs) return vd_fail_arg(ctx, name, "width * height * n_lights exceeds 0xf0000000");
         const size_t n = (size_t)gb->width * gb->height * ((n_lights + 31u) / 32u);
-        Arena a{nullptr, 0};
-        a.take<uint32_t>(n); a.take<uint32_t>(n);
-        if ((rc = vd_ensure(ctx, &ctx->lighting.state, &ctx->lighting.bytes, a.off))) return rc;
-        a = Arena{static_cast<char*>(ctx->lighting.state), 0};
-        d_occ = a.take<uint32_t>(n); d_inr = a.take<uint32_t>(n);
+        if ((rc = vd_carve(ctx, &ctx->lighting, [&](Arena& a) { d_occ = a.take<uint32_t>(n); d_inr = a.take<uint32_t>(n); }))) return rc;
         rc = scene ? vd_shadow_gbuffer_dev(ctx, scene, camera, gb, d_lights, n_lights, max_chunk_rays, d_occ, d_inr, out_info)
                    : vd_shadow_gbuffer_prepared_dev(ctx, accel, camera, gb, d_lights, n_lights, max_chunk_rays, d_occ, d_inr, out_info);
         if (rc) return rc;
@@ -246,7 +217,7 @@ int vd_lighting_dev(VdCtx* ctx, const VdCameraUniform* camera, const VdGBuffer* 
     bool empty;
     const int rc = check(ctx, name, camera, gb, d_lights, n_lights, d_materials, target, &empty);
     if (rc || empty) return rc;
-    if (n_lights && (!d_occluded || !d_in_range)) return fail(ctx, name, "null pointer");
+    if (n_lights && (!d_occluded || !d_in_range)) return vd_fail_arg(ctx, name, "null pointer");
     return launch(ctx, camera, gb, d_lights, n_lights, d_occluded, d_in_range, d_materials, target);
 }
 
@@ -254,7 +225,7 @@ int vd_shade_gbuffer_dev(VdCtx* ctx, const VdTraceScene* d_scene, const VdCamera
                          uint32_t max_chunk_rays, const VdFlatMaterial* d_materials, const VdColorTarget* target, VdShadowGBufferInfo* out_info) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!d_scene) return fail(ctx, "vd_shade_gbuffer", "null scene");
+    if (!d_scene) return vd_fail_arg(ctx, "vd_shade_gbuffer", "null scene");
     return shade_gbuffer(ctx, "vd_shade_gbuffer", d_scene, nullptr, camera, gb, d_lights, n_lights, max_chunk_rays, d_materials, target, out_info);
 }
 
@@ -263,7 +234,7 @@ int vd_shade_gbuffer_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const V
                                   VdShadowGBufferInfo* out_info) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!accel) return fail(ctx, "vd_shade_gbuffer_prepared", "null accel");
+    if (!accel) return vd_fail_arg(ctx, "vd_shade_gbuffer_prepared", "null accel");
     return shade_gbuffer(ctx, "vd_shade_gbuffer_prepared", nullptr, accel, camera, gb, d_lights, n_lights, max_chunk_rays, d_materials, target, out_info);
 }
 

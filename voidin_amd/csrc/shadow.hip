@@ -18,8 +18,9 @@
 //                         a read-modify-write ACROSS launches; the chunk that holds the word's first light writes without reading,
 //                         which is why the result does not depend on what the buffers held.
 //
-// The three tile kernels share one skeleton (ShadowTile) and one copy of the range test (shadow_in_range).
-#include "vd_common.hpp"
+// The three tile kernels share one skeleton (ShadowTile) and one copy of the range test (shadow_in_range); the scan itself, the pair
+// limit and the arena helper are vd_shade.hpp's, shared with the passes built on this one.
+#include "vd_shade.hpp"
 #include "../../include/voidin_shadow.h"
 
 namespace {
@@ -27,7 +28,6 @@ namespace {
 constexpr unsigned kPerLane = 8u;                       // points per lane
 constexpr unsigned kTilePoints = 64u * kPerLane;        // points per tile = per wave
 constexpr unsigned kTileWaves = 4u;                     // waves (tiles) per workgroup
-constexpr unsigned kScanThreads = 1024u, kScanItems = 4u;
 constexpr unsigned kDefaultChunkRays = 4u << 20;
 
 // raytraced_shadows.wgsl:90-92: `if dist - light.radius > 0. { continue; }` - negated, so that a NaN is in range
@@ -93,34 +93,10 @@ __global__ __launch_bounds__(64 * kTileWaves) void shadow_count_kernel(const flo
     });
 }
 
-// offsets[i] = count[0] + ... + count[i - 1] for i in [0, n]: ONE workgroup, kScanThreads * kScanItems counts per round.
+// offsets[i] = count[0] + ... + count[i - 1] for i in [0, n]: ONE workgroup (vd_block_scan).
 __global__ __launch_bounds__(kScanThreads) void shadow_scan_kernel(const unsigned* __restrict__ count, unsigned n, unsigned* __restrict__ offsets) {
-    __shared__ unsigned wave_sum[kScanThreads / 64u];
-    const unsigned lane = vd_lane(), wave = threadIdx.x >> 6;
-    unsigned carry = 0u;
-    for (unsigned base = 0; base < n; base += kScanThreads * kScanItems) {
-        const unsigned i0 = base + threadIdx.x * kScanItems;
-        unsigned v[kScanItems], mine = 0u;
-#pragma unroll
-        for (unsigned q = 0; q < kScanItems; ++q) { v[q] = i0 + q < n ? count[i0 + q] : 0u; mine += v[q]; }
-        unsigned incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned o = __shfl_up(incl, off);
-            if (lane >= (unsigned)off) incl += o;
-        }
-        if (lane == 63u) wave_sum[wave] = incl;
-        __syncthreads();
-        unsigned before = carry, total = 0u;
-#pragma unroll
-        for (unsigned w = 0; w < kScanThreads / 64u; ++w) { const unsigned s = wave_sum[w]; before += w < wave ? s : 0u; total += s; }
-        unsigned run = before + incl - mine;
-#pragma unroll
-        for (unsigned q = 0; q < kScanItems; ++q) { if (i0 + q < n) offsets[i0 + q] = run; run += v[q]; }
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u) offsets[n] = carry;
+    const unsigned total = vd_block_scan(count, n, offsets);
+    if (threadIdx.x == 0u) offsets[n] = total;
 }
 
 // What the per-chunk kernels are told: the chunk's cells [c0, c1), the ray offset of c0, and the tiles those cells touch.
@@ -192,36 +168,27 @@ __global__ __launch_bounds__(64 * kTileWaves) void shadow_fold_kernel(const floa
     });
 }
 
-int shadow_fail(VdCtx* ctx, const char* name, const char* what) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
-    return VD_ERR_INVALID_ARG;
-}
-
 // Both forms: exactly one of scene / accel is given (the entry points have checked that it is not null).
 int shadow_pass(VdCtx* ctx, const char* name, const VdTraceScene* scene, const VdTraceAccel* accel, const float* d_pos, const float* d_nor, uint32_t n_points,
                 const VdLight* d_lights, uint32_t n_lights, uint32_t max_chunk_rays, uint32_t* d_occluded, uint32_t* d_in_range, VdShadowPassInfo* out_info) {
     if (out_info) memset(out_info, 0, sizeof(*out_info));
     if (n_points == 0 || n_lights == 0) return VD_OK;
-    if (!d_pos || !d_nor || !d_lights || !d_occluded) return shadow_fail(ctx, name, "null pointer");
-    if (n_lights > VD_SHADOW_MAX_LIGHTS) return shadow_fail(ctx, name, "more than VD_SHADOW_MAX_LIGHTS lights");
-    if ((uint64_t)n_points * n_lights > 0xf0000000ull) return shadow_fail(ctx, name, "n_points * n_lights exceeds 0xf0000000");
+    if (!d_pos || !d_nor || !d_lights || !d_occluded) return vd_fail_arg(ctx, name, "null pointer");
+    if (n_lights > VD_SHADOW_MAX_LIGHTS) return vd_fail_arg(ctx, name, "more than VD_SHADOW_MAX_LIGHTS lights");
+    if ((uint64_t)n_points * n_lights > kMaxPairs) return vd_fail_arg(ctx, name, "n_points * n_lights exceeds 0xf0000000");
     // what the walk refuses it refuses now, before anything is launched: a call without rays checks the scene and does nothing else
     int rc = scene ? vd_trace_any_dev(ctx, scene, nullptr, 0u, nullptr) : vd_trace_any_prepared_dev(ctx, accel, nullptr, 0u, nullptr);
     if (rc) return rc;
     const unsigned words = (n_lights + 31u) / 32u;
     const unsigned n_tiles = (n_points + kTilePoints - 1u) / kTilePoints;
-    const unsigned n_cells = n_tiles * n_lights;                       // <= 0xf0000000 / 512 + 1024
+    const unsigned n_cells = n_tiles * n_lights;                       // <= kMaxPairs / 512 + 1024
     const unsigned max_rays = max_chunk_rays ? max_chunk_rays : kDefaultChunkRays;
 
     // counts and offsets; the offsets come back through the pinned staging
-    Arena a{nullptr, 0};
-    a.take<unsigned>(n_cells); a.take<unsigned>((size_t)n_cells + 1u);
-    const size_t tables = (a.off + 255) & ~(size_t)255;
-    if ((rc = vd_ensure(ctx, &ctx->shadow.state, &ctx->shadow.bytes, tables))) return rc;
-    if ((rc = vd_ensure_host(ctx, ((size_t)n_cells + 1u) * 4u))) return rc;
-    a = Arena{static_cast<char*>(ctx->shadow.state), 0};
-    unsigned* d_count = a.take<unsigned>(n_cells);
-    unsigned* d_off = a.take<unsigned>((size_t)n_cells + 1u);
+    unsigned* d_count = nullptr; unsigned* d_off = nullptr;
+    size_t tables = 0;                                                 // where the tables end
+    rc = vd_carve(ctx, &ctx->shadow, [&](Arena& a) { d_count = a.take<unsigned>(n_cells); d_off = a.take<unsigned>((size_t)n_cells + 1u); tables = a.off; });
+    if (rc || (rc = vd_ensure_host(ctx, ((size_t)n_cells + 1u) * 4u))) return rc;
     const unsigned tile_blocks = (n_tiles + kTileWaves - 1u) / kTileWaves;
     hipLaunchKernelGGL(shadow_count_kernel, dim3(tile_blocks), dim3(64 * kTileWaves), 0, ctx->stream, d_pos, n_points, d_lights, n_lights, n_tiles, d_count);
     hipLaunchKernelGGL(shadow_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, d_count, n_cells, d_off);
@@ -244,6 +211,7 @@ int shadow_pass(VdCtx* ctx, const char* name, const VdTraceScene* scene, const V
     }
     VdRay* d_rays = nullptr; unsigned* d_hit = nullptr;
     if (largest) {
+        Arena a{static_cast<char*>(ctx->shadow.state), tables};
         a.take<VdRay>(largest); a.take<unsigned>(largest);
         // growing moves the tables: the stream is idle and the host holds the offsets, so the counts may go and the offsets are put back
         if (a.off > ctx->shadow.bytes) {
@@ -290,7 +258,7 @@ int vd_shadow_pass_dev(VdCtx* ctx, const VdTraceScene* d_scene, const float* d_p
                        uint32_t n_lights, uint32_t max_chunk_rays, uint32_t* d_occluded, uint32_t* d_in_range, VdShadowPassInfo* out_info) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!d_scene) return shadow_fail(ctx, "vd_shadow_pass", "null scene");
+    if (!d_scene) return vd_fail_arg(ctx, "vd_shadow_pass", "null scene");
     return shadow_pass(ctx, "vd_shadow_pass", d_scene, nullptr, d_positions, d_normals, n_points, d_lights, n_lights, max_chunk_rays, d_occluded, d_in_range,
                        out_info);
 }
@@ -300,7 +268,7 @@ int vd_shadow_pass_prepared_dev(VdCtx* ctx, const VdTraceAccel* accel, const flo
                                 VdShadowPassInfo* out_info) {
     VdDeviceGuard vd_guard_(ctx);   // run on ctx->device whatever the calling thread's current device is
     if (!ctx) return VD_ERR_INVALID_ARG;
-    if (!accel) return shadow_fail(ctx, "vd_shadow_pass_prepared", "null accel");
+    if (!accel) return vd_fail_arg(ctx, "vd_shadow_pass_prepared", "null accel");
     return shadow_pass(ctx, "vd_shadow_pass_prepared", nullptr, accel, d_positions, d_normals, n_points, d_lights, n_lights, max_chunk_rays, d_occluded,
                        d_in_range, out_info);
 }

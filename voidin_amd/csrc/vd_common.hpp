@@ -22,26 +22,14 @@ struct VdRefitArena {
     unsigned n = 0;                     // instance count the arena's layout was last used with
 };
 
-// The shadow pass's grow-only device buffer (shadow.hip).  It frees itself where ctx.hip deletes the context (vd_ctx_destroy has
-// drained the stream and made the context's device current by then).
-struct VdShadowArena {
+// A self-freeing grow-only device buffer (sized through vd_carve below).  It frees itself where ctx.hip deletes the context
+// (vd_ctx_destroy has drained the stream and made the context's device current by then).
+struct VdDeviceBuffer {
     void* state = nullptr; size_t bytes = 0;
-    VdShadowArena() = default;
-    ~VdShadowArena() { if (state) (void)hipFree(state); }
-    VdShadowArena(const VdShadowArena&) = delete;
-    VdShadowArena& operator=(const VdShadowArena&) = delete;
-};
-
-// The G-buffer front end's grow-only device buffers (gbuffer.hip), freed the same way: the tile tables of an image, and the points of
-// a vd_shadow_gbuffer* call with their per-point words.  Two buffers, so that sizing the second by the count the first gave never
-// moves the tables.
-struct VdGBufferArena {
-    void* tables = nullptr; size_t tables_bytes = 0;
-    void* points = nullptr; size_t points_bytes = 0;
-    VdGBufferArena() = default;
-    ~VdGBufferArena() { if (tables) (void)hipFree(tables); if (points) (void)hipFree(points); }
-    VdGBufferArena(const VdGBufferArena&) = delete;
-    VdGBufferArena& operator=(const VdGBufferArena&) = delete;
+    VdDeviceBuffer() = default;
+    ~VdDeviceBuffer() { if (state) (void)hipFree(state); }
+    VdDeviceBuffer(const VdDeviceBuffer&) = delete;
+    VdDeviceBuffer& operator=(const VdDeviceBuffer&) = delete;
 };
 
 struct VdCtx {
@@ -73,10 +61,11 @@ struct VdCtx {
     void* trace_wide = nullptr;  size_t trace_wide_bytes = 0;     // vd_trace_wide*: the per-call records of a wide top level (64 B per node), mesh records, triangles, fan-out
     void* lbvh_state = nullptr;  size_t lbvh_state_bytes = 0;     // vd_tlas_build_lbvh*: leaf boxes, codes, the sort's tables, parent links, arrival words
     void* blas_lbvh_state = nullptr; size_t blas_lbvh_state_bytes = 0;   // vd_bvh_build_lbvh*: triangle boxes, the index copy, the sort's work memory, the radix tree
-    VdShadowArena shadow;                                         // vd_shadow_pass*: cell counts and offsets, then the rays and hit flags of one chunk (not `scratch`: the walk's arena)
-    VdGBufferArena gbuffer;                                       // vd_gbuffer_points_dev / vd_shadow_gbuffer*: tile counts and offsets; points, normals, pixel ids, per-point words
-    VdShadowArena gbuffer_trace;                                  // vd_gbuffer_trace*: the rays and hit records of one image (gbuffer_trace.hip; the same self-freeing buffer)
-    VdShadowArena lighting;                                       // vd_shade_gbuffer*: the two per-pixel bit arrays between the pass and the lighting step (lighting.hip)
+    VdDeviceBuffer shadow;                                        // vd_shadow_pass*: cell counts and offsets, then the rays and hit flags of one chunk (not `scratch`: the walk's arena)
+    VdDeviceBuffer gbuffer_tables, gbuffer_points;                // vd_gbuffer_points_dev / vd_shadow_gbuffer*: tile counts and offsets | points, normals, pixel ids, per-point words.
+                                                                  // Two buffers, so that sizing the second by the count the first gave never moves the tables
+    VdDeviceBuffer gbuffer_trace;                                 // vd_gbuffer_trace*: the rays and hit records of one image (gbuffer_trace.hip)
+    VdDeviceBuffer lighting;                                      // vd_shade_gbuffer*: the two per-pixel bit arrays between the pass and the lighting step (lighting.hip)
     VdRefitArena refit;                                           // vd_tlas_refit*: links + arrival words
     const void* fan_tlas = nullptr; unsigned fan_idle_calls = 0;  // traversal fan-out: top level of the last call that tried it, calls left to run without it
     unsigned fan_nodes = 0, fan_inst = 0;                         // ... and its node / instance counts: the verdict is about THAT scene
@@ -135,6 +124,12 @@ struct VdDeviceGuard {
         snprintf((ctx)->err, sizeof((ctx)->err), "%s", (msg));           \
         return (code);                                                   \
     } while (0)
+
+// "<name>: <what>" -> VD_ERR_INVALID_ARG: what an entry point answers to an argument it refuses.
+static inline int vd_fail_arg(VdCtx* ctx, const char* name, const char* what) {
+    snprintf(ctx->err, sizeof(ctx->err), "%s: %s", name, what);
+    return VD_ERR_INVALID_ARG;
+}
 
 // Grow-only arena helper. Never called between a kernel's enqueue and its completion on the
 // same buffer without a stream sync (callers sync before growing).
@@ -244,6 +239,19 @@ struct Arena {
         return p;
     }
 };
+
+// Sizes and carves a buffer from ONE statement of its layout: `layout(Arena&)` takes the arrays in order and keeps the pointers.  It
+// runs once over a null base (the pointers mean nothing yet), the buffer grows to what that took - draining the stream first when it
+// has to move, see vd_ensure - and it runs again over the real base.
+template <typename F> static inline int vd_carve(VdCtx* ctx, VdDeviceBuffer* buf, F&& layout) {
+    Arena a{nullptr, 0};
+    layout(a);
+    const int rc = vd_ensure(ctx, &buf->state, &buf->bytes, a.off);
+    if (rc) return rc;
+    a = Arena{static_cast<char*>(buf->state), 0};
+    layout(a);
+    return VD_OK;
+}
 
 // ctx.hip: the device memory of a plan (vd_bvh_lbvh_plan_dev, vd_bvh_refit_plan_dev) - ONE allocation: the parts in order, each
 // 256-byte aligned (*dev = where it went), then `work_bytes` of work memory (*work; may be null when there is none).  The parts
