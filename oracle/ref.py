@@ -42,6 +42,7 @@ def load() -> C.CDLL:
             "vd_ref_tlas_refit_wide": (_I, [_P, _U, _P, _U, _P]),
             "vd_ref_trace": (_I, [C.POINTER(abi.TraceScene), _P, _U, _P, _P, _I]),
             "vd_ref_trace_depths": (_I, [C.POINTER(abi.TraceScene), _P, _U, _P, _P, _P, _P, _I]),
+            "vd_ref_trace_range": (_I, [C.POINTER(abi.TraceScene), _P, _U, _P, _I]),
             "vd_ref_traverse_iter": (_I, [_P, _U, _P, _P, _P, _U, _P]),
             "vd_ref_traverse_iter_depths": (_I, [_P, _U, _P, _P, _P, _U, _P, _P]),
             "vd_ref_traverse": (_I, [_P, _U, _P, _P, _P, _U, C.c_float, _P]),
@@ -176,6 +177,15 @@ def trace(scene_arrays, rays, threads=1, depths=False, first_hit=False):
     _chk(load().vd_ref_trace_depths(C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data, C.addressof(ms), far.ctypes.data,
                                     at_hit.ctypes.data if first_hit else None, threads))
     return (out, ms.value, far, at_hit) if first_hit else (out, ms.value, far)
+
+
+def trace_range(scene_arrays, rays, threads=1):
+    """The walk of trace() under "Ray intervals" of include/voidin_abi.h: every ray's _pad0 / _pad1 are its (t_min, t_max) -> hits."""
+    s, keep = make_scene(*scene_arrays)
+    rays = _c(rays, abi.RAY)
+    out = np.zeros(len(rays), dtype=abi.HIT)
+    _chk(load().vd_ref_trace_range(C.byref(s), rays.ctypes.data, len(rays), out.ctypes.data, threads))
+    return out
 
 
 def shadow_rays(positions, normals, light_position):

@@ -70,6 +70,12 @@ int vd_ref_trace(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, 
  * accepted - where an occlusion walk (vd_trace_any*) stops - or 0xffffffff for a ray that hits nothing.                  */
 int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
                         uint32_t* out_max_stack, uint32_t* out_far_depth, uint32_t* out_hit_pending, int threads);
+/* The same walk under "Ray intervals" of include/voidin_abi.h (VD_OPT_TRACE_RAY_RANGE), word for word: t_lo = fmaxf(_pad0, 0),
+ * t_hi = fminf(_pad1, MAX_DIST); the result starts at dist = t_hi, a triangle is accepted when t_lo < t && t < hit, the box
+ * tests and the pruning by the distance found so far are unchanged - so a box whose float32 entry distance is not below t_hi
+ * is not entered, whatever a triangle inside it would have given - and a miss holds MAX_DIST.  With (0, MAX_DIST) the bytes of
+ * vd_ref_trace.                                                                                                            */
+int vd_ref_trace_range(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out, int threads);
 /* crates/bvh/src/blas.rs:247-295 + intersection.rs:47-92 (R2, BLAS only, Rust CPU harness).
  * out_dist[i] = t, or -1 for Dist::Miss.                                                 */
 /* Shadow rays of src/bin/raytraced_shadows.wgsl:90-97: eye = pos + nor * 0.0001, dir = light - pos. */

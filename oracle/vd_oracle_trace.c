@@ -28,7 +28,7 @@
  * triangle was accepted (where an occlusion walk stops), 0xffffffff while none was. */
 typedef struct { uint32_t max_stack, far_depth, tl_pending, hit_pending; } walk_stat;
 
-typedef struct { v3 eye, dir, inv_dir; } ray_t;
+typedef struct { v3 eye, dir, inv_dir; float t_lo; } ray_t;      /* t_lo: 0, or the lower end of the ray's interval (vd_ref_trace_range) */
 
 static inline float min_element(v3 v) { return fminf(v.x, fminf(v.y, v.z)); }   /* math.wgsl:19-21 */
 static inline float max_element(v3 v) { return fmaxf(v.x, fmaxf(v.y, v.z)); }   /* math.wgsl:23-25 */
@@ -60,7 +60,7 @@ static inline int intersect_trig_wgsl(const ray_t* r, v3 v0, v3 v1, v3 v2, float
     float v = inv_det * v3_dot(r->dir, vvec);
     if (v < 0.0f || u + v > 1.0f) return 0;
     float t = inv_det * v3_dot(edge2, vvec);
-    if (t > 0.0f && t < *hit) {
+    if (t > r->t_lo && t < *hit) {
         *hit = t;
         return 1;
     }
@@ -132,15 +132,17 @@ static int instance_intersect(const VdTraceScene* s, const ray_t* ray, uint32_t 
     nr.eye = v3_make(e[0], e[1], e[2]);
     nr.dir = v3_make(d[0], d[1], d[2]);
     nr.inv_dir = v3_make(1.0f / nr.dir.x, 1.0f / nr.dir.y, 1.0f / nr.dir.z);
+    nr.t_lo = ray->t_lo;
     return traverse_bvh(s, &nr, mesh, res, inst_id, ws);
 }
 
-/* bvh.wgsl:89-123 */
-static int traverse_tlas(const VdTraceScene* s, const ray_t* ray, VdHit* res, walk_stat* ws) {
+/* bvh.wgsl:89-123; t_hi: the distance the result starts at - MAX_DIST there, the upper end of the ray's interval under
+ * "Ray intervals" of include/voidin_abi.h.  A miss holds MAX_DIST, never t_hi. */
+static int traverse_tlas(const VdTraceScene* s, const ray_t* ray, VdHit* res, walk_stat* ws, float t_hi) {
     uint32_t stack[REF_STACK];
     uint32_t head = 0;
     stack[head++] = 0u;
-    res->dist = VD_REF_MAX_DIST; res->hit = 0; res->instance = 0xffffffffu; res->triangle = 0xffffffffu;
+    res->dist = t_hi; res->hit = 0; res->instance = 0xffffffffu; res->triangle = 0xffffffffu;
     while (head > 0) {
         VdTlasNode node = s->tlas_nodes[stack[--head]];
         if (head > ws->far_depth) ws->far_depth = head;
@@ -166,12 +168,13 @@ static int traverse_tlas(const VdTraceScene* s, const ray_t* ray, VdHit* res, wa
             if (head > ws->max_stack) ws->max_stack = head;
         }
     }
+    if (!res->hit) res->dist = VD_REF_MAX_DIST;
     return VD_OK;
 }
 
 typedef struct {
     const VdTraceScene* s; const VdRay* rays; uint32_t begin, end; VdHit* out; uint32_t* far_depth; uint32_t* hit_pending;
-    uint32_t max_stack; int rc;
+    uint32_t max_stack; int rc; int ranged;
 } trace_job;
 
 static void* trace_thread(void* p) {
@@ -184,8 +187,11 @@ static void* trace_thread(void* p) {
         r.dir = v3_load(j->rays[i].dir);
         /* intersections.wgsl:9-11 ray_new: inv_dir = 1. / dir */
         r.inv_dir = v3_make(1.0f / r.dir.x, 1.0f / r.dir.y, 1.0f / r.dir.z);
+        /* include/voidin_abi.h, "Ray intervals": a NaN or negative t_min reads as 0, a NaN or oversized t_max as MAX_DIST */
+        r.t_lo = j->ranged ? fmaxf(j->rays[i]._pad0, 0.0f) : 0.0f;
+        const float t_hi = j->ranged ? fminf(j->rays[i]._pad1, VD_REF_MAX_DIST) : VD_REF_MAX_DIST;
         ws.far_depth = 0u; ws.tl_pending = 0u; ws.hit_pending = 0xffffffffu;
-        int rc = traverse_tlas(j->s, &r, &j->out[i], &ws);
+        int rc = traverse_tlas(j->s, &r, &j->out[i], &ws, t_hi);
         if (rc && !j->rc) j->rc = rc;
         if (j->far_depth) j->far_depth[i] = ws.far_depth;
         if (j->hit_pending) j->hit_pending[i] = ws.hit_pending;
@@ -199,8 +205,8 @@ int vd_ref_trace(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, 
     return vd_ref_trace_depths(scene, rays, n_rays, out, out_max_stack, NULL, NULL, threads);
 }
 
-int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
-                        uint32_t* out_max_stack, uint32_t* out_far_depth, uint32_t* out_hit_pending, int threads) {
+static int trace_all(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
+                     uint32_t* out_max_stack, uint32_t* out_far_depth, uint32_t* out_hit_pending, int threads, int ranged) {
     if (!scene || !scene->tlas_nodes || !scene->instances || !scene->meshes || !scene->bvh_nodes ||
         !scene->vertices || !scene->indices || (n_rays && (!rays || !out)))
         return VD_ERR_INVALID_ARG;
@@ -211,6 +217,7 @@ int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n
     trace_job job[256];
     for (int t = 0; t < threads; ++t) {
         job[t].s = scene; job[t].rays = rays; job[t].out = out; job[t].far_depth = out_far_depth; job[t].hit_pending = out_hit_pending;
+        job[t].ranged = ranged;
         job[t].begin = (uint32_t)((uint64_t)n_rays * t / threads);
         job[t].end = (uint32_t)((uint64_t)n_rays * (t + 1) / threads);
         if (threads == 1 || pthread_create(&tid[t], NULL, trace_thread, &job[t]) != 0) {
@@ -227,6 +234,15 @@ int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n
     }
     if (out_max_stack) *out_max_stack = ms;
     return rc;
+}
+
+int vd_ref_trace_depths(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out,
+                        uint32_t* out_max_stack, uint32_t* out_far_depth, uint32_t* out_hit_pending, int threads) {
+    return trace_all(scene, rays, n_rays, out, out_max_stack, out_far_depth, out_hit_pending, threads, 0);
+}
+
+int vd_ref_trace_range(const VdTraceScene* scene, const VdRay* rays, uint32_t n_rays, VdHit* out, int threads) {
+    return trace_all(scene, rays, n_rays, out, NULL, NULL, NULL, threads, 1);
 }
 
 /* ---------------- R2: Rust CPU harness variant (BLAS only) ---------------- */
